@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- Mpaths/s of the path-tracing hot path on MI355X (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload sponza-1080p]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload sponza-1080p] [--dump-outputs DIR] [--full]
   N > 1:  python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one RenderRound of the workload: every pixel of the frame gets `multisample`
@@ -18,10 +18,17 @@ sample count stay fixed and the centre-out tile list is dealt round-robin, so wi
 traces 1/N of the tiles (`--scaling weak` takes N x the samples per pixel instead: fixed work
 per GPU).
 
-The JSON line also carries `roofline` -- the binding ceiling of the dominant kernel with
-frac <= 1 (traversal: VALU issue; shading: HBM), per-kernel records under `kernels`, every
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`,
+`ms_per_step`, ...).  With `--full` the line also carries `roofline` -- the binding ceiling
+of the dominant kernel with frac <= 1 (traversal: VALU issue; shading: HBM), per-kernel
+records under `kernels` (HIP-event times inside the timed steps), `first_round_ms`, every
 profile-derived number with its source -- and, at N = 1, `cpu_baseline` (the CPU oracle
 timed on the host cores on a bounded tile sample).
+
+`--dump-outputs DIR` writes, after the timed steps, what they handed the caller: DIR/accum.npy
+(the frame's RGB sums, float32), DIR/count.npy (samples per pixel) and DIR/counters.npy (paths,
+path rays, shadow rays of the last step, all ranks), float64.  A frame above DUMP_BYTES is
+written as a fixed, seeded sample of its pixels, with their flat indices in DIR/pixel_index.npy.
 """
 import argparse
 import json
@@ -31,6 +38,7 @@ import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
+DUMP_BYTES = 60_000_000  # --dump-outputs: at most this much array data (64 MB with room to spare)
 
 
 def host_cores():
@@ -113,6 +121,26 @@ def self_launch(n, argv):
     return 0
 
 
+def dump_outputs(dirname, accum, count, last_counters):
+    """--dump-outputs: the accumulator a caller of the timed path receives (rank 0, after the reduce) and the last step's counters,
+    as .npy files.  Above DUMP_BYTES, the same seeded sample of pixels every run (it depends on the frame size only)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    acc = np.ascontiguousarray(accum, dtype=np.float32).reshape(-1, 3)
+    cnt = np.ascontiguousarray(count).view(np.uint32).reshape(-1).astype(np.float64)
+    arrays = {"accum": acc, "count": cnt}
+    if acc.nbytes + cnt.nbytes > DUMP_BYTES:
+        k = DUMP_BYTES // (acc.itemsize * 3 + cnt.itemsize + 8)
+        idx = np.sort(np.random.default_rng(0).choice(len(cnt), size=k, replace=False))
+        arrays = {"accum": acc[idx], "count": cnt[idx], "pixel_index": idx.astype(np.float64)}
+    else:
+        arrays["accum"] = acc.reshape(np.shape(accum))
+        arrays["count"] = cnt.reshape(np.shape(count))
+    arrays["counters"] = np.asarray(last_counters, dtype=np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -128,6 +156,9 @@ def main():
     ap.add_argument("--textures", choices=["u8", "f32"], default="u8", help="f32: hand every image texture over as floats, as a binding to the "
                     "reference does (FileTexture keeps only decoded floats); the core then stores those with <= 256 distinct values as bytes itself")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend; 'gloo' + RGK_FORCE_DEVICE=0 rehearses N ranks on one GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the accumulator and the last step's counters to DIR/*.npy")
+    ap.add_argument("--full", action="store_true", help="beside the headline: per-kernel times, first-round time, a counting round, the roofline "
+                    "and (N = 1, unless --no-cpu-baseline) the CPU baseline")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -182,7 +213,7 @@ def main():
         def get_params(sampler=capi.SAMPLER_HALTON, flags=0):
             return wl.params(sampler, flags)
 
-    drv = rd.RenderDriver(scene, Cfg, wl.camera, rank=rank, world_size=world, device=device, flags=capi.FLAG_TIME_KERNELS,
+    drv = rd.RenderDriver(scene, Cfg, wl.camera, rank=rank, world_size=world, device=device, flags=capi.FLAG_TIME_KERNELS if args.full else 0,
                           host_reduce=(args.backend != "nccl"))
 
     if args.emulate_shard > 1:  # what one rank of a K-GPU run computes per round (its fixed per-round costs included)
@@ -215,141 +246,19 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    # whole-job unit counts (all ranks)
-    local = np.array([sum(c.paths for c in cnts), sum(c.path_rays for c in cnts), sum(c.shadow_rays for c in cnts)], dtype=np.float64)
+    # whole-job unit counts (all ranks): all timed steps, then the last one (--dump-outputs)
+    last = cnts[-1]
+    local = np.array([sum(c.paths for c in cnts), sum(c.path_rays for c in cnts), sum(c.shadow_rays for c in cnts),
+                      last.paths, last.path_rays, last.shadow_rays], dtype=np.float64)
     if world > 1:
         t = torch.tensor(local, dtype=torch.float64, device=cdev)
         dist.all_reduce(t, op=dist.ReduceOp.SUM)
         tot = t.cpu().numpy()
     else:
         tot = local
-    paths, path_rays, shadow_rays = tot
-
-    # ---- a frame's FIRST round (BASELINE configs[2] is `rounds: 1`): the timed steps above are later rounds of one frame -- camera-ray
-    # entry lists capped behind round 1's first hits, per-frame lists cached.  Resetting the per-frame state (what a new camera
-    # or tile list does) makes the next round pay for all of it: uncapped lists, the distance ranges, the list builds.
-    first_round_ms = None
-    if world == 1 and not args.emulate_shard:
-        fr = []
-        for _ in range(3):
-            scene.set_tuning(entry_points=1)   # (same value: the call drops the per-frame lists)
-            barrier()
-            t1 = time.perf_counter()
-            drv.render_round()
-            barrier()
-            fr.append((time.perf_counter() - t1) * 1e3)
-        first_round_ms = round(sorted(fr)[1], 3)
-
-    # ---- rooflines.  LIVE in this run: HIP-event time, launches and units (rays / vertices) PER KERNEL inside the timed steps
-    # (rgk_counters.kernel[], events on the stream the kernels run on), and each kernel's node visits / triangle tests from one
-    # extra untimed counting round (deterministic per seed) -> SURVEY 8(d)'s algorithmic bytes per launch.  FROM THE COMMITTED
-    # PROFILE of this same command (profiles/<tag>_<workload>_roofline.json: tools/profile_round.sh + tools/summarize_prof.py): the
-    # VALU instruction mix, lane utilisation and the physical HBM bytes per launch (rocprofv3 --pmc in separate passes; bench.py
-    # cannot run the profiler on itself) -- attached only when workload and N match the profiled run, always with their source.
-    KID = capi.KERNEL_IDS
-    P_l, R_l, S_l = (sum(c.paths for c in cnts), sum(c.path_rays for c in cnts), sum(c.shadow_rays for c in cnts))  # this rank
-    drv_c = rd.RenderDriver(scene, Cfg, wl.camera, rank=rank, world_size=world, device=device, flags=capi.FLAG_COUNT_TRAVERSAL,
-                            host_reduce=(args.backend != "nccl"))
-    cc = drv_c.render_round(reduce=False)
-    nodes_per_ray = cc.node_visits / max(1, cc.path_rays)
-    tris_per_ray = cc.tri_tests / max(1, cc.path_rays)
-    bytes_per_ray = 32 + 4 + 16 + nodes_per_ray * info.node_bytes + tris_per_ray * info.tri_bytes
-    # SURVEY 8(d) per shaded vertex: 56 path state + 96 vertex attributes + 32 material (+ 4*12*n_maps texels, n_maps = 2, + 3*12 bump
-    # + 4*20 LTC entries for a textured, bump-mapped LTC material: the Sponza kind) -- 184 B for Cornell's solid diffuse, 396 B otherwise
-    shade_bytes = 184.0 if args.workload.startswith("cornell") else 396.0
-    prof, prof_name = None, None
-    try:
-        if args.scale == 1.0 and args.spp is None and world == 1 and not args.emulate_shard:
-            cands = sorted(f for f in os.listdir(os.path.join(ROOT, "profiles")) if f.endswith(f"_{args.workload}_roofline.json"))
-            if cands:
-                prof_name = cands[-1]
-                prof = json.load(open(os.path.join(ROOT, "profiles", prof_name)))["kernels"]
-    except Exception:
-        prof = None
-
-    def prof_rec(kid):
-        """The profiled record of one kernel: the non-counting instantiation whose name starts with the kernel's prefix."""
-        pre = capi.KERNEL_NAMES.get(kid)
-        if not prof or not pre:
-            return None
-        recs = [r for k, r in prof.items() if k.startswith(pre) and "<true, 256" not in k and "<true, 32" not in k]
-        if not recs:
-            return None
-        n = sum(r["launches_profiled"] for r in recs)
-        w = lambda key: sum((r.get(key) or 0.0) * r["launches_profiled"] for r in recs) / n
-        return {"avg_ms": w("avg_ms"), "valu_slow_pipe_cycles": w("valu_slow_pipe_cycles"), "valu_issue_cycles": w("valu_issue_cycles"),
-                "lane_util": w("lane_util"), "hbm_bytes_per_launch": w("hbm_bytes_per_launch") or None, "launches_profiled": n}
-
-    kernels, step_hbm_bytes, step_hbm_covered_ms = [], 0.0, 0.0
-    for i, kid in enumerate(KID):
-        ms_k = sum(c.kernel[i].ms for c in cnts)
-        n_k = sum(c.kernel[i].launches for c in cnts)
-        u_k = sum(c.kernel[i].units for c in cnts)
-        if n_k == 0:
-            continue
-        avg_s = ms_k / n_k * 1e-3
-        rec = {"kernel": kid, "ms_per_step": round(ms_k / args.steps, 3), "launches_per_step": round(n_k / args.steps, 2),
-               "avg_launch_ms": round(ms_k / n_k, 4), "units_per_step": int(u_k / args.steps)}
-        ck = cc.kernel[i]
-        alg = None   # SURVEY 8(d) algorithmic bytes per unit
-        if kid in ("trace_camera", "trace_closest", "light_trace") and ck.units:
-            rec["nodes_per_ray"], rec["tris_per_ray"] = round(ck.node_visits / ck.units, 2), round(ck.tri_tests / ck.units, 2)
-            alg = 32 + 4 + 16 + ck.node_visits / ck.units * info.node_bytes + ck.tri_tests / ck.units * info.tri_bytes
-        elif kid in ("shadow_first", "shadow", "light_splat") and ck.units:
-            rec["nodes_per_ray"], rec["tris_per_ray"] = round(ck.node_visits / ck.units, 2), round(ck.tri_tests / ck.units, 2)
-            alg = 32 + 4 + ck.node_visits / ck.units * info.node_bytes + ck.tri_tests / ck.units * info.tri_bytes
-        elif kid in ("shade_first", "shade"):
-            alg = shade_bytes
-        elif kid == "resolve":
-            alg = 16.0
-        if alg is not None and u_k:
-            per_launch = alg * u_k / n_k
-            rec.update({"algorithmic_bytes_per_unit": round(alg, 1), "algorithmic_bytes_per_launch": round(per_launch),
-                        "algorithmic_GBps": round(per_launch / avg_s / 1e9, 1), "algorithmic_frac_of_hbm_peak": round(per_launch / avg_s / 8.0e12, 4)})
-        pr = prof_rec(kid)
-        if pr:
-            rec.update({"source": f"profiles/{prof_name}", "profile_avg_launch_ms": round(pr["avg_ms"], 4),
-                        # VALU: the non-fp32 ("slow") pipe's busy cycles from the profiled instruction mix (tools/summarize_prof.py) against
-                        # 1024 SIMDs x 2.4 GHz x the LIVE launch time
-                        "valu_slow_pipe_frac": round(pr["valu_slow_pipe_cycles"] / (1024 * 2.4e9 * avg_s), 4),
-                        "valu_issue_frac": round(pr["valu_issue_cycles"] / (1024 * 2.4e9 * avg_s), 4), "lane_util": round(pr["lane_util"], 4)})
-            if pr.get("hbm_bytes_per_launch"):
-                # physical bytes: 128 B per TCC_EA0_RDREQ (= FETCH_SIZE x 2: every read request of these kernels, gathers included, is a
-                # 128-byte line fill -- profiles/r03_fetch_calibration.txt) + WRITE_SIZE
-                rec.update({"hbm_bytes_per_launch": pr["hbm_bytes_per_launch"], "hbm_frac": round(pr["hbm_bytes_per_launch"] / avg_s / 8.0e12, 4)})
-                step_hbm_bytes += pr["hbm_bytes_per_launch"] * n_k / args.steps
-                step_hbm_covered_ms += ms_k / args.steps
-        kernels.append(rec)
-    ms_step = elapsed / args.steps * 1e3
-    dom = max((r for r in kernels if r["kernel"] not in ("other",)), key=lambda r: r["ms_per_step"])
-    traversal = dom["kernel"] in ("trace_camera", "trace_closest", "shadow_first", "shadow", "shadow_jobs", "light_trace", "light_splat")
-    if traversal:   # bounded by the VALU's non-fp32 pipe (DESIGN.md 6), not by HBM: its bytes are cache-served
-        bound, unit, peak = "valu", "G SIMD-cycles/s of the non-fp32 VALU pipe", 1024 * 2.4
-        frac = dom.get("valu_slow_pipe_frac")
-        achieved = frac * peak if frac is not None else None
-    else:           # shading / resolve: gathers + queue records, bounded by the memory system
-        bound, unit, peak = "hbm", "GB/s", 8000.0
-        achieved = (dom["hbm_bytes_per_launch"] / (dom["avg_launch_ms"] * 1e-3) / 1e9) if dom.get("hbm_bytes_per_launch") else dom.get("algorithmic_GBps")
-        frac = achieved / peak if achieved else None
-    roofline = {"bound": bound, "kernel": capi.KERNEL_NAMES.get(dom["kernel"], dom["kernel"]), "kernel_id": dom["kernel"],
-                "avg_launch_ms": dom["avg_launch_ms"], "achieved": round(achieved, 1) if achieved else None, "peak": peak, "unit": unit,
-                "frac": round(frac, 4) if frac is not None else None,
-                "traffic": dom.get("hbm_bytes_per_launch"),
-                "traffic_source": f"profiles/{prof_name}: rocprofv3 --pmc, 128 B x TCC_EA0_RDREQ (= FETCH_SIZE x 2, calibrated for gathers too: profiles/r03_fetch_calibration.txt) + WRITE_SIZE" if dom.get("hbm_bytes_per_launch") else None,
-                "hbm_frac": dom.get("hbm_frac"), "lane_util": dom.get("lane_util"),
-                # SURVEY 8(d)'s figure for the same kernel: algorithmic bytes per launch over the live launch time.  Node and triangle
-                # bytes are served by L1 / L2 / Infinity Cache, so for traversal this exceeds what HBM could deliver: it is the
-                # algorithmic rate, NOT an HBM fraction (the physical one is hbm_frac)
-                "algorithmic": {k: dom.get(k) for k in ("algorithmic_bytes_per_unit", "algorithmic_bytes_per_launch", "algorithmic_GBps", "algorithmic_frac_of_hbm_peak", "nodes_per_ray", "tris_per_ray")},
-                # the north-star target (>= 40 % of the HBM roofline on Sponza 1080p x 256) is judged on THIS: physical bytes of all
-                # kernels of a step over the step's wall time
-                "step_hbm_frac": round(step_hbm_bytes / (ms_step * 1e-3) / 8.0e12, 4) if step_hbm_bytes else None,
-                "step_hbm_GB": round(step_hbm_bytes / 1e9, 2) if step_hbm_bytes else None,
-                "step_algorithmic_GB": round(sum(r.get("algorithmic_bytes_per_launch", 0) * r["launches_per_step"] for r in kernels) / 1e9, 1),
-                "first_round_ms": first_round_ms,
-                "whole_round": {"nodes_per_path_ray": round(nodes_per_ray, 2), "tris_per_path_ray": round(tris_per_ray, 2), "bytes_per_path_ray": round(bytes_per_ray, 1),
-                                "node_bytes": info.node_bytes, "tri_bytes": info.tri_bytes},
-                "kernels": kernels}
+    paths, path_rays, shadow_rays = tot[:3]
+    if args.dump_outputs and rank == 0:  # before anything else renders into the accumulator
+        dump_outputs(args.dump_outputs, drv.total_ob.data.cpu().numpy(), drv.total_ob.count.cpu().numpy(), tot[3:])
 
     metric_name = {"sponza-1080p": "Sponza 1920x1080x256spp", "cornell-1024": "Cornell box 1024x1024x256spp", "cornell-256": "Cornell box 256x256x16spp",
                    "dragon-sponza-1080p": "Dragon-Sponza 1920x1080x512spp reverse 3", "sponza4-2160p": "Sponza4 3840x2160x1024spp"}[args.workload]
@@ -367,11 +276,139 @@ def main():
                    "tiles": drv.n_tasks, "parallelism": f"tiles round-robin over {world} GPU(s) + one RCCL reduce per round"},
         "mrays_per_s_path": round(path_rays / elapsed / 1e6, 2),
         "mrays_per_s_all": round((path_rays + shadow_rays) / elapsed / 1e6, 2),
-        "roofline": roofline,
     }
 
+    if args.full:
+        # ---- a frame's FIRST round (BASELINE configs[2] is `rounds: 1`): the timed steps above are later rounds of one frame -- camera-ray
+        # entry lists capped behind round 1's first hits, per-frame lists cached.  Resetting the per-frame state (what a new camera
+        # or tile list does) makes the next round pay for all of it: uncapped lists, the distance ranges, the list builds.
+        first_round_ms = None
+        if world == 1 and not args.emulate_shard:
+            fr = []
+            for _ in range(3):
+                scene.set_tuning(entry_points=1)   # (same value: the call drops the per-frame lists)
+                barrier()
+                t1 = time.perf_counter()
+                drv.render_round()
+                barrier()
+                fr.append((time.perf_counter() - t1) * 1e3)
+            first_round_ms = round(sorted(fr)[1], 3)
+
+        # ---- rooflines.  LIVE in this run: HIP-event time, launches and units (rays / vertices) PER KERNEL inside the timed steps
+        # (rgk_counters.kernel[], events on the stream the kernels run on), and each kernel's node visits / triangle tests from one
+        # extra untimed counting round (deterministic per seed) -> SURVEY 8(d)'s algorithmic bytes per launch.  FROM THE COMMITTED
+        # PROFILE of this same command (profiles/<tag>_<workload>_roofline.json: tools/profile_round.sh + tools/summarize_prof.py): the
+        # VALU instruction mix, lane utilisation and the physical HBM bytes per launch (rocprofv3 --pmc in separate passes; bench.py
+        # cannot run the profiler on itself) -- attached only when workload and N match the profiled run, always with their source.
+        KID = capi.KERNEL_IDS
+        P_l, R_l, S_l = (sum(c.paths for c in cnts), sum(c.path_rays for c in cnts), sum(c.shadow_rays for c in cnts))  # this rank
+        drv_c = rd.RenderDriver(scene, Cfg, wl.camera, rank=rank, world_size=world, device=device, flags=capi.FLAG_COUNT_TRAVERSAL,
+                                host_reduce=(args.backend != "nccl"))
+        cc = drv_c.render_round(reduce=False)
+        nodes_per_ray = cc.node_visits / max(1, cc.path_rays)
+        tris_per_ray = cc.tri_tests / max(1, cc.path_rays)
+        bytes_per_ray = 32 + 4 + 16 + nodes_per_ray * info.node_bytes + tris_per_ray * info.tri_bytes
+        # SURVEY 8(d) per shaded vertex: 56 path state + 96 vertex attributes + 32 material (+ 4*12*n_maps texels, n_maps = 2, + 3*12 bump
+        # + 4*20 LTC entries for a textured, bump-mapped LTC material: the Sponza kind) -- 184 B for Cornell's solid diffuse, 396 B otherwise
+        shade_bytes = 184.0 if args.workload.startswith("cornell") else 396.0
+        prof, prof_name = None, None
+        try:
+            if args.scale == 1.0 and args.spp is None and world == 1 and not args.emulate_shard:
+                cands = sorted(f for f in os.listdir(os.path.join(ROOT, "profiles")) if f.endswith(f"_{args.workload}_roofline.json"))
+                if cands:
+                    prof_name = cands[-1]
+                    prof = json.load(open(os.path.join(ROOT, "profiles", prof_name)))["kernels"]
+        except Exception:
+            prof = None
+
+        def prof_rec(kid):
+            """The profiled record of one kernel: the non-counting instantiation whose name starts with the kernel's prefix."""
+            pre = capi.KERNEL_NAMES.get(kid)
+            if not prof or not pre:
+                return None
+            recs = [r for k, r in prof.items() if k.startswith(pre) and "<true, 256" not in k and "<true, 32" not in k]
+            if not recs:
+                return None
+            n = sum(r["launches_profiled"] for r in recs)
+            w = lambda key: sum((r.get(key) or 0.0) * r["launches_profiled"] for r in recs) / n
+            return {"avg_ms": w("avg_ms"), "valu_slow_pipe_cycles": w("valu_slow_pipe_cycles"), "valu_issue_cycles": w("valu_issue_cycles"),
+                    "lane_util": w("lane_util"), "hbm_bytes_per_launch": w("hbm_bytes_per_launch") or None, "launches_profiled": n}
+
+        kernels, step_hbm_bytes, step_hbm_covered_ms = [], 0.0, 0.0
+        for i, kid in enumerate(KID):
+            ms_k = sum(c.kernel[i].ms for c in cnts)
+            n_k = sum(c.kernel[i].launches for c in cnts)
+            u_k = sum(c.kernel[i].units for c in cnts)
+            if n_k == 0:
+                continue
+            avg_s = ms_k / n_k * 1e-3
+            rec = {"kernel": kid, "ms_per_step": round(ms_k / args.steps, 3), "launches_per_step": round(n_k / args.steps, 2),
+                   "avg_launch_ms": round(ms_k / n_k, 4), "units_per_step": int(u_k / args.steps)}
+            ck = cc.kernel[i]
+            alg = None   # SURVEY 8(d) algorithmic bytes per unit
+            if kid in ("trace_camera", "trace_closest", "light_trace") and ck.units:
+                rec["nodes_per_ray"], rec["tris_per_ray"] = round(ck.node_visits / ck.units, 2), round(ck.tri_tests / ck.units, 2)
+                alg = 32 + 4 + 16 + ck.node_visits / ck.units * info.node_bytes + ck.tri_tests / ck.units * info.tri_bytes
+            elif kid in ("shadow_first", "shadow", "light_splat") and ck.units:
+                rec["nodes_per_ray"], rec["tris_per_ray"] = round(ck.node_visits / ck.units, 2), round(ck.tri_tests / ck.units, 2)
+                alg = 32 + 4 + ck.node_visits / ck.units * info.node_bytes + ck.tri_tests / ck.units * info.tri_bytes
+            elif kid in ("shade_first", "shade"):
+                alg = shade_bytes
+            elif kid == "resolve":
+                alg = 16.0
+            if alg is not None and u_k:
+                per_launch = alg * u_k / n_k
+                rec.update({"algorithmic_bytes_per_unit": round(alg, 1), "algorithmic_bytes_per_launch": round(per_launch),
+                            "algorithmic_GBps": round(per_launch / avg_s / 1e9, 1), "algorithmic_frac_of_hbm_peak": round(per_launch / avg_s / 8.0e12, 4)})
+            pr = prof_rec(kid)
+            if pr:
+                rec.update({"source": f"profiles/{prof_name}", "profile_avg_launch_ms": round(pr["avg_ms"], 4),
+                            # VALU: the non-fp32 ("slow") pipe's busy cycles from the profiled instruction mix (tools/summarize_prof.py) against
+                            # 1024 SIMDs x 2.4 GHz x the LIVE launch time
+                            "valu_slow_pipe_frac": round(pr["valu_slow_pipe_cycles"] / (1024 * 2.4e9 * avg_s), 4),
+                            "valu_issue_frac": round(pr["valu_issue_cycles"] / (1024 * 2.4e9 * avg_s), 4), "lane_util": round(pr["lane_util"], 4)})
+                if pr.get("hbm_bytes_per_launch"):
+                    # physical bytes: 128 B per TCC_EA0_RDREQ (= FETCH_SIZE x 2: every read request of these kernels, gathers included, is a
+                    # 128-byte line fill -- profiles/r03_fetch_calibration.txt) + WRITE_SIZE
+                    rec.update({"hbm_bytes_per_launch": pr["hbm_bytes_per_launch"], "hbm_frac": round(pr["hbm_bytes_per_launch"] / avg_s / 8.0e12, 4)})
+                    step_hbm_bytes += pr["hbm_bytes_per_launch"] * n_k / args.steps
+                    step_hbm_covered_ms += ms_k / args.steps
+            kernels.append(rec)
+        ms_step = elapsed / args.steps * 1e3
+        dom = max((r for r in kernels if r["kernel"] not in ("other",)), key=lambda r: r["ms_per_step"])
+        traversal = dom["kernel"] in ("trace_camera", "trace_closest", "shadow_first", "shadow", "shadow_jobs", "light_trace", "light_splat")
+        if traversal:   # bounded by the VALU's non-fp32 pipe (DESIGN.md 6), not by HBM: its bytes are cache-served
+            bound, unit, peak = "valu", "G SIMD-cycles/s of the non-fp32 VALU pipe", 1024 * 2.4
+            frac = dom.get("valu_slow_pipe_frac")
+            achieved = frac * peak if frac is not None else None
+        else:           # shading / resolve: gathers + queue records, bounded by the memory system
+            bound, unit, peak = "hbm", "GB/s", 8000.0
+            achieved = (dom["hbm_bytes_per_launch"] / (dom["avg_launch_ms"] * 1e-3) / 1e9) if dom.get("hbm_bytes_per_launch") else dom.get("algorithmic_GBps")
+            frac = achieved / peak if achieved else None
+        roofline = {"bound": bound, "kernel": capi.KERNEL_NAMES.get(dom["kernel"], dom["kernel"]), "kernel_id": dom["kernel"],
+                    "avg_launch_ms": dom["avg_launch_ms"], "achieved": round(achieved, 1) if achieved else None, "peak": peak, "unit": unit,
+                    "frac": round(frac, 4) if frac is not None else None,
+                    "traffic": dom.get("hbm_bytes_per_launch"),
+                    "traffic_source": f"profiles/{prof_name}: rocprofv3 --pmc, 128 B x TCC_EA0_RDREQ (= FETCH_SIZE x 2, calibrated for gathers too: profiles/r03_fetch_calibration.txt) + WRITE_SIZE" if dom.get("hbm_bytes_per_launch") else None,
+                    "hbm_frac": dom.get("hbm_frac"), "lane_util": dom.get("lane_util"),
+                    # SURVEY 8(d)'s figure for the same kernel: algorithmic bytes per launch over the live launch time.  Node and triangle
+                    # bytes are served by L1 / L2 / Infinity Cache, so for traversal this exceeds what HBM could deliver: it is the
+                    # algorithmic rate, NOT an HBM fraction (the physical one is hbm_frac)
+                    "algorithmic": {k: dom.get(k) for k in ("algorithmic_bytes_per_unit", "algorithmic_bytes_per_launch", "algorithmic_GBps", "algorithmic_frac_of_hbm_peak", "nodes_per_ray", "tris_per_ray")},
+                    # the north-star target (>= 40 % of the HBM roofline on Sponza 1080p x 256) is judged on THIS: physical bytes of all
+                    # kernels of a step over the step's wall time
+                    "step_hbm_frac": round(step_hbm_bytes / (ms_step * 1e-3) / 8.0e12, 4) if step_hbm_bytes else None,
+                    "step_hbm_GB": round(step_hbm_bytes / 1e9, 2) if step_hbm_bytes else None,
+                    "step_algorithmic_GB": round(sum(r.get("algorithmic_bytes_per_launch", 0) * r["launches_per_step"] for r in kernels) / 1e9, 1),
+                    "first_round_ms": first_round_ms,
+                    "whole_round": {"nodes_per_path_ray": round(nodes_per_ray, 2), "tris_per_path_ray": round(tris_per_ray, 2), "bytes_per_path_ray": round(bytes_per_ray, 1),
+                                    "node_bytes": info.node_bytes, "tri_bytes": info.tri_bytes},
+                    "kernels": kernels}
+
+        out["roofline"] = roofline
+
     # ---- CPU baseline: the oracle on the host cores, rank 0 at N = 1 only, bounded sample
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         from oracle import rgk_oracle as O
         osc = O.OracleScene(wl.builder.to_desc())
         threads = max(1, host_cores() - 1)  # hardware_concurrency() - 1, render_driver.cpp:205-206

@@ -10,8 +10,6 @@ import numpy as np
 import pytest
 
 from rgk_amd import capi
-
-REF_DIR = os.environ.get("RGK_REFERENCE", "/root/reference")
 from rgk_amd.config import Config, ConfigFileException, parse_json, strip_json_comments
 from rgk_amd.scene import SceneBuilder, primitive_data
 
@@ -183,27 +181,45 @@ def _canonical(v):
     return "{" + ",".join('"%s":%s' % (k, _canonical(v[k])) for k in sorted(v)) + "}"
 
 
-def test_json_front_end_parses_every_shipped_scene_like_the_references_jsoncpp():
+def _scene_configs():
+    """tests/golden/scene_configs_jsoncpp.json (tools/make_fixtures.py): every scene config the reference ships -- its path under
+    scenes/, its text as it lies on disk, and the tree the reference's own JSON reader (oracle/_ref/jsoncpp_ref) parsed from it."""
+    with open(os.path.join(ROOT, "tests", "golden", "scene_configs_jsoncpp.json")) as f:
+        return json.load(f)
+
+
+def _write_scene_config(tmp_path, rec):
+    path = tmp_path / rec["path"]
+    path.parent.mkdir(parents=True, exist_ok=True)
+    with open(path, "w", newline="") as f:
+        f.write(rec["text"])
+    return str(path)
+
+
+def test_json_front_end_parses_every_shipped_scene_like_the_references_jsoncpp(tmp_path):
     """f1 pinned: the reference's own JSON reader (external/jsoncpp.cpp, compiled where it lies into oracle/_ref/jsoncpp_ref,
     called as src/config.cpp:266-272 calls it) against rgk_amd.config's comment stripping + json parse, on all the scene
-    files the reference ships: identical trees -- keys, nesting, strings, integer-vs-real typing, every number to 17 digits."""
-    exe = os.path.join(ROOT, "oracle", "_ref", "jsoncpp_ref")
-    scenes = os.path.join(REF_DIR, "scenes")
-    if not (os.path.exists(exe) and os.path.isdir(scenes)):
-        pytest.skip("oracle/_ref/jsoncpp_ref or the reference's scenes are absent on this box")
-    files = sorted(os.path.join(d, f) for d, _, fs in os.walk(scenes) for f in fs if f.endswith(".json") or f.endswith(".rtc"))
-    assert len(files) >= 39
-    out = subprocess.run([exe] + files, capture_output=True, text=True, check=True).stdout.strip().split("\n")
-    assert len(out) == len(files)
+    files the reference ships: identical trees -- keys, nesting, strings, integer-vs-real typing, every number to 17 digits.
+    The reader's trees are recorded with the files (_scene_configs); where oracle/_ref/jsoncpp_ref is built it parses the
+    files again and must print the recorded trees."""
+    recs = _scene_configs()
+    assert len(recs) >= 39
+    files = [_write_scene_config(tmp_path, r) for r in recs]
     n_comments = 0
-    for line, path in zip(out, files):
-        p, tree = line.split("\t", 1)
-        assert p == path and tree != "ERROR", path
+    for rec, path in zip(recs, files):
+        assert rec["jsoncpp"] != "ERROR", rec["path"]
         text = open(path).read()
         n_comments += ("//" in text) or ("/*" in text)
         mine = _canonical(parse_json(text))
-        assert mine == tree, path
+        assert mine == rec["jsoncpp"], rec["path"]
     assert n_comments >= 5   # the comment syntax is exercised (scenes/cornell-box.json and others carry comments)
+    exe = os.path.join(ROOT, "oracle", "_ref", "jsoncpp_ref")
+    if os.path.exists(exe):
+        out = subprocess.run([exe] + files, capture_output=True, text=True, check=True).stdout.strip().split("\n")
+        assert len(out) == len(files)
+        for line, path, rec in zip(out, files, recs):
+            p, tree = line.split("\t", 1)
+            assert p == path and tree == rec["jsoncpp"], rec["path"]
 
 
 def _write_hdr(path, img_rgbe, rle, header_extra=b"", first=b"#?RADIANCE"):
@@ -234,35 +250,33 @@ def _write_hdr(path, img_rgbe, rle, header_extra=b"", first=b"#?RADIANCE"):
 def test_hdr_decoder_equals_the_references_stb_image(tmp_path):
     """f1 pinned: rgk_amd.scene.load_hdr against the decoder the reference vendors and calls (external/stb_image.h through
     stbi_loadf, src/texture.cpp:294-321; compiled where it lies into oracle/_ref/stbi_ref) on run-length encoded, flat and
-    narrow Radiance files: the same floats bit for bit."""
+    narrow Radiance files: the same floats bit for bit.  tests/golden/hdr_stb_image.npz (tools/make_fixtures.py) holds the
+    RGBE images (random, with long runs and black pixels) and the floats stb_image decoded from the files _write_hdr makes of
+    them; where oracle/_ref/stbi_ref is built it decodes the files again and must give the recorded floats."""
     from rgk_amd.scene import load_hdr
+    z = np.load(os.path.join(ROOT, "tests", "golden", "hdr_stb_image.npz"))
     exe = os.path.join(ROOT, "oracle", "_ref", "stbi_ref")
-    if not os.path.exists(exe):
-        pytest.skip("oracle/_ref/stbi_ref not built (reference absent on this box)")
-    rng = np.random.default_rng(9)
-    cases = []
-    for (h, w, rle) in ((17, 64, True), (9, 300, True), (5, 40, False), (6, 5, False), (3, 8, True)):
-        img = rng.integers(0, 256, (h, w, 4), dtype=np.uint8)
-        img[..., 3] = rng.integers(100, 150, (h, w))                # exponents around 128
-        img[1:3, : w // 2] = img[1, 0]                               # long runs
-        img[0, ::7, 3] = 0                                           # zero exponent -> black
-        if not rle:
-            img[0, 0, :3] = (200, 100, 50)                           # a first pixel that cannot be mistaken for a scan-line header
-        cases.append((img, rle))
-    for n, (img, rle) in enumerate(cases):
+    live = os.path.exists(exe)
+    n_cases = sum(k.startswith("rgbe") for k in z.files)
+    assert n_cases == 5 and any(bool(z[f"rle{n}"]) for n in range(n_cases)) and not all(bool(z[f"rle{n}"]) for n in range(n_cases))
+    for n in range(n_cases):
+        img, rle, ref = z[f"rgbe{n}"], bool(z[f"rle{n}"]), z[f"stb{n}"]
         path = str(tmp_path / f"t{n}.hdr")
         _write_hdr(path, img, rle, header_extra=b"# made by the test\nEXPOSURE=1.0\n")
-        out = str(tmp_path / f"t{n}.bin")
-        subprocess.run([exe, path, out], check=True)
-        b = open(out, "rb").read()
-        w, h, c = np.frombuffer(b, dtype=np.int32, count=3)
-        ref = np.frombuffer(b, dtype=np.float32, offset=12).reshape(h, w, c)
+        if live:
+            out = str(tmp_path / f"t{n}.bin")
+            subprocess.run([exe, path, out], check=True)
+            b = open(out, "rb").read()
+            w, h, c = np.frombuffer(b, dtype=np.int32, count=3)
+            assert np.array_equal(np.frombuffer(b, dtype=np.float32, offset=12).reshape(h, w, c).view(np.uint32), ref.view(np.uint32)), n
         mine = load_hdr(path)
         assert mine.shape == ref.shape == img.shape[:2] + (3,)
         assert np.array_equal(mine.view(np.uint32), ref.view(np.uint32)), n
     bad = str(tmp_path / "bad.hdr")
-    _write_hdr(bad, cases[0][0], True, first=b"#?RGBE")              # this stb version knows only #?RADIANCE
-    assert subprocess.run([exe, bad, str(tmp_path / "bad.bin")], capture_output=True).returncode != 0
+    _write_hdr(bad, z["rgbe0"], True, first=b"#?RGBE")               # this stb version knows only #?RADIANCE
+    assert bool(z["bad_refused"])
+    if live:
+        assert subprocess.run([exe, bad, str(tmp_path / "bad.bin")], capture_output=True).returncode != 0
     with pytest.raises(ValueError):
         load_hdr(bad)
 
@@ -290,10 +304,9 @@ def test_rtc_config_format(tmp_path):
     short.write_text("c\nm.obj\no.exr\n3\n64 48")
     with pytest.raises(ConfigFileException, match="prematurely"):
         load_config(str(short))
-    ref = os.path.join(REF_DIR, "scenes", "sponza.rtc")
-    if os.path.exists(ref):
-        with pytest.raises(ConfigFileException):
-            load_config(ref)                                          # JSON inside a .rtc: std::stoi of `"output-width": 1200,` (F7)
+    ref = _write_scene_config(tmp_path / "ref", next(r for r in _scene_configs() if r["path"] == "sponza.rtc"))
+    with pytest.raises(ConfigFileException):
+        load_config(ref)                                              # JSON inside a .rtc: std::stoi of `"output-width": 1200,` (F7)
     with pytest.raises(ConfigFileException, match="not recognized"):
         load_config(str(tmp_path / "x.txt"))
 
@@ -339,20 +352,22 @@ def test_builtin_primitives_match_reference_shapes():
     assert pos[0].tolist() == [1, 0, 1] and uv[0].tolist() == [1, 1] and pos[3].tolist() == [-1, 0, -1]
 
 
-def test_cornell_fixture_matches_reference_config():
-    ref = "/root/reference/scenes/cornell-box.json"
-    if not os.path.exists(ref):
-        pytest.skip("reference not present on this box")
+def test_cornell_fixture_matches_reference_config(tmp_path):
+    ref = _write_scene_config(tmp_path, next(r for r in _scene_configs() if r["path"] == "cornell-box.json"))
     a = Config(ref).build_scene().finalize()
     b = SceneBuilder.load_npz(os.path.join(ROOT, "rgk_amd", "data", "cornell_scene.npz"))
     assert np.array_equal(a.V, b.V) and np.array_equal(a.F, b.F) and np.array_equal(a.N, b.N) and np.array_equal(a.FM, b.FM)
     assert len(a.F) == 36 and len(a.V) == 108 and a.areal == b.areal == [[34], [35]]   # 36 triangles, 2 lights
 
 
-def test_obj_loader_on_reference_meshes():
-    ref = "/root/reference/scenes/cubes/cube3.obj"
-    if not os.path.exists(ref):
-        pytest.skip("reference not present on this box")
+def test_obj_loader_on_reference_meshes(tmp_path):
+    """The reference's scenes/cubes/cube3 mesh and materials (tests/golden/cube3.obj.gz, cube3.mtl)."""
+    import gzip
+    import shutil
+    with gzip.open(os.path.join(ROOT, "tests", "golden", "cube3.obj.gz"), "rb") as f:
+        (tmp_path / "cube3.obj").write_bytes(f.read())
+    shutil.copyfile(os.path.join(ROOT, "tests", "golden", "cube3.mtl"), tmp_path / "cube3.mtl")
+    ref = str(tmp_path / "cube3.obj")
     sb = SceneBuilder()
     sb.load_obj(ref, np.eye(4, dtype=np.float32))
     sb.finalize()

@@ -15,8 +15,17 @@ needs /root/reference).  Fixtures are DATA: inputs and expected outputs.
                      triangles, reverse = 3), cornell-box-spheres (LTC Beckmann + dielectric spheres).
   rgk_amd/data/sponza_textures_u8.npz  the 17 JPGs shipped under scenes/sponza-fixed/ as decoded bytes (the Sponza proxy's
                      textures; the mesh itself is absent from the reference checkout).
+  scene_configs_jsoncpp.json  every scene config the reference ships (scenes/**/*.json, *.rtc: settings only) with the
+                     tree its vendored JSON reader parses from it (oracle/_ref/jsoncpp_ref).
+  hdr_stb_image.npz  Radiance files (run-length encoded, flat, narrow) as RGBE bytes, and the floats the reference's
+                     vendored stb_image decodes from them (oracle/_ref/stbi_ref).
+  cube3.obj.gz, cube3.mtl  the reference's scenes/cubes/cube3 mesh and its materials (gzip: the mesh is 576 KB).
 """
+import gzip
+import hashlib
+import json
 import os
+import shutil
 import subprocess
 import sys
 
@@ -36,7 +45,66 @@ def halton():
                          capture_output=True, check=True).stdout
     vals = np.frombuffer(out, dtype=np.float32).reshape(256, len(idx))
     np.savez_compressed(os.path.join(GOLD, "halton_faure.npz"), index=idx, values=vals)
-    print("halton_faure.npz", vals.shape)
+    print("halton_faure.npz", vals.shape, "sha256 of index + values:", hashlib.sha256(idx.tobytes() + vals.tobytes()).hexdigest())
+
+
+def scene_configs():
+    """The scene files as they lie (text exactly as read from disk) + the canonical tree jsoncpp_ref prints for each."""
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "ref"])
+    scenes = os.path.join(REF, "scenes")
+    files = sorted(os.path.join(d, f) for d, _, fs in os.walk(scenes) for f in fs if f.endswith(".json") or f.endswith(".rtc"))
+    out = subprocess.run([os.path.join(ROOT, "oracle", "_ref", "jsoncpp_ref")] + files, capture_output=True, text=True,
+                         check=True).stdout.strip().split("\n")
+    recs = []
+    for line, path in zip(out, files):
+        p, tree = line.split("\t", 1)
+        assert p == path and tree != "ERROR", path
+        recs.append({"path": os.path.relpath(path, scenes), "text": open(path, newline="").read(), "jsoncpp": tree})
+    with open(os.path.join(GOLD, "scene_configs_jsoncpp.json"), "w") as f:
+        json.dump(recs, f, indent=0)
+        f.write("\n")
+    print("scene_configs_jsoncpp.json", len(recs), "files")
+
+
+def hdr_stb():
+    """Random RGBE images with long runs and black pixels, written by tests/test_host_cpu.py's _write_hdr and decoded by the
+    reference's stb_image (stbi_loadf); bad_refused: a '#?RGBE' first line is rejected (this stb version knows '#?RADIANCE')."""
+    import tempfile
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "ref"])
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from test_host_cpu import _write_hdr
+    exe = os.path.join(ROOT, "oracle", "_ref", "stbi_ref")
+    rng = np.random.default_rng(9)
+    arrs = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        for n, (h, w, rle) in enumerate(((17, 64, True), (9, 300, True), (5, 40, False), (6, 5, False), (3, 8, True))):
+            img = rng.integers(0, 256, (h, w, 4), dtype=np.uint8)
+            img[..., 3] = rng.integers(100, 150, (h, w))                # exponents around 128
+            img[1:3, : w // 2] = img[1, 0]                               # long runs
+            img[0, ::7, 3] = 0                                           # zero exponent -> black
+            if not rle:
+                img[0, 0, :3] = (200, 100, 50)                           # a first pixel that cannot be mistaken for a scan-line header
+            path, out = os.path.join(tmp, f"t{n}.hdr"), os.path.join(tmp, f"t{n}.bin")
+            _write_hdr(path, img, rle, header_extra=b"# made by the test\nEXPOSURE=1.0\n")
+            subprocess.run([exe, path, out], check=True)
+            b = open(out, "rb").read()
+            w_, h_, c_ = np.frombuffer(b, dtype=np.int32, count=3)
+            arrs[f"rgbe{n}"], arrs[f"rle{n}"] = img, np.array(rle)
+            arrs[f"stb{n}"] = np.frombuffer(b, dtype=np.float32, offset=12).reshape(h_, w_, c_)
+        bad = os.path.join(tmp, "bad.hdr")
+        _write_hdr(bad, arrs["rgbe0"], True, first=b"#?RGBE")
+        arrs["bad_refused"] = np.array(subprocess.run([exe, bad, os.path.join(tmp, "bad.bin")], capture_output=True).returncode != 0)
+    np.savez_compressed(os.path.join(GOLD, "hdr_stb_image.npz"), **arrs)
+    print("hdr_stb_image.npz", len(arrs), "arrays")
+
+
+def cube3_mesh():
+    src = os.path.join(REF, "scenes", "cubes")
+    with open(os.path.join(src, "cube3.obj"), "rb") as f, open(os.path.join(GOLD, "cube3.obj.gz"), "wb") as g:
+        with gzip.GzipFile(filename="", mode="wb", fileobj=g, mtime=0, compresslevel=9) as z:   # mtime 0: the same bytes every time
+            z.write(f.read())
+    shutil.copyfile(os.path.join(src, "cube3.mtl"), os.path.join(GOLD, "cube3.mtl"))
+    print("cube3.obj.gz", os.path.getsize(os.path.join(GOLD, "cube3.obj.gz")), "bytes")
 
 
 def cornell():
@@ -114,3 +182,6 @@ if __name__ == "__main__":
     for n in REFERENCE_SCENES:
         reference_scene(n)
     sponza_textures()
+    scene_configs()
+    hdr_stb()
+    cube3_mesh()

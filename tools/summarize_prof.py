@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Condense rocprofv3 output (gpurun_out/prof_<tag>_*, written by tools/profile_round.sh) into the small files kept
+"""Condense rocprofv3 output ($OUT/prof_<tag>_*, default out/, written by tools/profile_round.sh) into the small files kept
 under profiles/ -- the evidence bench.py's `roofline` object points at.
 
   python tools/summarize_prof.py <round-tag>
@@ -75,7 +75,7 @@ def counters(d):
 
 def main():
     tag = sys.argv[1]
-    base = os.path.join(ROOT, "gpurun_out", f"prof_{tag}_")
+    base = os.path.join(os.environ.get("OUT", os.path.join(ROOT, "out")), f"prof_{tag}_")
     out = os.path.join(ROOT, "profiles")
     os.makedirs(out, exist_ok=True)
     stats = {}
@@ -115,8 +115,8 @@ def main():
                         round(rqpl, 1) if rq else "", round(r32[0] / max(r32[1], 1), 1) if r32 else "",
                         round((128.0 * (rqpl - r32[0] / max(r32[1], 1)) + 32.0 * r32[0] / max(r32[1], 1)) / 1e6, 2) if rq and r32 else "",
                         round(hit[0] / max(hit[0] + miss[0], 1), 4) if hit and miss else ""])
-    roof = {"tag": tag, "command": "python bench.py --steps 1 --warmup 0 --no-cpu-baseline (one rocprofv3 --pmc pass per counter group); "
-                                   "durations from the --kernel-trace --stats pass of bench.py --steps 3 --warmup 1",
+    roof = {"tag": tag, "command": "python bench.py --full --steps 1 --warmup 0 --no-cpu-baseline (one rocprofv3 --pmc pass per counter group); "
+                                   "durations from the --kernel-trace --stats pass of bench.py --full --steps 3 --warmup 1",
             "valu_issue_cost_cycles": COST, "n_simd": N_SIMD, "hbm_peak_GBps": HBM_PEAK / 1e9, "kernels": {}}
     for k, m in merged.items():
         if not k.startswith("k_") or k not in stats or "SQ_INSTS_VALU" not in m:
