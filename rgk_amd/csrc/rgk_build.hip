@@ -197,8 +197,21 @@ __global__ void k_refit_rotate(const RgkBuildPrim* __restrict__ prims, const uns
 // best partner -- the one within `radius` places of the current order whose union with it has the smallest surface.  That is
 // a surface-area criterion at every merge, which the prefix hierarchy does not have.  cid: a cluster's child code (>= 0 inner
 // node, < 0 ~(position of a reference in the sorted order)); cbox: its box; cnum: references below it.
-__device__ __forceinline__ bool ploc_better(float a, int lo, int hi, float ba, int blo, int bhi) { // one total order for both partners
-    return a < ba || (a == ba && (lo < blo || (lo == blo && hi < bhi)));
+// The order of pairs: the surface of the union, then -- for two IDENTICAL boxes only -- a hash of the pair, then (lo, hi).  In
+// a run of identical boxes (coincident triangles, or clusters of them) every pair ties, and by index alone every member picks
+// the run's leftmost partner: one merge per round, and the run becomes a chain as deep as it is long.  Hashed, about a
+// constant fraction of the run pairs up each round.  A scene without identical boxes gets the tree of the index order.
+__device__ __forceinline__ uint32_t ploc_pair_hash(int lo, int hi) { // (murmur3's 64-bit finaliser)
+    unsigned long long x = ((unsigned long long)(uint32_t)lo << 32) | (uint32_t)hi;
+    x ^= x >> 33; x *= 0xff51afd7ed558ccdull; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull; x ^= x >> 33;
+    return (uint32_t)x;
+}
+__device__ __forceinline__ uint32_t ploc_tie_key(const BBox& p, const BBox& q, int lo, int hi) {
+    const bool same = p.mn[0] == q.mn[0] && p.mn[1] == q.mn[1] && p.mn[2] == q.mn[2] && p.mx[0] == q.mx[0] && p.mx[1] == q.mx[1] && p.mx[2] == q.mx[2];
+    return same ? ploc_pair_hash(lo, hi) : 0u;
+}
+__device__ __forceinline__ bool ploc_better(float a, uint32_t h, int lo, int hi, float ba, uint32_t bh, int blo, int bhi) { // one total order for both partners
+    return a < ba || (a == ba && (h < bh || (h == bh && (lo < blo || (lo == blo && hi < bhi)))));
 }
 __global__ void k_ploc_init(const RgkBuildPrim* __restrict__ prims, const unsigned long long* __restrict__ keys, uint32_t n, float pad,
                             int* __restrict__ cid, BBox* __restrict__ cbox, uint32_t* __restrict__ cnum) {
@@ -211,12 +224,15 @@ __global__ void k_ploc_nn(const BBox* __restrict__ cbox, int m, int radius, int*
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < m; i += gridDim.x * blockDim.x) {
         const BBox b = cbox[i];
         float best = __builtin_inff();
+        uint32_t bh = 0u;
         int bj = -1;
         const int j0 = max(0, i - radius), j1 = min(m - 1, i + radius);
         for (int j = j0; j <= j1; j++) {
             if (j == i) continue;
-            const float a = area(unite(b, cbox[j]));
-            if (bj < 0 || ploc_better(a, min(i, j), max(i, j), best, min(i, bj), max(i, bj))) { best = a; bj = j; }
+            const BBox c = cbox[j];
+            const float a = area(unite(b, c));
+            const uint32_t h = ploc_tie_key(b, c, min(i, j), max(i, j));
+            if (bj < 0 || ploc_better(a, h, min(i, j), max(i, j), best, bh, min(i, bj), max(i, bj))) { best = a; bh = h; bj = j; }
         }
         nn[i] = bj;
     }

@@ -1439,16 +1439,24 @@ int rgk_render_round_device(rgk_scene* s, const rgk_camera* camera, const rgk_pa
     // fill.  Measured inside one process, same bits: Sponza 1080p x 256 126.7 vs 126.9 ms per round (nothing), Cornell 1024 x 256
     // 119.3 vs 110.4 (8 % WORSE: ten bounces of short launches, each now competing for the card) -- the launches fill the machine
     // one at a time, as round 2 found with two processes and with two host threads.
+    // What keeps the lanes apart: a lane is picked per PIXEL RANGE, so all sample passes of a range run in order on one stream
+    // (they share the range's pixsum entries, and a later pass reads the entry lists its first pass capped); and the ranges
+    // are whole 1024-pixel blocks, so no pixel group (RGK_ENTRY_PIX) -- its trange, entry list, cap, light-side list and box --
+    // belongs to two lanes.  A batch too small for a whole block per lane renders on one lane.
     const bool count_stats = (prm->flags & RGK_FLAG_COUNT_TRAVERSAL) != 0;
     const bool track = prm->depth > 12; // measured: depth 10 loses 4 % to the read-backs, depth 40 gains 4 %
-    const bool two = s->tune.two_lanes && R == 0 && !track && !count_stats && (uint64_t)P * prm->multisample >= (1ull << 22) && P >= 4096;
+    bool two = s->tune.two_lanes && R == 0 && !track && !count_stats && (uint64_t)P * prm->multisample >= (1ull << 22) && P >= 4096;
+    static_assert(1024 % RGK_ENTRY_PIX == 0, "two-lane pixel ranges are whole pixel groups");
     size_t npix_pass;
     uint32_t ns_pass;
     size_t lane_cap = 0; // paths per lane = offset of the second lane in every workspace array
     for (;;) {
         const size_t Bl = two ? B / 2 : B; // per lane
         npix_pass = std::min(P, Bl);
-        if (two) npix_pass = std::min(npix_pass, ((P + 1) / 2 + 1023) & ~(size_t)1023); // at least two passes: halves of the list, whole 1024-pixel tiles
+        if (two) { // at least two ranges: halves of the list at most, whole 1024-pixel blocks
+            npix_pass = std::min(npix_pass, ((P + 1) / 2 + 1023) & ~(size_t)1023) & ~(size_t)1023;
+            if (npix_pass == 0) { two = false; continue; }
+        }
         const uint32_t ns_max = (uint32_t)std::max<size_t>(1, std::min<size_t>(prm->multisample, Bl / npix_pass));
         const uint32_t n_sample_passes = (prm->multisample + ns_max - 1) / ns_max;
         ns_pass = (prm->multisample + n_sample_passes - 1) / n_sample_passes; // equal-sized passes
@@ -1558,7 +1566,7 @@ int rgk_render_round_device(rgk_scene* s, const rgk_camera* camera, const rgk_pa
     // a lane's finished pass: wait for its stream, add its queue counters to the round's totals
     bool pending[2] = {false, false};
     uint32_t pend_n0[2] = {0, 0};
-    uint32_t pass_index = 0;
+    uint32_t range_index = 0;
     const bool light_entry_units = light_entry;
     auto harvest = [&](int l) -> int {
         HIPCHK(hipStreamSynchronize(l ? s->stream2 : s->stream));
@@ -1585,7 +1593,7 @@ int rgk_render_round_device(rgk_scene* s, const rgk_camera* camera, const rgk_pa
     // everything queued so far (pixel and seed lists, entry nodes, the Halton table) is on the first stream: the second waits for it
     HIPCHK(hipEventRecord(s->ev_prelude, s->stream));
     if (two) HIPCHK(hipStreamWaitEvent(s->stream2, s->ev_prelude, 0));
-    for (size_t j0 = 0; j0 < P; j0 += npix_pass) {
+    for (size_t j0 = 0; j0 < P; j0 += npix_pass, range_index++) {
         pp.j0 = (uint32_t)j0;
         pp.npix = (uint32_t)std::min(npix_pass, P - j0);
         for (uint32_t s0 = 0; s0 < prm->multisample; s0 += ns_pass) {
@@ -1603,10 +1611,10 @@ int rgk_render_round_device(rgk_scene* s, const rgk_camera* camera, const rgk_pa
                 pp.beam = (s->tune.beam == 2 || (s->tune.beam == 1 && !lists_capped)) ? 1u : 0u;
             }
             const uint32_t n0 = pp.npix * pp.ns;
-            // which lane: its stream, its half of every workspace array, its counter blocks; a lane's previous pass is harvested
-            // (waited for, its counters added up) before the next one is queued on it
-            lane = two ? (int)(pass_index & 1u) : 0;
-            pass_index++;
+            // which lane (one per pixel range: its sample passes stay in order on one stream): its stream, its half of every
+            // workspace array, its counter blocks; a lane's previous pass is harvested (waited for, its counters added up) before
+            // the next one is queued on it
+            lane = two ? (int)(range_index & 1u) : 0;
             st = lane ? s->stream2 : s->stream;
             if (pending[lane] && (rc = harvest(lane))) return rc;
             const size_t off = (size_t)lane * lane_cap;
