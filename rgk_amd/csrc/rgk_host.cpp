@@ -444,10 +444,15 @@ struct QbvhBuilder {
 };
 
 // ------------------------------------------------------------------ scene object
+// A device allocation with one owner: freed by its destructor, never copied.
 template <typename T>
 struct DevBuf {
     T* p = nullptr;
     size_t n = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
     int alloc(size_t count) {
         if (count <= n && p) return 0;
         if (p) (void)hipFree(p);
@@ -465,11 +470,11 @@ struct DevBuf {
         }
         return 0;
     }
-    int upload(const std::vector<T>& v) {
-        int rc = alloc(v.size());
+    int upload(const T* src, size_t count) {
+        int rc = alloc(count);
         if (rc) return rc;
-        if (!v.empty()) {
-            hipError_t e = hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
+        if (count) {
+            hipError_t e = hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice);
             if (e != hipSuccess) return fail(RGK_ERR_DEVICE, "hipMemcpy H2D: %s", hipGetErrorString(e));
         }
         return 0;
@@ -494,7 +499,6 @@ struct RgkTuning {
     double workspace_gb = 0;  // ... or from this many GB; 0: 96 (160 for bidirectional rounds), at most 60 % of what is free
     int beam = 1;             // pinhole cameras: bounce 0 walks the tree once per pixel for 8 samples (k_trace_camera_beam) -- 1: while the
                               // entry lists are uncapped (a frame's first round), 2: always, 0: never
-    bool two_lanes = false;   // experiment (measured: no gain, see render_round): the two halves of the pixel list as two passes on two streams
     bool debug_bvh = false, debug_util = false;
 };
 
@@ -502,13 +506,10 @@ struct rgk_scene {
     int device = 0;
     RgkTuning tune;
     hipStream_t stream = nullptr;
-    hipStream_t stream2 = nullptr;   // second lane of a round (two halves of the pixel list side by side: one's launch tails under the other's launches)
-    hipEvent_t ev_prelude = nullptr; // the round's lists and tables are in place (stream2 waits for it)
     rgk_scene_info info{};
     DevScene dev{};
     RgkTraceCfg tcfg{32, 32, nullptr};
-    DevBuf<int> ovf; // traversal-stack overflow area (deep trees), one per lane
-    size_t ovf_lane = 0;
+    DevBuf<int> ovf; // traversal-stack overflow area (deep trees)
     // scene data
     DevBuf<QNode> nodes;
     DevBuf<TriIsect> tris;
@@ -563,21 +564,15 @@ struct rgk_scene {
     std::atomic<uint32_t> prog_stages{0}, prog_rounds{0}, prog_busy{0};
     uint32_t* h_stage = nullptr; // pinned word the DEVICE writes (k_stage_mark): stages of the running round that are done
     std::atomic<uint64_t> prog_pixels{0}, prog_paths{0};
+    // What is not a DevBuf.  The DevBuf members free themselves after this body has run, and no queued kernel can read one
+    // by then: the body waits for the stream first (an entry point waits for the work it queued before it returns, but one
+    // that fails halfway may leave some behind).
     ~rgk_scene() {
         (void)hipSetDevice(device);
+        if (stream) (void)hipStreamSynchronize(stream);
         for (auto e : events) (void)hipEventDestroy(e);
         if (h_counters) (void)hipHostFree(h_counters);
         if (h_stage) (void)hipHostFree(h_stage);
-        nodes.release(); tris.release(); tri_shade.release(); materials.release(); texels8.release(); luts.release();
-        texels.release(); pointlights.release(); areal.release(); areal_tris.release(); ltc.release(); self.release(); ovf.release();
-        hdims.release(); hperm.release(); texrefs.release(); d_idx.release(); leaf_pb.release();
-        for (int i = 0; i < 2; i++) { rayA[i].release(); rayB[i].release(); }
-        hit.release(); thr.release(); tot.release(); shA.release(); shB.release(); shC.release(); pixsum.release();
-        light.release(); generic.release(); htab.release(); lstart.release(); lv.release(); hitlist.release(); lvmask.release(); connlist.release(); conn.release(); jobs.release(); rads.release();
-        nearfar.release(); counters.release(); pix_xy.release(); pix_seed.release(); tile_buf.release(); stats.release(); entry.release(); entry_cap.release(); lentry.release(); trange.release(); lbox.release();
-        scratch_f.release(); scratch_u.release();
-        if (ev_prelude) (void)hipEventDestroy(ev_prelude);
-        if (stream2) (void)hipStreamDestroy(stream2);
         if (stream) (void)hipStreamDestroy(stream);
     }
 };
@@ -608,11 +603,11 @@ int ensure_workspace(rgk_scene* s, size_t paths, uint32_t reverse = 0) {
     }
     if (!rc) rc = s->light.alloc(paths);
     if (!rc) rc = s->generic.alloc(paths);
-    if (!rc) rc = s->counters.alloc(4 * RGK_CNT_TOTAL); // per lane: [0] camera phase, [1] light sub-path phase
+    if (!rc) rc = s->counters.alloc(2 * RGK_CNT_TOTAL); // [0] camera phase, [1] light sub-path phase
     if (!rc) rc = s->stats.alloc(8);
     if (rc) { s->batch = 0; s->batch_reverse = 0; return rc; } // some buffers are gone: the next call starts over
-    if (!s->h_counters) HIPCHK(hipHostMalloc((void**)&s->h_counters, 4 * RGK_CNT_TOTAL * sizeof(uint32_t)));
-    if (!s->h_stage) { HIPCHK(hipHostMalloc((void**)&s->h_stage, 2 * sizeof(uint32_t))); s->h_stage[0] = s->h_stage[1] = 0; }
+    if (!s->h_counters) HIPCHK(hipHostMalloc((void**)&s->h_counters, 2 * RGK_CNT_TOTAL * sizeof(uint32_t)));
+    if (!s->h_stage) { HIPCHK(hipHostMalloc((void**)&s->h_stage, sizeof(uint32_t))); *s->h_stage = 0; }
     s->batch = paths;
     s->batch_reverse = reverse;
     return 0;
@@ -724,14 +719,6 @@ int validate_desc(const rgk_scene_desc* d) {
 } // namespace
 
 namespace {
-// host arrays -> device scratch, one call
-template <typename T>
-int up(DevBuf<T>& b, const T* src, size_t count) {
-    int rc = b.alloc(count);
-    if (rc) return rc;
-    if (hipMemcpy(b.p, src, count * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return fail(RGK_ERR_DEVICE, "hipMemcpy H2D failed");
-    return 0;
-}
 template <typename T>
 int down(T* dst, const DevBuf<T>& b, size_t count) {
     if (hipMemcpy(dst, b.p, count * sizeof(T), hipMemcpyDeviceToHost) != hipSuccess) return fail(RGK_ERR_DEVICE, "hipMemcpy D2H failed");
@@ -839,8 +826,6 @@ int rgk_scene_create(const rgk_scene_desc* d, int device, rgk_scene** out) {
     s->device = device;
     struct Guard { rgk_scene* s; ~Guard() { delete s; } } guard{s};
     HIPCHK(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-    HIPCHK(hipStreamCreateWithFlags(&s->stream2, hipStreamNonBlocking));
-    HIPCHK(hipEventCreateWithFlags(&s->ev_prelude, hipEventDisableTiming));
     {
         auto off = [](const char* name) { const char* e = std::getenv(name); return e && e[0] == '0'; };
         RgkTuning& t = s->tune;
@@ -849,7 +834,6 @@ int rgk_scene_create(const rgk_scene_desc* d, int device, rgk_scene** out) {
         if (const char* e = std::getenv("RGK_BATCH_PATHS")) t.batch_paths = std::max<size_t>(1024, strtoull(e, nullptr, 10));
         if (const char* e = std::getenv("RGK_WORKSPACE_GB")) t.workspace_gb = atof(e);
         if (const char* e = std::getenv("RGK_BEAM")) t.beam = std::min(2, std::max(0, std::atoi(e)));
-        { const char* e = std::getenv("RGK_TWO_LANES"); t.two_lanes = e && e[0] == '1'; }
         t.debug_bvh = std::getenv("RGK_DEBUG_BVH") != nullptr; t.debug_util = std::getenv("RGK_DEBUG_UTIL") != nullptr;
     }
 
@@ -949,12 +933,11 @@ int rgk_scene_create(const rgk_scene_desc* d, int device, rgk_scene** out) {
             for (int a = 0; a < 4; a++) bp[i].pb[a] = prims[i].pb[a];
         }
         DevBuf<TriIsect> d_recs;
-        if ((rc = d_recs.upload(recs)) || (rc = s->nodes.alloc(prims.size())) || (rc = s->tris.alloc(prims.size())) || (rc = s->leaf_pb.alloc(prims.size()))) { d_recs.release(); return rc; }
+        if ((rc = d_recs.upload(recs.data(), recs.size())) || (rc = s->nodes.alloc(prims.size())) || (rc = s->tris.alloc(prims.size())) || (rc = s->leaf_pb.alloc(prims.size()))) return rc;
         uint32_t levels = 0;
         const char* err = "";
         const char* rot = std::getenv("RGK_LBVH_ROTATE"); // passes of the rotation step; 0: the plain LBVH (for comparisons)
         rc = rgk_build_bvh4_device(s->stream, bp.data(), n_refs, mn, mx, eps, (uint32_t)MAX_LEAF_DEV, rot ? std::max(0, std::min(32, std::atoi(rot))) : RGK_LBVH_ROTATE_PASSES, d_recs.p, s->nodes.p, s->tris.p, s->leaf_pb.p, &n_nodes, &levels, &err);
-        d_recs.release();
         if (rc) return fail(rc, "device BVH build: %s", err);
         max_depth = levels;
         max_stack = 3 * levels; // three pushes per level at most
@@ -1001,8 +984,7 @@ int rgk_scene_create(const rgk_scene_desc* d, int device, rgk_scene** out) {
         s->tcfg.ovf = nullptr;
         if (s->tcfg.lds < s->tcfg.stack) {
             const size_t per_lane = (size_t)std::max(need - std::min(s->tcfg.lds, 8), 1); // (k_trace_camera_beam keeps 8 entries in LDS)
-            s->ovf_lane = (size_t)rgk_trace_grid(s->tcfg.lds) * RGK_TRACE_BLOCK * per_lane;
-            if ((rc = s->ovf.alloc(2 * s->ovf_lane))) return rc; // one area per lane of a round: two traversal launches may be in flight
+            if ((rc = s->ovf.alloc((size_t)rgk_trace_grid(s->tcfg.lds) * RGK_TRACE_BLOCK * per_lane))) return rc;
             s->tcfg.ovf = s->ovf.p;
         }
     }
@@ -1180,13 +1162,15 @@ int rgk_scene_create(const rgk_scene_desc* d, int device, rgk_scene** out) {
         s->h_areal_off.assign(d->areal_offsets, d->areal_offsets + d->n_areal_lights + 1);
         s->h_areal_tris.assign(d->areal_tris, d->areal_tris + d->areal_offsets[d->n_areal_lights]);
     }
-    if ((rc = s->d_idx.upload(s->h_idx))) return rc;
-    if ((rc = s->texrefs.upload(trefs))) return rc;
-    if (!on_device && ((rc = s->nodes.upload(qnodes)) || (rc = s->tris.upload(leaf_recs)) || (rc = s->leaf_pb.upload(leaf_pb)))) return rc;
-    if ((rc = s->tri_shade.upload(tsh)) ||
-        (rc = s->materials.upload(mats)) || (rc = s->texels.upload(pool)) || (rc = s->texels8.upload(pool8)) ||
-        (rc = s->luts.upload(luts)) || (rc = s->pointlights.upload(pls)) || (rc = s->areal.upload(als)) ||
-        (rc = s->areal_tris.upload(ats)) || (rc = s->hdims.upload(hd)) || (rc = s->hperm.upload(hp)))
+    if ((rc = s->d_idx.upload(s->h_idx.data(), s->h_idx.size()))) return rc;
+    if ((rc = s->texrefs.upload(trefs.data(), trefs.size()))) return rc;
+    if (!on_device && ((rc = s->nodes.upload(qnodes.data(), qnodes.size())) || (rc = s->tris.upload(leaf_recs.data(), leaf_recs.size())) ||
+                       (rc = s->leaf_pb.upload(leaf_pb.data(), leaf_pb.size()))))
+        return rc;
+    if ((rc = s->tri_shade.upload(tsh.data(), tsh.size())) ||
+        (rc = s->materials.upload(mats.data(), mats.size())) || (rc = s->texels.upload(pool.data(), pool.size())) || (rc = s->texels8.upload(pool8.data(), pool8.size())) ||
+        (rc = s->luts.upload(luts.data(), luts.size())) || (rc = s->pointlights.upload(pls.data(), pls.size())) || (rc = s->areal.upload(als.data(), als.size())) ||
+        (rc = s->areal_tris.upload(ats.data(), ats.size())) || (rc = s->hdims.upload(hd.data(), hd.size())) || (rc = s->hperm.upload(hp.data(), hp.size())))
         return rc;
     { // both LTC tables in one buffer, {m0,m2,m4,m6}{amp,0,0,0} per entry (two 16-byte loads): GGX, then Beckmann
         std::vector<float4> t(2 * 2 * 4096, make_float4(0.f, 0.f, 0.f, 0.f));
@@ -1196,7 +1180,7 @@ int rgk_scene_create(const rgk_scene_desc* d, int device, rgk_scene** out) {
                 t[(size_t)w * 8192 + 2 * k] = make_float4(src[w][5 * k], src[w][5 * k + 1], src[w][5 * k + 2], src[w][5 * k + 3]);
                 t[(size_t)w * 8192 + 2 * k + 1] = make_float4(src[w][5 * k + 4], 0.f, 0.f, 0.f);
             }
-        if ((rc = s->ltc.upload(t))) return rc;
+        if ((rc = s->ltc.upload(t.data(), t.size()))) return rc;
     }
     ds.nodes = s->nodes.p;
     { const char* e = std::getenv("RGK_WALK_Q"); ds.walk_q = e ? (uint32_t)std::atoi(e) : 3u; }
@@ -1245,11 +1229,10 @@ int rgk_scene_refit(rgk_scene* s, const float* vertices, const float* normals, c
     if (!(eps == eps) || !(diameter < std::numeric_limits<float>::infinity())) return fail(RGK_ERR_INVALID, "non-finite vertex coordinates");
     // ---- records, shading normals / tangents, and the tree's boxes: on the device
     int rc;
-    if ((rc = up(s->scratch_f, vertices, 3 * (size_t)nv))) return rc;
+    if ((rc = s->scratch_f.upload(vertices, 3 * (size_t)nv))) return rc;
     DevBuf<float> d_n, d_t;
-    struct Rel { DevBuf<float>&a, &b; ~Rel() { a.release(); b.release(); } } rel{d_n, d_t};
-    if (normals && (rc = up(d_n, normals, 3 * (size_t)nv))) return rc;
-    if (tangents && (rc = up(d_t, tangents, 3 * (size_t)nv))) return rc;
+    if (normals && (rc = d_n.upload(normals, 3 * (size_t)nv))) return rc;
+    if (tangents && (rc = d_t.upload(tangents, 3 * (size_t)nv))) return rc;
     const char* err = "";
     rc = rgk_refit_bvh4_device(s->stream, s->n_refs, s->n_nodes, nt, s->scratch_f.p, normals ? d_n.p : nullptr, tangents ? d_t.p : nullptr, s->d_idx.p, s->leaf_pb.p, eps,
                                s->tris.p, s->nodes.p, s->tri_shade.p, &err);
@@ -1261,7 +1244,7 @@ int rgk_scene_refit(rgk_scene* s, const float* vertices, const float* normals, c
     float total_areal = 0.f;
     build_areal_tables(vertices, s->h_normals.data(), s->h_idx.data(), s->h_tri_mat.data(), s->h_mats.data(), (uint32_t)(s->h_areal_off.empty() ? 0 : s->h_areal_off.size() - 1),
                        s->h_areal_off.data(), s->h_areal_tris.data(), als, ats, total_areal);
-    if ((rc = s->areal.upload(als)) || (rc = s->areal_tris.upload(ats))) return rc;
+    if ((rc = s->areal.upload(als.data(), als.size())) || (rc = s->areal_tris.upload(ats.data(), ats.size()))) return rc;
     DevScene& ds = s->dev;
     ds.areal = s->areal.p; ds.areal_tris = s->areal_tris.p; ds.n_areal = (uint32_t)als.size(); ds.total_areal_power = total_areal;
     ds.epsilon = eps;
@@ -1283,7 +1266,7 @@ int rgk_scene_get_info(const rgk_scene* s, rgk_scene_info* out) {
 
 int rgk_scene_get_progress(const rgk_scene* s, rgk_progress* out) {
     if (!s || !out) return fail(RGK_ERR_INVALID, "null argument");
-    out->stage = s->h_stage ? ((volatile const uint32_t*)s->h_stage)[0] + ((volatile const uint32_t*)s->h_stage)[1] : 0u; out->stages = s->prog_stages.load(); out->rounds = s->prog_rounds.load(); out->busy = s->prog_busy.load();
+    out->stage = s->h_stage ? *(volatile const uint32_t*)s->h_stage : 0u; out->stages = s->prog_stages.load(); out->rounds = s->prog_rounds.load(); out->busy = s->prog_busy.load();
     out->round_pixels = s->prog_pixels.load(); out->round_paths = s->prog_paths.load();
     if (out->stage > out->stages) out->stage = out->stages;
     return RGK_OK;
@@ -1300,7 +1283,6 @@ int rgk_scene_set_tuning(rgk_scene* s, const char* key, double value) {
     else if (k == "sample_group") t.sample_group = value < 0 ? -1 : (int)std::min(6.0, value);
     else if (k == "batch_paths") t.batch_paths = value <= 0 ? 0 : std::max<size_t>(1024, (size_t)value);
     else if (k == "workspace_gb") t.workspace_gb = value <= 0 ? 0.0 : value;
-    else if (k == "two_lanes") t.two_lanes = value != 0;
     else if (k == "beam") t.beam = (int)std::min(2.0, std::max(0.0, value));
     else return fail(RGK_ERR_INVALID, "unknown tuning key '%s'", key);
     // per-frame lists were made under the old switches: the next round rebuilds them
@@ -1380,6 +1362,299 @@ static size_t batch_paths(const RgkTuning& tune, uint32_t reverse) {
     return std::min<size_t>(std::max<size_t>(b, 1024), (size_t)1 << 30);
 }
 
+} // extern "C"
+
+namespace {
+// ------------------------------------------------------------------ the round driver
+// rgk_render_round_device: the round's pixel list (prepare_round_lists), a plan of passes the workspace holds (plan_passes), and
+// per pass -- pixels [j0, j0 + npix) of the list x samples [s0, s0 + ns) -- its launches queued on the scene's stream
+// (queue_pass), a wait, and its queue counters added to the round's totals (add_pass_counters).
+
+// Per-kernel records of a round (rgk_counters::kernel and the four class sums).  RGK_FLAG_TIME_KERNELS: a pair of events around
+// every launch.  RGK_FLAG_COUNT_TRAVERSAL: the traversal counters (stats[0..3]: closest nodes / triangles, shadow nodes /
+// triangles) are read back after every traversal launch, so that each kernel gets its own share (stream-ordered copies; nobody
+// times a counting round).  The pass code names the kernel class of each launch: run(class, launch).
+struct KernelLog {
+    rgk_scene* s;
+    bool timing, count_stats;
+    struct Ev { int cls; hipEvent_t a, b; };
+    std::vector<Ev> evs;
+    size_t ev_used = 0; // events of the scene's pool taken by this round
+    std::vector<std::pair<int, std::array<unsigned long long, 4>>> snaps;
+
+    KernelLog(rgk_scene* s_, uint32_t flags)
+        : s(s_), timing((flags & RGK_FLAG_TIME_KERNELS) != 0), count_stats((flags & RGK_FLAG_COUNT_TRAVERSAL) != 0) {
+        if (count_stats) snaps.reserve(4096);
+    }
+    static bool closest(int k) { return k == RGK_K_TRACE_CAMERA || k == RGK_K_TRACE_CLOSEST || k == RGK_K_LIGHT_TRACE; }
+    static bool shadow(int k) { return k == RGK_K_SHADOW_FIRST || k == RGK_K_SHADOW || k == RGK_K_SHADOW_JOBS || k == RGK_K_LIGHT_SPLAT; }
+    static bool shade(int k) { return k == RGK_K_SHADE_FIRST || k == RGK_K_SHADE || k == RGK_K_CONNECT || k == RGK_K_LIGHT_SHADE; }
+    int event(hipEvent_t& e) {
+        if (ev_used == s->events.size()) { hipEvent_t n; HIPCHK(hipEventCreate(&n)); s->events.push_back(n); }
+        e = s->events[ev_used++];
+        return 0;
+    }
+    template <class Launch>
+    int run(int cls, Launch&& launch) {
+        Ev ev{cls, nullptr, nullptr};
+        if (timing) {
+            int rc;
+            if ((rc = event(ev.a)) || (rc = event(ev.b))) return rc;
+            HIPCHK(hipEventRecord(ev.a, s->stream));
+        }
+        launch();
+        if (timing) {
+            HIPCHK(hipEventRecord(ev.b, s->stream));
+            evs.push_back(ev);
+        }
+        if (count_stats && (closest(cls) || shadow(cls))) {
+            snaps.emplace_back(cls, std::array<unsigned long long, 4>{});
+            HIPCHK(hipMemcpyAsync(snaps.back().second.data(), s->stats.p, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->stream));
+            HIPCHK(hipStreamSynchronize(s->stream));
+        }
+        return 0;
+    }
+    int fold(rgk_counters& c) const {
+        for (const Ev& e : evs) {
+            float ms = 0.f;
+            HIPCHK(hipEventElapsedTime(&ms, e.a, e.b));
+            rgk_kernel_stat& ks = c.kernel[e.cls];
+            ks.ms += ms; ks.launches++;
+            if (closest(e.cls)) { c.ms_trace += ms; c.n_trace_launches++; }
+            else if (shadow(e.cls)) { c.ms_shadow += ms; c.n_shadow_launches++; }
+            else if (shade(e.cls)) { c.ms_shade += ms; c.n_shade_launches++; }
+            else c.ms_other += ms;
+        }
+        std::array<unsigned long long, 4> prev{}; // per-kernel traversal counters: differences between consecutive read-backs
+        for (const auto& sn : snaps) {
+            rgk_kernel_stat& ks = c.kernel[sn.first];
+            const int o = closest(sn.first) ? 0 : 2;
+            ks.node_visits += sn.second[o] - prev[o];
+            ks.tri_tests += sn.second[o + 1] - prev[o + 1];
+            prev = sn.second;
+        }
+        return 0;
+    }
+};
+
+// Deep path loops (depth > 12): the length of the next queue is read back every other bounce from the fourth on; it bounds the
+// grids of the following launches (queues only shrink) and ends the loop once no path is left.  The copy lands in pinned memory;
+// polling it costs microseconds where hipStreamSynchronize was measured at 2-3 ms per call (blocking wait), more than the
+// launches it saves.
+int queue_len(rgk_scene* s, const uint32_t* dptr, uint32_t& out) {
+    volatile uint32_t* h = s->h_counters;
+    h[0] = 0xffffffffu; // never a queue length (queues hold < 2^30 entries)
+    HIPCHK(hipMemcpyAsync(s->h_counters, dptr, sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+    for (uint64_t spins = 0; h[0] == 0xffffffffu; spins++) {
+        if ((spins & 0xfffff) != 0xfffff) continue;
+        // every ~1 M polls ask the stream: not-ready means keep polling, success means the copy has landed (re-read), anything
+        // else is a sticky launch / device error that would otherwise spin here for ever
+        const hipError_t q = hipStreamQuery(s->stream);
+        if (q == hipErrorNotReady) continue;
+        if (q != hipSuccess) return fail(RGK_ERR_DEVICE, "queue-length read-back: %s", hipGetErrorString(q));
+        if (h[0] == 0xffffffffu) HIPCHK(hipStreamSynchronize(s->stream));
+        if (h[0] == 0xffffffffu) return fail(RGK_ERR_DEVICE, "queue-length read-back never landed");
+        break;
+    }
+    out = h[0];
+    return 0;
+}
+
+// A finished pass's share of the round's totals, from its host counter blocks (camera phase, then light sub-path phase): path
+// and shadow rays as the reference counts them, and what each kernel processed (rays / vertices / paths).
+void add_pass_counters(const uint32_t* hc, const PassParams& pp, bool light_entry, rgk_counters& c) {
+    const uint32_t* hl = hc + RGK_CNT_TOTAL;
+    const uint32_t n0 = pp.npix * pp.ns;
+    auto units = [&c](int k) -> uint64_t& { return c.kernel[k].units; };
+    for (uint32_t b = 0; b < pp.depth; b++) { c.path_rays += hc[RGK_CNT_QUEUE + b]; c.shadow_rays += hc[RGK_CNT_SHADOW + b] + hc[RGK_CNT_SRAYS + b]; }
+    units(RGK_K_TRACE_CAMERA) += hc[RGK_CNT_QUEUE]; units(RGK_K_SHADE_FIRST) += hc[RGK_CNT_QUEUE];
+    for (uint32_t b = 1; b < pp.depth; b++) { units(RGK_K_TRACE_CLOSEST) += hc[RGK_CNT_QUEUE + b]; units(RGK_K_SHADE) += hc[RGK_CNT_QUEUE + b]; }
+    for (uint32_t b = 0; b < pp.depth; b++) {
+        units((b == 0 && light_entry) ? RGK_K_SHADOW_FIRST : RGK_K_SHADOW) += hc[RGK_CNT_SHADOW + b];
+        units(RGK_K_SHADOW_JOBS) += hc[RGK_CNT_CONN + b]; units(RGK_K_CONNECT) += hc[RGK_CNT_CONN + b];
+    }
+    for (uint32_t k = 0; k < pp.reverse; k++) {
+        units(RGK_K_LIGHT_TRACE) += hl[RGK_CNT_QUEUE + k]; units(RGK_K_LIGHT_SHADE) += hl[RGK_CNT_HITS + k];
+        units(RGK_K_LIGHT_SPLAT) += hl[RGK_CNT_SHADOW + k];
+    }
+    units(RGK_K_RESOLVE) += n0;
+    // (light rays: the reference traces and counts one per path, path_tracer.cpp:126,349 -- the ones culled before the queue included)
+    for (uint32_t k = 0; k < pp.reverse; k++) { c.path_rays += k == 0 ? n0 : hl[RGK_CNT_QUEUE + k]; c.shadow_rays += hl[RGK_CNT_SHADOW + k]; }
+}
+
+// The round's pixel list in Tracer::Render order and its per-pixel seeds (a1, a2), built on the device from the tile list, and
+// the camera rays' entry nodes per pixel group.  P: the round's pixels (0: nothing queued).  `toff` receives the tiles' offsets
+// into the list, which a queued copy reads: the caller keeps it until it has synchronised the stream.
+int prepare_round_lists(rgk_scene* s, const rgk_camera* camera, const rgk_params* prm, const rgk_tile* tiles, uint32_t n_tiles,
+                        std::vector<uint32_t>& toff, size_t& P) {
+    toff.assign(n_tiles + 1, 0u);
+    for (uint32_t i = 0; i < n_tiles; i++) {
+        const rgk_tile& t = tiles[i];
+        if (t.x1 > prm->xres || t.y1 > prm->yres || t.x0 > t.x1 || t.y0 > t.y1) return fail(RGK_ERR_INVALID, "tile %u outside the frame", i);
+        const uint64_t n = (uint64_t)toff[i] + (uint64_t)(t.x1 - t.x0) * (t.y1 - t.y0);
+        if (n >= (1ull << 31)) return fail(RGK_ERR_UNSUPPORTED, "more than 2^31 pixels in one round");
+        toff[i + 1] = (uint32_t)n;
+    }
+    P = toff[n_tiles];
+    if (P == 0) return 0;
+    hipStream_t st = s->stream;
+    int rc;
+    if ((rc = s->pix_xy.alloc(P)) || (rc = s->pix_seed.alloc(P)) || (rc = s->tile_buf.alloc((size_t)n_tiles * 5 + n_tiles + 1))) return rc;
+    static_assert(sizeof(rgk_tile) == 5 * sizeof(uint32_t), "rgk_tile layout");
+    HIPCHK(hipMemcpyAsync(s->tile_buf.p, tiles, (size_t)n_tiles * sizeof(rgk_tile), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(s->tile_buf.p + (size_t)n_tiles * 5, toff.data(), (n_tiles + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    rgk_launch_build_pixel_list(st, reinterpret_cast<const rgk_tile*>(s->tile_buf.p), s->tile_buf.p + (size_t)n_tiles * 5, n_tiles, s->pix_xy.p, s->pix_seed.p);
+    if (!s->tune.entry_points) { // (off: every camera ray starts at the root)
+        s->entry.release(); s->entry_cap.release();
+        return 0;
+    }
+    // the entry nodes depend on the camera and on which pixels the list holds in which order -- not on the seeds: a frame's
+    // rounds share them (0.7 ms per round at 1080p otherwise)
+    uint64_t key = 1469598103934665603ull;
+    auto mix = [&key](const void* p, size_t n) { const unsigned char* b = (const unsigned char*)p; for (size_t i = 0; i < n; i++) { key ^= b[i]; key *= 1099511628211ull; } };
+    mix(camera, sizeof(*camera)); mix(&prm->xres, sizeof(prm->xres)); mix(&prm->yres, sizeof(prm->yres));
+    for (uint32_t t = 0; t < n_tiles; t++) mix(&tiles[t], 4 * sizeof(uint32_t)); // x0, x1, y0, y1 (the seed is the fifth word)
+    const size_t n_entry = ((size_t)P + RGK_ENTRY_PIX - 1) / RGK_ENTRY_PIX * RGK_ENTRY_K;
+    if (s->entry.p && s->entry_n == n_entry && s->entry_key == key) return 0;
+    if ((rc = s->entry.alloc(n_entry)) || (rc = s->entry_cap.alloc(n_entry / RGK_ENTRY_K + 1)) || (rc = s->trange.alloc((n_entry / RGK_ENTRY_K + 1) * 2))) return rc;
+    DevCamera cam0;
+    make_camera(camera, cam0);
+    rgk_launch_entry_points(st, s->dev, cam0, prm->xres, prm->yres, s->pix_xy.p, (uint32_t)P, 0u, (uint32_t)(n_entry / RGK_ENTRY_K), nullptr, s->entry.p, s->entry_cap.p);
+    s->entry_key = key; s->entry_n = n_entry;
+    s->entry_capped = 0; s->lentry_done = 0; // a new frame: capped / light-side lists are rebuilt as its first passes finish
+    return 0;
+}
+
+// The pass plan: pixel ranges of npix_pass pixels x equal-sized sample passes of ns_pass samples, and the workspace for them.
+// Paths per pass: what the card has room for now (an existing workspace counts as room); halved on an allocation failure.
+int plan_passes(rgk_scene* s, const rgk_params* prm, size_t P, uint32_t R, size_t& npix_pass, uint32_t& ns_pass) {
+    size_t B = batch_paths(s->tune, R);
+    if (!s->tune.batch_paths && s->batch_reverse >= R) B = std::max(B, s->batch); // (an explicit batch size is taken literally)
+    int rc;
+    for (;;) {
+        npix_pass = std::min(P, B);
+        const uint32_t ns_max = (uint32_t)std::max<size_t>(1, std::min<size_t>(prm->multisample, B / npix_pass));
+        const uint32_t n_sample_passes = (prm->multisample + ns_max - 1) / ns_max;
+        ns_pass = (prm->multisample + n_sample_passes - 1) / n_sample_passes; // equal-sized passes
+        rc = ensure_workspace(s, npix_pass * ns_pass, R);
+        if (rc != RGK_ERR_OOM || B <= ((size_t)1 << 20)) break;
+        (void)hipGetLastError();
+        B /= 2;
+    }
+    if (rc) return rc;
+    return s->pixsum.alloc(P);
+}
+
+// Behind bounce 0's trace, once per frame and pixel range (later rounds and sample ranges reuse them): how far the first hits of
+// each pixel group lie -> the camera rays' entry lists capped behind them, and where the group's shadow rays can go (light-side
+// entry nodes and their boxes, which pp points to from here on).
+int queue_first_hit_lists(rgk_scene* s, KernelLog& kl, const DevCamera& cam, PassParams& pp, uint32_t P, bool cap_entries, bool light_entry) {
+    hipStream_t st = s->stream;
+    const size_t end = (size_t)pp.j0 + pp.npix;
+    const bool need_cap = cap_entries && end > s->entry_capped;
+    const bool need_light = light_entry && end > s->lentry_done;
+    int rc;
+    if ((need_cap || need_light) && (rc = kl.run(RGK_K_OTHER, [&] { rgk_launch_group_trange(st, pp, s->hit.p, s->trange.p); }))) return rc;
+    if (need_cap) {
+        const uint32_t g_first = pp.j0 >> RGK_ENTRY_SHIFT, g_last = (uint32_t)((end + RGK_ENTRY_PIX - 1) >> RGK_ENTRY_SHIFT);
+        if ((rc = kl.run(RGK_K_OTHER, [&] { rgk_launch_entry_points(st, s->dev, cam, pp.xres, pp.yres, s->pix_xy.p, P, g_first, g_last - g_first, s->trange.p, s->entry.p, s->entry_cap.p); })))
+            return rc;
+        s->entry_capped = end;
+    }
+    if (!light_entry) return 0;
+    pp.lentry = s->lentry.p; pp.lbox = s->lbox.p;
+    if (!need_light) return 0;
+    if ((rc = kl.run(RGK_K_OTHER, [&] { rgk_launch_light_entry_points(st, s->dev, cam, pp, P, s->trange.p, s->lentry.p, s->lbox.p); }))) return rc;
+    s->lentry_done = end;
+    if (s->tune.debug_bvh) { // how many pixel groups got light-side entry nodes below the root
+        const size_t g0 = pp.j0 >> RGK_ENTRY_SHIFT, g1 = (end + RGK_ENTRY_PIX - 1) >> RGK_ENTRY_SHIFT;
+        std::vector<int> he((g1 - g0) * RGK_ENTRY_K);
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipMemcpy(he.data(), s->lentry.p + g0 * RGK_ENTRY_K, he.size() * sizeof(int), hipMemcpyDeviceToHost));
+        size_t below = 0, total_e = 0;
+        for (size_t g = 0; g < g1 - g0; g++) { if (he[g * RGK_ENTRY_K] != 0) below++; for (int k = 0; k < RGK_ENTRY_K; k++) total_e += he[g * RGK_ENTRY_K + k] != 0x7fffffff; }
+        std::fprintf(stderr, "[rgk] light-side entry nodes: %zu of %zu pixel groups start below the root, %.2f entries per group\n", below, g1 - g0, (double)total_e / (double)(g1 - g0));
+    }
+    return 0;
+}
+
+// One pass, queued on the scene's stream: the light sub-path (reverse > 0), the camera path's bounces, the resolve into the
+// accumulator, a progress mark behind every bounce (`stage`: the round's stages before this pass), and the copy of the pass's
+// counter blocks into h_counters.
+int queue_pass(rgk_scene* s, KernelLog& kl, const DevCamera& cam, PassParams& pp, size_t P, bool light_entry, float* d_accum_rgb,
+               uint32_t* d_accum_count, uint32_t stage) {
+    hipStream_t st = s->stream;
+    const RgkTraceCfg& tc = s->tcfg;
+    const bool count_stats = kl.count_stats, cap_entries = s->entry.p != nullptr && s->tune.entry_cap;
+    const bool track = pp.depth > 12; // queue lengths read back (queue_len): measured, depth 10 loses 4 % to the read-backs, depth 40 gains 4 %
+    const uint32_t R = pp.reverse, n0 = pp.npix * pp.ns;
+    {   // 2^gshift samples of a pixel side by side in the slot order (rgk_kernels.h PassParams); RGK_SAMPLE_GROUP = log2
+        uint32_t g = s->tune.sample_group >= 0 ? (uint32_t)s->tune.sample_group : (uint32_t)RGK_SAMPLE_GROUP_DEFAULT;
+        while (g && (pp.ns & ((1u << g) - 1u))) g--;
+        pp.gshift = g;
+        // the bundle walk (k_trace_camera_beam) for passes whose entry lists are not capped yet -- a frame's first round:
+        // measured on the headline workload, camera launch 20.6 (per ray, uncapped) -> 17.2 ms (bundles), a one-round
+        // frame 135.2 -> 130.8 ms; against CAPPED lists the per-ray walk is the faster one (16.1 vs 17.2: a bundle tests
+        // every triangle it meets against all 8 rays, 2.86 tests per ray instead of 2.57, at half the occupancy)
+        const bool lists_capped = cap_entries && (size_t)pp.j0 + pp.npix <= s->entry_capped;
+        pp.beam = (s->tune.beam == 2 || (s->tune.beam == 1 && !lists_capped)) ? 1u : 0u;
+    }
+    float4* const rayA[2] = {s->rayA[0].p, s->rayA[1].p};
+    float4* const rayB[2] = {s->rayB[0].p, s->rayB[1].p};
+    float4 *const hit = s->hit.p, *const thr = s->thr.p, *const tot = s->tot.p, *const shA = s->shA.p, *const shB = s->shB.p, *const shC = s->shC.p;
+    uint32_t* const cn = s->counters.p;      // camera-phase counters
+    uint32_t* const cl = cn + RGK_CNT_TOTAL; // light-phase counters
+    int rc;
+    if (R > 0) {
+        // light sub-path first (its sampler dimensions are fixed), splats straight into the accumulator
+        rgk_launch_set_bound(n0, n0);
+        if ((rc = kl.run(RGK_K_OTHER, [&] { rgk_launch_init_counters(st, cl, 0u); })) || // (k_raygen_light queues the light rays that can touch the scene's box)
+            (rc = kl.run(RGK_K_LIGHT_SHADE, [&] { rgk_launch_raygen_light(st, s->dev, cam, pp, rayA[0], rayB[0], thr, cl); })))
+            return rc;
+        for (uint32_t k = 0; k < R; k++) {
+            const int q = k & 1;
+            if ((rc = kl.run(RGK_K_LIGHT_TRACE, [&] { rgk_launch_trace_closest(st, s->dev, tc, count_stats, rayA[q], rayB[q], nullptr, hit, cl + RGK_CNT_QUEUE + k, cl + RGK_CNT_FETCH_T + k, s->stats.p); })) ||
+                (rc = kl.run(RGK_K_LIGHT_SHADE, [&] { rgk_launch_list_hits(st, hit, cl + RGK_CNT_QUEUE + k, s->hitlist.p, cl + RGK_CNT_HITS + k); })) ||
+                (rc = kl.run(RGK_K_LIGHT_SHADE, [&] { rgk_launch_shade_light(st, s->dev, cam, pp, k, rayA[q], rayB[q], hit, thr, rayA[q ^ 1], rayB[q ^ 1], shA, shB, shC, cl); })) ||
+                (rc = kl.run(RGK_K_LIGHT_SPLAT, [&] { rgk_launch_trace_shadow(st, s->dev, tc, count_stats, shA, shB, shC, nullptr, nullptr, RGK_SHADOW_SPLAT, d_accum_rgb,
+                                                                              cl + RGK_CNT_SHADOW + k, cl + RGK_CNT_FETCH_S + k, s->stats.p); })))
+                return rc;
+        }
+    }
+    // the camera path: the same pipeline for uni- and bidirectional rounds (R > 0: vertices with connections take the record
+    // route -- k_shade<BDPT> -> k_connect -> k_trace_shadow_jobs -- beside the plain NEE rays)
+    if ((rc = kl.run(RGK_K_OTHER, [&] { rgk_launch_init_counters(st, cn, n0); }))) return rc;
+    uint32_t ub = n0; // upper bound on bounce b's queue
+    for (uint32_t b = 0; b < pp.depth && ub > 0; b++) {
+        const int q = b & 1;
+        rgk_launch_set_bound(ub, ub);
+        if (b == 0) // no ray queue at bounce 0: the camera ray of slot i is made where it is traced and shaded
+            rc = kl.run(RGK_K_TRACE_CAMERA, [&] { rgk_launch_trace_camera(st, s->dev, cam, pp, tc, count_stats, hit, cn + RGK_CNT_QUEUE, cn + RGK_CNT_FETCH_T, s->stats.p); });
+        else
+            rc = kl.run(RGK_K_TRACE_CLOSEST, [&] { rgk_launch_trace_closest(st, s->dev, tc, count_stats, rayA[q], rayB[q], nullptr, hit, cn + RGK_CNT_QUEUE + b, cn + RGK_CNT_FETCH_T + b, s->stats.p); });
+        if (rc || (b == 0 && (rc = queue_first_hit_lists(s, kl, cam, pp, (uint32_t)P, cap_entries, light_entry)))) return rc;
+        if ((rc = kl.run(b == 0 ? RGK_K_SHADE_FIRST : RGK_K_SHADE, [&] { rgk_launch_shade(st, s->dev, cam, pp, b, rayA[q], rayB[q], hit, thr, tot, rayA[q ^ 1], rayB[q ^ 1], shA, shB, shC, cn, R > 0); })) ||
+            (R > 0 && (rc = kl.run(RGK_K_CONNECT, [&] { rgk_launch_connect(st, s->dev, pp, b, s->jobs.p, s->rads.p, cn); }))))
+            return rc;
+        if (b == 0 && light_entry)
+            rc = kl.run(RGK_K_SHADOW_FIRST, [&] { rgk_launch_trace_shadow_first(st, s->dev, pp, tc, count_stats, shA, shB, shC, tot, cn + RGK_CNT_SHADOW + b, cn + RGK_CNT_FETCH_S + b, s->stats.p); });
+        else
+            rc = kl.run(RGK_K_SHADOW, [&] { rgk_launch_trace_shadow(st, s->dev, tc, count_stats, shA, shB, shC, tot, nullptr, RGK_SHADOW_ADD, nullptr, cn + RGK_CNT_SHADOW + b, cn + RGK_CNT_FETCH_S + b, s->stats.p); });
+        // (the vertex queue after the plain rays: both add into the slot sums, a slot has a vertex in ONE of the two queues)
+        if (rc || (R > 0 && (rc = kl.run(RGK_K_SHADOW_JOBS, [&] { rgk_launch_trace_shadow_jobs(st, s->dev, pp, tc, count_stats, s->jobs.p, s->rads.p, tot, cn + RGK_CNT_CONN + b, cn + RGK_CNT_FETCH_J + b, s->stats.p); }))))
+            return rc;
+        rgk_launch_stage_mark(st, s->h_stage, stage + b + 1);
+        if (track && b >= 3 && (b & 1) && b + 1 < pp.depth && (rc = queue_len(s, cn + RGK_CNT_QUEUE + b + 1, ub))) return rc;
+    }
+    if ((rc = kl.run(RGK_K_RESOLVE, [&] { rgk_launch_resolve(st, pp, tot, s->pixsum.p, d_accum_rgb, d_accum_count); }))) return rc;
+    rgk_launch_stage_mark(st, s->h_stage, stage + std::max(1u, pp.depth)); // (all of the pass's stages: bounces that never ran count too)
+    HIPCHK(hipMemcpyAsync(s->h_counters, cn, 2 * RGK_CNT_TOTAL * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    return 0;
+}
+} // namespace
+
+extern "C" {
+
 int rgk_render_round_device(rgk_scene* s, const rgk_camera* camera, const rgk_params* prm, const rgk_tile* tiles, uint32_t n_tiles,
                             float* d_accum_rgb, uint32_t* d_accum_count, rgk_counters* counters) {
     if (!s || !camera || !prm || (!tiles && n_tiles) || !d_accum_rgb || !d_accum_count) return fail(RGK_ERR_INVALID, "null argument");
@@ -1390,148 +1665,38 @@ int rgk_render_round_device(rgk_scene* s, const rgk_camera* camera, const rgk_pa
     if (prm->sampler != RGK_SAMPLER_HALTON) return fail(RGK_ERR_UNSUPPORTED, "the HIP path implements the Halton sampler only");
     HIPCHK(hipSetDevice(s->device));
     if (counters) std::memset(counters, 0, sizeof(*counters));
-    // ---- pixel list in Tracer::Render order, per-pixel seeds (a1, a2): built on the device from the tile list
-    std::vector<uint32_t> toff(n_tiles + 1, 0u);
-    for (uint32_t i = 0; i < n_tiles; i++) {
-        const rgk_tile& t = tiles[i];
-        if (t.x1 > prm->xres || t.y1 > prm->yres || t.x0 > t.x1 || t.y0 > t.y1) return fail(RGK_ERR_INVALID, "tile %u outside the frame", i);
-        const uint64_t n = (uint64_t)toff[i] + (uint64_t)(t.x1 - t.x0) * (t.y1 - t.y0);
-        if (n >= (1ull << 31)) return fail(RGK_ERR_UNSUPPORTED, "more than 2^31 pixels in one round");
-        toff[i + 1] = (uint32_t)n;
-    }
-    const size_t P = toff[n_tiles];
-    if (P == 0) return RGK_OK;
+    std::vector<uint32_t> toff; // (read by a queued copy: it lives to the end of this call, which synchronises the stream before returning)
+    size_t P = 0, npix_pass = 0;
+    uint32_t ns_pass = 0;
     int rc;
-    {
-        hipStream_t st0 = s->stream;
-        if ((rc = s->pix_xy.alloc(P)) || (rc = s->pix_seed.alloc(P)) || (rc = s->tile_buf.alloc((size_t)n_tiles * 5 + n_tiles + 1))) return rc;
-        // (both sources outlive the copies: `toff` lives to the end of this call, which synchronises the stream before returning)
-        static_assert(sizeof(rgk_tile) == 5 * sizeof(uint32_t), "rgk_tile layout");
-        HIPCHK(hipMemcpyAsync(s->tile_buf.p, tiles, (size_t)n_tiles * sizeof(rgk_tile), hipMemcpyHostToDevice, st0));
-        HIPCHK(hipMemcpyAsync(s->tile_buf.p + (size_t)n_tiles * 5, toff.data(), (n_tiles + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st0));
-        rgk_launch_build_pixel_list(st0, reinterpret_cast<const rgk_tile*>(s->tile_buf.p), s->tile_buf.p + (size_t)n_tiles * 5, n_tiles, s->pix_xy.p, s->pix_seed.p);
-        if (s->tune.entry_points) { // (off: every camera ray starts at the root)
-            // the entry nodes depend on the camera and on which pixels the list holds in which order -- not on the seeds: a frame's
-            // rounds share them (0.7 ms per round at 1080p otherwise)
-            uint64_t key = 1469598103934665603ull;
-            auto mix = [&key](const void* p, size_t n) { const unsigned char* b = (const unsigned char*)p; for (size_t i = 0; i < n; i++) { key ^= b[i]; key *= 1099511628211ull; } };
-            mix(camera, sizeof(*camera)); mix(&prm->xres, sizeof(prm->xres)); mix(&prm->yres, sizeof(prm->yres));
-            for (uint32_t t = 0; t < n_tiles; t++) mix(&tiles[t], 4 * sizeof(uint32_t)); // x0, x1, y0, y1 (the seed is the fifth word)
-            const size_t n_entry = ((size_t)P + RGK_ENTRY_PIX - 1) / RGK_ENTRY_PIX * RGK_ENTRY_K;
-            if (!(s->entry.p && s->entry_n == n_entry && s->entry_key == key)) {
-                if ((rc = s->entry.alloc(n_entry)) || (rc = s->entry_cap.alloc(n_entry / RGK_ENTRY_K + 1)) || (rc = s->trange.alloc((n_entry / RGK_ENTRY_K + 1) * 2))) return rc;
-                DevCamera cam0;
-                make_camera(camera, cam0);
-                rgk_launch_entry_points(st0, s->dev, cam0, prm->xres, prm->yres, s->pix_xy.p, (uint32_t)P, 0u, (uint32_t)(n_entry / RGK_ENTRY_K), nullptr, s->entry.p, s->entry_cap.p);
-                s->entry_key = key; s->entry_n = n_entry;
-                s->entry_capped = 0; s->lentry_done = 0; // a new frame: capped / light-side lists are rebuilt as its first passes finish
-            }
-        } else { s->entry.release(); s->entry_cap.release(); }
-    }
+    if ((rc = prepare_round_lists(s, camera, prm, tiles, n_tiles, toff, P))) return rc;
+    if (P == 0) return RGK_OK;
     // no light at all: TracePath builds no light sub-path (`reverse > 0 && valid light`), same as reverse == 0
     const uint32_t R = (s->dev.total_point_power + s->dev.total_areal_power > 0.0f) ? prm->reverse : 0u;
-    // paths per pass: what the card has room for now (an existing workspace counts as room); halved on an allocation failure
-    size_t B = batch_paths(s->tune, R);
-    if (!s->tune.batch_paths && s->batch_reverse >= R) B = std::max(B, s->batch); // (an explicit batch size is taken literally)
-    // Two lanes (an experiment, off by default: RGK_TWO_LANES=1 / rgk_scene_set_tuning "two_lanes"): a unidirectional round of
-    // shallow depth runs the two halves of its pixel list as two passes side by side on two streams, each in its own half of the
-    // workspace -- the idea being that every launch ends in a tail of waves still finishing which the other lane's launches could
-    // fill.  Measured inside one process, same bits: Sponza 1080p x 256 126.7 vs 126.9 ms per round (nothing), Cornell 1024 x 256
-    // 119.3 vs 110.4 (8 % WORSE: ten bounces of short launches, each now competing for the card) -- the launches fill the machine
-    // one at a time, as round 2 found with two processes and with two host threads.
-    // What keeps the lanes apart: a lane is picked per PIXEL RANGE, so all sample passes of a range run in order on one stream
-    // (they share the range's pixsum entries, and a later pass reads the entry lists its first pass capped); and the ranges
-    // are whole 1024-pixel blocks, so no pixel group (RGK_ENTRY_PIX) -- its trange, entry list, cap, light-side list and box --
-    // belongs to two lanes.  A batch too small for a whole block per lane renders on one lane.
-    const bool count_stats = (prm->flags & RGK_FLAG_COUNT_TRAVERSAL) != 0;
-    const bool track = prm->depth > 12; // measured: depth 10 loses 4 % to the read-backs, depth 40 gains 4 %
-    bool two = s->tune.two_lanes && R == 0 && !track && !count_stats && (uint64_t)P * prm->multisample >= (1ull << 22) && P >= 4096;
-    static_assert(1024 % RGK_ENTRY_PIX == 0, "two-lane pixel ranges are whole pixel groups");
-    size_t npix_pass;
-    uint32_t ns_pass;
-    size_t lane_cap = 0; // paths per lane = offset of the second lane in every workspace array
-    for (;;) {
-        const size_t Bl = two ? B / 2 : B; // per lane
-        npix_pass = std::min(P, Bl);
-        if (two) { // at least two ranges: halves of the list at most, whole 1024-pixel blocks
-            npix_pass = std::min(npix_pass, ((P + 1) / 2 + 1023) & ~(size_t)1023) & ~(size_t)1023;
-            if (npix_pass == 0) { two = false; continue; }
-        }
-        const uint32_t ns_max = (uint32_t)std::max<size_t>(1, std::min<size_t>(prm->multisample, Bl / npix_pass));
-        const uint32_t n_sample_passes = (prm->multisample + ns_max - 1) / ns_max;
-        ns_pass = (prm->multisample + n_sample_passes - 1) / n_sample_passes; // equal-sized passes
-        lane_cap = npix_pass * ns_pass;
-        rc = ensure_workspace(s, two ? 2 * lane_cap : lane_cap, R);
-        if (rc != RGK_ERR_OOM || B <= ((size_t)1 << 20)) break;
-        (void)hipGetLastError();
-        B /= 2;
-    }
-    if (rc) return rc;
-    if ((rc = s->pixsum.alloc(P))) return rc;
+    if ((rc = plan_passes(s, prm, P, R, npix_pass, ns_pass))) return rc;
 
     DevCamera cam;
     make_camera(camera, cam);
-    hipStream_t st = s->stream;
-    const bool timing = (prm->flags & RGK_FLAG_TIME_KERNELS) != 0;
-    HIPCHK(hipMemsetAsync(s->stats.p, 0, 8 * sizeof(unsigned long long), st));
-    struct Ev { int cls; hipEvent_t a, b; };
-    std::vector<Ev> evs;
-    size_t ev_used = 0;
-    auto ev_get = [&](hipEvent_t& e) -> int {
-        if (ev_used == s->events.size()) { hipEvent_t n; HIPCHK(hipEventCreate(&n)); s->events.push_back(n); }
-        e = s->events[ev_used++];
-        return 0;
-    };
-    // counting mode: the traversal counters (stats[0..3]: closest nodes / triangles, shadow nodes / triangles) are read back after
-    // every traversal launch, so that each kernel gets its own share (stream-ordered copies; nobody times a counting round)
-    std::vector<std::pair<int, std::array<unsigned long long, 4>>> snaps;
-    if (count_stats) snaps.reserve(4096);
-#define TIMED(kid_, call)                                                \
-    do {                                                                 \
-        if (timing) {                                                    \
-            Ev ev; ev.cls = (kid_);                                      \
-            if ((rc = ev_get(ev.a)) || (rc = ev_get(ev.b))) return rc;   \
-            HIPCHK(hipEventRecord(ev.a, st));                            \
-            call;                                                        \
-            HIPCHK(hipEventRecord(ev.b, st));                            \
-            evs.push_back(ev);                                           \
-        } else { call; }                                                 \
-        if (count_stats && is_trace_kernel(kid_)) {                      \
-            snaps.emplace_back((int)(kid_), std::array<unsigned long long, 4>{}); \
-            HIPCHK(hipMemcpyAsync(snaps.back().second.data(), s->stats.p, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st)); \
-            HIPCHK(hipStreamSynchronize(st));                            \
-        }                                                                \
-    } while (0)
-    auto is_trace_kernel = [](int k) { return k == RGK_K_TRACE_CAMERA || k == RGK_K_TRACE_CLOSEST || k == RGK_K_SHADOW_FIRST || k == RGK_K_SHADOW ||
-                                              k == RGK_K_SHADOW_JOBS || k == RGK_K_LIGHT_TRACE || k == RGK_K_LIGHT_SPLAT; };
-    uint64_t units[RGK_K_COUNT] = {};
-
-    uint64_t path_rays = 0, shadow_rays = 0;
+    HIPCHK(hipMemsetAsync(s->stats.p, 0, 8 * sizeof(unsigned long long), s->stream));
+    KernelLog kl(s, prm->flags);
     // progress: one stage per bounce per pass; a one-thread kernel queued behind each bounce writes the stage number into pinned
     // host memory when the DEVICE gets there (a host function in the stream did the same but stalls the stream for a host
     // round trip per mark)
+    const uint32_t pass_stages = std::max(1u, prm->depth);
     {
         const uint32_t n_pix_passes = (uint32_t)((P + npix_pass - 1) / npix_pass), n_s_passes = (prm->multisample + ns_pass - 1) / ns_pass;
-        ((volatile uint32_t*)s->h_stage)[0] = 0; ((volatile uint32_t*)s->h_stage)[1] = 0; s->prog_stages = n_pix_passes * n_s_passes * std::max(1u, prm->depth);
+        *(volatile uint32_t*)s->h_stage = 0; s->prog_stages = n_pix_passes * n_s_passes * pass_stages;
         s->prog_pixels = P; s->prog_paths = (uint64_t)P * prm->multisample; s->prog_busy = 1;
     }
-    struct Done { rgk_scene* s; ~Done() { ((volatile uint32_t*)s->h_stage)[0] = s->prog_stages.load(); ((volatile uint32_t*)s->h_stage)[1] = 0; s->prog_busy = 0; } } done_guard{s};
-    uint32_t stage_targets[2] = {0, 0}; // per lane: what its stage word must read once everything queued on it so far has run
-    int lane = 0;
-    auto stage_mark = [&](uint32_t upto) -> int { // queued: "this lane's stages up to `upto` are done" (monotonic: bounces that never ran count too)
-        rgk_launch_stage_mark(st, s->h_stage + lane, upto);
-        return 0;
-    };
+    struct Done { rgk_scene* s; ~Done() { *(volatile uint32_t*)s->h_stage = s->prog_stages.load(); s->prog_busy = 0; } } done_guard{s};
     PassParams pp{};
     pp.multisample = prm->multisample; pp.depth = prm->depth; pp.xres = prm->xres; pp.yres = prm->yres;
     pp.clamp = prm->clamp; pp.russian = prm->russian; pp.bumpmap_scale = prm->bumpmap_scale; pp.reverse = R;
     pp.lstart = s->lstart.p; pp.lv = s->lv.p; pp.hitlist = s->hitlist.p; pp.lvmask = s->lvmask.p; pp.conn = s->conn.p; pp.connlist = s->connlist.p;
     pp.batch = (uint32_t)s->batch;
-    pp.pix_xy = s->pix_xy.p; pp.pix_seed = s->pix_seed.p;
+    pp.pix_xy = s->pix_xy.p; pp.pix_seed = s->pix_seed.p; pp.light = s->light.p; pp.generic = s->generic.p;
     pp.entry = s->entry.p; // (null when switched off; only the unidirectional bounce-0 launch reads it)
     pp.entry_cap = s->entry_cap.p;
-    const bool cap_entries = s->entry.p != nullptr && s->tune.entry_cap;
-    pp.lentry = nullptr;
     // one point / sphere light and nothing else that emits: every first-vertex shadow ray starts there (k_entry_points_light)
     const bool light_entry = s->entry.p && s->tune.light_entry && s->dev.n_pointlights == 1 && s->dev.n_areal == 0;
     if (light_entry) {
@@ -1539,213 +1704,35 @@ int rgk_render_round_device(rgk_scene* s, const rgk_camera* camera, const rgk_pa
         if ((rc = s->lentry.alloc(groups * RGK_ENTRY_K)) || (rc = s->trange.alloc(groups * 2)) || (rc = s->lbox.alloc(groups * 2))) return rc;
     }
     if ((rc = s->htab.alloc((size_t)192 * prm->multisample))) return rc;
-    TIMED(RGK_K_OTHER, rgk_launch_build_halton_table(st, s->dev, prm->multisample, s->htab.p));
+    if ((rc = kl.run(RGK_K_OTHER, [&] { rgk_launch_build_halton_table(s->stream, s->dev, prm->multisample, s->htab.p); }))) return rc;
     pp.htab = s->htab.p;
-    // Deep path loops (depth > 12): the length of the next queue is read back every other bounce from the fourth on; it
-    // bounds the grids of the following launches (queues only shrink) and ends the loop once no path is left.
-    auto queue_len = [&](const uint32_t* dptr, uint32_t& out) -> int {
-        // the copy lands in pinned memory; polling it costs microseconds where hipStreamSynchronize was measured at
-        // 2-3 ms per call (blocking wait), more than the launches it saves
-        volatile uint32_t* h = s->h_counters;
-        h[0] = 0xffffffffu; // never a queue length (queues hold < 2^30 entries)
-        HIPCHK(hipMemcpyAsync(s->h_counters, dptr, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        for (uint64_t spins = 0; h[0] == 0xffffffffu; spins++) {
-            if ((spins & 0xfffff) != 0xfffff) continue;
-            // every ~1 M polls ask the stream: not-ready means keep polling, success means the copy has landed (re-read), anything
-            // else is a sticky launch / device error that would otherwise spin here for ever
-            const hipError_t q = hipStreamQuery(st);
-            if (q == hipErrorNotReady) continue;
-            if (q != hipSuccess) return fail(RGK_ERR_DEVICE, "queue-length read-back: %s", hipGetErrorString(q));
-            if (h[0] == 0xffffffffu) HIPCHK(hipStreamSynchronize(st));
-            if (h[0] == 0xffffffffu) return fail(RGK_ERR_DEVICE, "queue-length read-back never landed");
-            break;
-        }
-        out = h[0];
-        return 0;
-    };
-    // a lane's finished pass: wait for its stream, add its queue counters to the round's totals
-    bool pending[2] = {false, false};
-    uint32_t pend_n0[2] = {0, 0};
-    uint32_t range_index = 0;
-    const bool light_entry_units = light_entry;
-    auto harvest = [&](int l) -> int {
-        HIPCHK(hipStreamSynchronize(l ? s->stream2 : s->stream));
-        pending[l] = false;
-        const uint32_t* hc = s->h_counters + (size_t)l * 2 * RGK_CNT_TOTAL;
-        const uint32_t n0 = pend_n0[l];
-        for (uint32_t b = 0; b < prm->depth; b++) { path_rays += hc[RGK_CNT_QUEUE + b]; shadow_rays += hc[RGK_CNT_SHADOW + b] + hc[RGK_CNT_SRAYS + b]; }
-        // what each kernel processed in this pass: rays / vertices, from the queue counters
-        units[RGK_K_TRACE_CAMERA] += hc[RGK_CNT_QUEUE]; units[RGK_K_SHADE_FIRST] += hc[RGK_CNT_QUEUE];
-        for (uint32_t b = 1; b < prm->depth; b++) { units[RGK_K_TRACE_CLOSEST] += hc[RGK_CNT_QUEUE + b]; units[RGK_K_SHADE] += hc[RGK_CNT_QUEUE + b]; }
-        for (uint32_t b = 0; b < prm->depth; b++) {
-            units[(b == 0 && light_entry_units) ? RGK_K_SHADOW_FIRST : RGK_K_SHADOW] += hc[RGK_CNT_SHADOW + b];
-            units[RGK_K_SHADOW_JOBS] += hc[RGK_CNT_CONN + b]; units[RGK_K_CONNECT] += hc[RGK_CNT_CONN + b];
-        }
-        for (uint32_t k = 0; k < R; k++) {
-            units[RGK_K_LIGHT_TRACE] += hc[RGK_CNT_TOTAL + RGK_CNT_QUEUE + k]; units[RGK_K_LIGHT_SHADE] += hc[RGK_CNT_TOTAL + RGK_CNT_HITS + k];
-            units[RGK_K_LIGHT_SPLAT] += hc[RGK_CNT_TOTAL + RGK_CNT_SHADOW + k];
-        }
-        units[RGK_K_RESOLVE] += n0;
-        // (light rays: the reference traces and counts one per path, path_tracer.cpp:126,349 -- the ones culled before the queue included)
-        for (uint32_t k = 0; k < R; k++) { path_rays += k == 0 ? n0 : hc[RGK_CNT_TOTAL + RGK_CNT_QUEUE + k]; shadow_rays += hc[RGK_CNT_TOTAL + RGK_CNT_SHADOW + k]; }
-        return 0;
-    };
-    // everything queued so far (pixel and seed lists, entry nodes, the Halton table) is on the first stream: the second waits for it
-    HIPCHK(hipEventRecord(s->ev_prelude, s->stream));
-    if (two) HIPCHK(hipStreamWaitEvent(s->stream2, s->ev_prelude, 0));
-    for (size_t j0 = 0; j0 < P; j0 += npix_pass, range_index++) {
+
+    rgk_counters tot{};
+    uint32_t stage = 0; // progress stages of the passes before this one
+    for (size_t j0 = 0; j0 < P; j0 += npix_pass) {
         pp.j0 = (uint32_t)j0;
         pp.npix = (uint32_t)std::min(npix_pass, P - j0);
-        for (uint32_t s0 = 0; s0 < prm->multisample; s0 += ns_pass) {
+        for (uint32_t s0 = 0; s0 < prm->multisample; s0 += ns_pass, stage += pass_stages) {
             pp.s0 = s0;
             pp.ns = std::min(ns_pass, prm->multisample - s0);
-            {   // 2^gshift samples of a pixel side by side in the slot order (rgk_kernels.h PassParams); RGK_SAMPLE_GROUP = log2
-                uint32_t g = s->tune.sample_group >= 0 ? (uint32_t)s->tune.sample_group : (uint32_t)RGK_SAMPLE_GROUP_DEFAULT;
-                while (g && (pp.ns & ((1u << g) - 1u))) g--;
-                pp.gshift = g;
-                // the bundle walk (k_trace_camera_beam) for passes whose entry lists are not capped yet -- a frame's first round:
-                // measured on the headline workload, camera launch 20.6 (per ray, uncapped) -> 17.2 ms (bundles), a one-round
-                // frame 135.2 -> 130.8 ms; against CAPPED lists the per-ray walk is the faster one (16.1 vs 17.2: a bundle tests
-                // every triangle it meets against all 8 rays, 2.86 tests per ray instead of 2.57, at half the occupancy)
-                const bool lists_capped = cap_entries && (size_t)pp.j0 + pp.npix <= s->entry_capped;
-                pp.beam = (s->tune.beam == 2 || (s->tune.beam == 1 && !lists_capped)) ? 1u : 0u;
-            }
-            const uint32_t n0 = pp.npix * pp.ns;
-            // which lane (one per pixel range: its sample passes stay in order on one stream): its stream, its half of every
-            // workspace array, its counter blocks; a lane's previous pass is harvested (waited for, its counters added up) before
-            // the next one is queued on it
-            lane = two ? (int)(range_index & 1u) : 0;
-            st = lane ? s->stream2 : s->stream;
-            if (pending[lane] && (rc = harvest(lane))) return rc;
-            const size_t off = (size_t)lane * lane_cap;
-            float4* const w_rayA[2] = {s->rayA[0].p + off, s->rayA[1].p + off};
-            float4* const w_rayB[2] = {s->rayB[0].p + off, s->rayB[1].p + off};
-            float4 *const w_hit = s->hit.p + off, *const w_thr = s->thr.p + off, *const w_tot = s->tot.p + off;
-            float4 *const w_shA = s->shA.p + off, *const w_shB = s->shB.p + off, *const w_shC = s->shC.p + off;
-            pp.light = s->light.p + off; pp.generic = s->generic.p + off;
-            uint32_t* cn = s->counters.p + (size_t)lane * 2 * RGK_CNT_TOTAL; // camera-phase counters
-            uint32_t* cl = cn + RGK_CNT_TOTAL;                               // light-phase counters
-            uint32_t& stage_target = stage_targets[lane];
-            pend_n0[lane] = n0;
-            RgkTraceCfg tcl = s->tcfg; // (the lane's own overflow area of the traversal stack)
-            if (tcl.ovf) tcl.ovf += (size_t)lane * s->ovf_lane;
-            if (R > 0) {
-                // light sub-path first (its sampler dimensions are fixed), splats straight into the accumulator
-                rgk_launch_set_bound(n0, n0);
-                TIMED(RGK_K_OTHER, rgk_launch_init_counters(st, cl, 0u)); // (k_raygen_light queues the light rays that can touch the scene's box)
-                TIMED(RGK_K_LIGHT_SHADE, rgk_launch_raygen_light(st, s->dev, cam, pp, w_rayA[0], w_rayB[0], w_thr, cl));
-                for (uint32_t k = 0; k < R; k++) {
-                    int q = k & 1;
-                    TIMED(RGK_K_LIGHT_TRACE, rgk_launch_trace_closest(st, s->dev, tcl, count_stats, w_rayA[q], w_rayB[q], nullptr, w_hit,
-                                                      cl + RGK_CNT_QUEUE + k, cl + RGK_CNT_FETCH_T + k, s->stats.p));
-                    TIMED(RGK_K_LIGHT_SHADE, rgk_launch_list_hits(st, w_hit, cl + RGK_CNT_QUEUE + k, s->hitlist.p, cl + RGK_CNT_HITS + k));
-                    TIMED(RGK_K_LIGHT_SHADE, rgk_launch_shade_light(st, s->dev, cam, pp, k, w_rayA[q], w_rayB[q], w_hit, w_thr,
-                                                    w_rayA[q ^ 1], w_rayB[q ^ 1], w_shA, w_shB, w_shC, cl));
-                    TIMED(RGK_K_LIGHT_SPLAT, rgk_launch_trace_shadow(st, s->dev, tcl, count_stats, w_shA, w_shB, w_shC, nullptr, nullptr,
-                                                     RGK_SHADOW_SPLAT, d_accum_rgb, cl + RGK_CNT_SHADOW + k, cl + RGK_CNT_FETCH_S + k, s->stats.p));
-                }
-            }
-            {   // the camera path: the same pipeline for uni- and bidirectional rounds (R > 0: vertices with connections take
-                // the record route -- k_shade<BDPT> -> k_connect -> k_trace_shadow_jobs -- beside the plain NEE rays)
-                TIMED(RGK_K_OTHER, rgk_launch_init_counters(st, cn, n0));
-                uint32_t ub = n0; // upper bound on bounce b's queue
-                for (uint32_t b = 0; b < prm->depth && ub > 0; b++) {
-                    int q = b & 1;
-                    rgk_launch_set_bound(ub, ub);
-                    if (b == 0) // no ray queue at bounce 0: the camera ray of slot i is made where it is traced and shaded
-                        TIMED(RGK_K_TRACE_CAMERA, rgk_launch_trace_camera(st, s->dev, cam, pp, tcl, count_stats, w_hit, cn + RGK_CNT_QUEUE, cn + RGK_CNT_FETCH_T, s->stats.p));
-                    else
-                        TIMED(RGK_K_TRACE_CLOSEST, rgk_launch_trace_closest(st, s->dev, tcl, count_stats, w_rayA[q], w_rayB[q], nullptr, w_hit,
-                                                          cn + RGK_CNT_QUEUE + b, cn + RGK_CNT_FETCH_T + b, s->stats.p));
-                    if (b == 0 && (cap_entries || light_entry)) {
-                        // once per frame and pixel range (later rounds and sample ranges reuse it): how far the first hits of each
-                        // pixel group lie -> camera-ray entry lists capped behind them, and where the group's shadow rays can go
-                        const bool need_cap = cap_entries && (size_t)pp.j0 + pp.npix > s->entry_capped;
-                        const bool need_light = light_entry && (size_t)pp.j0 + pp.npix > s->lentry_done;
-                        if (need_cap || need_light) TIMED(RGK_K_OTHER, rgk_launch_group_trange(st, pp, w_hit, s->trange.p));
-                        if (need_cap) {
-                            const uint32_t g_first = pp.j0 >> RGK_ENTRY_SHIFT, g_last = (uint32_t)(((size_t)pp.j0 + pp.npix + RGK_ENTRY_PIX - 1) >> RGK_ENTRY_SHIFT);
-                            TIMED(RGK_K_OTHER, rgk_launch_entry_points(st, s->dev, cam, prm->xres, prm->yres, s->pix_xy.p, (uint32_t)P, g_first, g_last - g_first, s->trange.p, s->entry.p, s->entry_cap.p));
-                            s->entry_capped = (size_t)pp.j0 + pp.npix;
-                        }
-                    }
-                    if (b == 0 && light_entry) {
-                        pp.lentry = s->lentry.p; pp.lbox = s->lbox.p;
-                        if ((size_t)pp.j0 + pp.npix > s->lentry_done) {
-                            TIMED(RGK_K_OTHER, rgk_launch_light_entry_points(st, s->dev, cam, pp, (uint32_t)P, s->trange.p, s->lentry.p, s->lbox.p));
-                            s->lentry_done = (size_t)pp.j0 + pp.npix;
-                            if (s->tune.debug_bvh) { // how many pixel groups got light-side entry nodes below the root
-                                const size_t g0 = pp.j0 >> RGK_ENTRY_SHIFT, g1 = ((size_t)pp.j0 + pp.npix + RGK_ENTRY_PIX - 1) >> RGK_ENTRY_SHIFT;
-                                std::vector<int> he((g1 - g0) * RGK_ENTRY_K);
-                                HIPCHK(hipStreamSynchronize(st));
-                                HIPCHK(hipMemcpy(he.data(), s->lentry.p + g0 * RGK_ENTRY_K, he.size() * sizeof(int), hipMemcpyDeviceToHost));
-                                size_t below = 0, total_e = 0;
-                                for (size_t g = 0; g < g1 - g0; g++) { if (he[g * RGK_ENTRY_K] != 0) below++; for (int k = 0; k < RGK_ENTRY_K; k++) total_e += he[g * RGK_ENTRY_K + k] != 0x7fffffff; }
-                                std::fprintf(stderr, "[rgk] light-side entry nodes: %zu of %zu pixel groups start below the root, %.2f entries per group\n", below, g1 - g0, (double)total_e / (double)(g1 - g0));
-                            }
-                        }
-                    }
-                    TIMED(b == 0 ? RGK_K_SHADE_FIRST : RGK_K_SHADE, rgk_launch_shade(st, s->dev, cam, pp, b, w_rayA[q], w_rayB[q], w_hit, w_thr, w_tot,
-                                              w_rayA[q ^ 1], w_rayB[q ^ 1], w_shA, w_shB, w_shC, cn, R > 0));
-                    if (R > 0) TIMED(RGK_K_CONNECT, rgk_launch_connect(st, s->dev, pp, b, s->jobs.p, s->rads.p, cn));
-                    if (b == 0 && light_entry)
-                        TIMED(RGK_K_SHADOW_FIRST, rgk_launch_trace_shadow_first(st, s->dev, pp, tcl, count_stats, w_shA, w_shB, w_shC, w_tot,
-                                                               cn + RGK_CNT_SHADOW + b, cn + RGK_CNT_FETCH_S + b, s->stats.p));
-                    else
-                        TIMED(RGK_K_SHADOW, rgk_launch_trace_shadow(st, s->dev, tcl, count_stats, w_shA, w_shB, w_shC, w_tot, nullptr,
-                                                         RGK_SHADOW_ADD, nullptr, cn + RGK_CNT_SHADOW + b, cn + RGK_CNT_FETCH_S + b, s->stats.p));
-                    if (R > 0) // (after the plain rays: both add into the slot sums, a slot has a vertex in ONE of the two queues)
-                        TIMED(RGK_K_SHADOW_JOBS, rgk_launch_trace_shadow_jobs(st, s->dev, pp, tcl, count_stats, s->jobs.p, s->rads.p, w_tot,
-                                                              cn + RGK_CNT_CONN + b, cn + RGK_CNT_FETCH_J + b, s->stats.p));
-                    if ((rc = stage_mark(stage_target + b + 1))) return rc;
-                    if (track && b >= 3 && (b & 1) && b + 1 < prm->depth && (rc = queue_len(cn + RGK_CNT_QUEUE + b + 1, ub))) return rc;
-                }
-            }
-            TIMED(RGK_K_RESOLVE, rgk_launch_resolve(st, pp, w_tot, s->pixsum.p, d_accum_rgb, d_accum_count));
-            stage_target += std::max(1u, prm->depth);
-            if ((rc = stage_mark(stage_target))) return rc;
-            HIPCHK(hipMemcpyAsync(s->h_counters + (size_t)lane * 2 * RGK_CNT_TOTAL, cn, 2 * RGK_CNT_TOTAL * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-            pending[lane] = true;
-            if (!two && (rc = harvest(lane))) return rc;
+            if ((rc = queue_pass(s, kl, cam, pp, P, light_entry, d_accum_rgb, d_accum_count, stage))) return rc;
+            HIPCHK(hipStreamSynchronize(s->stream));
+            add_pass_counters(s->h_counters, pp, light_entry, tot);
         }
     }
-    for (int l = 0; l < 2; l++) if (pending[l] && (rc = harvest(l))) return rc;
     HIPCHK(hipGetLastError());
     s->prog_rounds++;
     if (counters) {
-        counters->paths = (uint64_t)P * prm->multisample;
-        counters->path_rays = path_rays;
-        counters->shadow_rays = shadow_rays;
-        if (count_stats) {
+        tot.paths = (uint64_t)P * prm->multisample;
+        if (kl.count_stats) {
             unsigned long long h[8];
             HIPCHK(hipMemcpy(h, s->stats.p, sizeof(h), hipMemcpyDeviceToHost));
-            counters->node_visits = h[0]; counters->tri_tests = h[1]; counters->shadow_node_visits = h[2]; counters->shadow_tri_tests = h[3];
+            tot.node_visits = h[0]; tot.tri_tests = h[1]; tot.shadow_node_visits = h[2]; tot.shadow_tri_tests = h[3];
         }
-        for (auto& e : evs) {
-            float ms = 0.f;
-            HIPCHK(hipEventElapsedTime(&ms, e.a, e.b));
-            rgk_kernel_stat& ks = counters->kernel[e.cls];
-            ks.ms += ms; ks.launches++;
-            const int k = e.cls;
-            if (k == RGK_K_TRACE_CAMERA || k == RGK_K_TRACE_CLOSEST || k == RGK_K_LIGHT_TRACE) { counters->ms_trace += ms; counters->n_trace_launches++; }
-            else if (k == RGK_K_SHADOW_FIRST || k == RGK_K_SHADOW || k == RGK_K_SHADOW_JOBS || k == RGK_K_LIGHT_SPLAT) { counters->ms_shadow += ms; counters->n_shadow_launches++; }
-            else if (k == RGK_K_SHADE_FIRST || k == RGK_K_SHADE || k == RGK_K_CONNECT || k == RGK_K_LIGHT_SHADE) { counters->ms_shade += ms; counters->n_shade_launches++; }
-            else counters->ms_other += ms;
-        }
-        for (int k = 0; k < RGK_K_COUNT; k++) counters->kernel[k].units = units[k];
-        {   // per-kernel traversal counters: differences between consecutive read-backs
-            std::array<unsigned long long, 4> prev{};
-            for (auto& sn : snaps) {
-                rgk_kernel_stat& ks = counters->kernel[sn.first];
-                const bool shadow = !(sn.first == RGK_K_TRACE_CAMERA || sn.first == RGK_K_TRACE_CLOSEST || sn.first == RGK_K_LIGHT_TRACE);
-                ks.node_visits += sn.second[shadow ? 2 : 0] - prev[shadow ? 2 : 0];
-                ks.tri_tests += sn.second[shadow ? 3 : 1] - prev[shadow ? 3 : 1];
-                prev = sn.second;
-            }
-        }
+        if ((rc = kl.fold(tot))) return rc;
+        *counters = tot;
     }
     return RGK_OK;
-#undef TIMED
 }
 
 int rgk_render_round(rgk_scene* s, const rgk_camera* camera, const rgk_params* prm, const rgk_tile* tiles, uint32_t n_tiles,
@@ -1856,13 +1843,11 @@ int rgk_bxdf_value(rgk_scene* s, uint32_t n, uint32_t route, const uint32_t* mat
     HIPCHK(hipSetDevice(s->device));
     DevBuf<uint32_t> dm; DevBuf<float> dvi, dvr, duv, dout;
     int rc;
-    if (!(rc = up(dm, mat, n)) && !(rc = up(dvi, Vi, (size_t)3 * n)) && !(rc = up(dvr, Vr, (size_t)3 * n)) && !(rc = up(duv, uv, (size_t)2 * n)) && !(rc = dout.alloc((size_t)3 * n))) {
-        rgk_launch_bxdf_value(s->stream, s->dev, n, route, dm.p, dvi.p, dvr.p, duv.p, dout.p);
-        if (hipStreamSynchronize(s->stream) != hipSuccess) rc = fail(RGK_ERR_DEVICE, "bxdf value kernel failed");
-        else rc = down(out_rgb, dout, (size_t)3 * n);
-    }
-    dm.release(); dvi.release(); dvr.release(); duv.release(); dout.release();
-    return rc;
+    if ((rc = dm.upload(mat, n)) || (rc = dvi.upload(Vi, (size_t)3 * n)) || (rc = dvr.upload(Vr, (size_t)3 * n)) || (rc = duv.upload(uv, (size_t)2 * n)) || (rc = dout.alloc((size_t)3 * n)))
+        return rc;
+    rgk_launch_bxdf_value(s->stream, s->dev, n, route, dm.p, dvi.p, dvr.p, duv.p, dout.p);
+    if (hipStreamSynchronize(s->stream) != hipSuccess) return fail(RGK_ERR_DEVICE, "bxdf value kernel failed");
+    return down(out_rgb, dout, (size_t)3 * n);
 }
 
 int rgk_bxdf_sample(rgk_scene* s, uint32_t n, uint32_t route, const uint32_t* mat, const float* Vi, const float* uv, const float* u, float* out_dir,
@@ -1873,14 +1858,13 @@ int rgk_bxdf_sample(rgk_scene* s, uint32_t n, uint32_t route, const uint32_t* ma
     HIPCHK(hipSetDevice(s->device));
     DevBuf<uint32_t> dm; DevBuf<float> dvi, duv, du, dd, dw; DevBuf<uint8_t> dl;
     int rc;
-    if (!(rc = up(dm, mat, n)) && !(rc = up(dvi, Vi, (size_t)3 * n)) && !(rc = up(duv, uv, (size_t)2 * n)) && !(rc = up(du, u, (size_t)2 * n)) &&
-        !(rc = dd.alloc((size_t)3 * n)) && !(rc = dw.alloc((size_t)3 * n)) && !(rc = dl.alloc(n))) {
-        rgk_launch_bxdf_sample(s->stream, s->dev, n, route, dm.p, dvi.p, duv.p, du.p, dd.p, dw.p, dl.p);
-        if (hipStreamSynchronize(s->stream) != hipSuccess) rc = fail(RGK_ERR_DEVICE, "bxdf sample kernel failed");
-        else if (!(rc = down(out_dir, dd, (size_t)3 * n)) && !(rc = down(out_weight, dw, (size_t)3 * n))) rc = down(may_leak, dl, n);
-    }
-    dm.release(); dvi.release(); duv.release(); du.release(); dd.release(); dw.release(); dl.release();
-    return rc;
+    if ((rc = dm.upload(mat, n)) || (rc = dvi.upload(Vi, (size_t)3 * n)) || (rc = duv.upload(uv, (size_t)2 * n)) || (rc = du.upload(u, (size_t)2 * n)) ||
+        (rc = dd.alloc((size_t)3 * n)) || (rc = dw.alloc((size_t)3 * n)) || (rc = dl.alloc(n)))
+        return rc;
+    rgk_launch_bxdf_sample(s->stream, s->dev, n, route, dm.p, dvi.p, duv.p, du.p, dd.p, dw.p, dl.p);
+    if (hipStreamSynchronize(s->stream) != hipSuccess) return fail(RGK_ERR_DEVICE, "bxdf sample kernel failed");
+    if ((rc = down(out_dir, dd, (size_t)3 * n)) || (rc = down(out_weight, dw, (size_t)3 * n))) return rc;
+    return down(may_leak, dl, n);
 }
 
 int rgk_texture_sample(rgk_scene* s, uint32_t n, const int32_t* tex, const float* uv, float* rgb, float* slope_right, float* slope_bottom) {
@@ -1890,13 +1874,11 @@ int rgk_texture_sample(rgk_scene* s, uint32_t n, const int32_t* tex, const float
     HIPCHK(hipSetDevice(s->device));
     DevBuf<int32_t> dt; DevBuf<float> duv, drgb, dr, db;
     int rc;
-    if (!(rc = up(dt, tex, n)) && !(rc = up(duv, uv, (size_t)2 * n)) && !(rc = drgb.alloc((size_t)3 * n)) && !(rc = dr.alloc(n)) && !(rc = db.alloc(n))) {
-        rgk_launch_texture_sample(s->stream, s->dev, n, s->texrefs.p, dt.p, duv.p, drgb.p, dr.p, db.p);
-        if (hipStreamSynchronize(s->stream) != hipSuccess) rc = fail(RGK_ERR_DEVICE, "texture sample kernel failed");
-        else if (!(rc = down(rgb, drgb, (size_t)3 * n)) && !(rc = down(slope_right, dr, n))) rc = down(slope_bottom, db, n);
-    }
-    dt.release(); duv.release(); drgb.release(); dr.release(); db.release();
-    return rc;
+    if ((rc = dt.upload(tex, n)) || (rc = duv.upload(uv, (size_t)2 * n)) || (rc = drgb.alloc((size_t)3 * n)) || (rc = dr.alloc(n)) || (rc = db.alloc(n))) return rc;
+    rgk_launch_texture_sample(s->stream, s->dev, n, s->texrefs.p, dt.p, duv.p, drgb.p, dr.p, db.p);
+    if (hipStreamSynchronize(s->stream) != hipSuccess) return fail(RGK_ERR_DEVICE, "texture sample kernel failed");
+    if ((rc = down(rgb, drgb, (size_t)3 * n)) || (rc = down(slope_right, dr, n))) return rc;
+    return down(slope_bottom, db, n);
 }
 
 int rgk_libm_eval(int fn, uint32_t n, const float* a, const float* b, float* out) {
@@ -1907,12 +1889,9 @@ int rgk_libm_eval(int fn, uint32_t n, const float* a, const float* b, float* out
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(RGK_ERR_NO_DEVICE, "no HIP device visible");
     DevBuf<float> da, db, dout;
     int rc;
-    if (!(rc = up(da, a, n)) && !(rc = up(db, b ? b : a, n)) && !(rc = dout.alloc(n))) {
-        rgk_launch_libm_eval(nullptr, fn, n, da.p, db.p, dout.p);
-        rc = down(out, dout, n);
-    }
-    da.release(); db.release(); dout.release();
-    return rc;
+    if ((rc = da.upload(a, n)) || (rc = db.upload(b ? b : a, n)) || (rc = dout.alloc(n))) return rc;
+    rgk_launch_libm_eval(nullptr, fn, n, da.p, db.p, dout.p);
+    return down(out, dout, n);
 }
 
 int rgk_sampler_eval(uint32_t n, const uint32_t* seed, const uint32_t* index, const uint32_t* dim, int is2d, float* out) {
@@ -1927,18 +1906,16 @@ int rgk_sampler_eval(uint32_t n, const uint32_t* seed, const uint32_t* index, co
     DevBuf<uint16_t> dp;
     DevBuf<uint32_t> ds_, di, dd;
     DevBuf<float> dout;
-    int rc = RGK_OK;
-    std::vector<uint32_t> vs(seed, seed + n), vi(index, index + n), vd(dim, dim + n);
-    if (!(rc = dh.upload(hd)) && !(rc = dp.upload(hp)) && !(rc = ds_.upload(vs)) && !(rc = di.upload(vi)) && !(rc = dd.upload(vd)) &&
-        !(rc = dout.alloc((size_t)2 * n))) {
-        DevScene sc{};
-        sc.hdims = dh.p; sc.hperm = dp.p;
-        rgk_launch_sampler_eval(nullptr, sc, n, ds_.p, di.p, dd.p, is2d, dout.p);
-        hipError_t e = hipMemcpy(out, dout.p, (size_t)2 * n * sizeof(float), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = fail(RGK_ERR_DEVICE, "sampler eval: %s", hipGetErrorString(e));
-    }
-    dh.release(); dp.release(); ds_.release(); di.release(); dd.release(); dout.release();
-    return rc;
+    int rc;
+    if ((rc = dh.upload(hd.data(), hd.size())) || (rc = dp.upload(hp.data(), hp.size())) || (rc = ds_.upload(seed, n)) || (rc = di.upload(index, n)) ||
+        (rc = dd.upload(dim, n)) || (rc = dout.alloc((size_t)2 * n)))
+        return rc;
+    DevScene sc{};
+    sc.hdims = dh.p; sc.hperm = dp.p;
+    rgk_launch_sampler_eval(nullptr, sc, n, ds_.p, di.p, dd.p, is2d, dout.p);
+    hipError_t e = hipMemcpy(out, dout.p, (size_t)2 * n * sizeof(float), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(RGK_ERR_DEVICE, "sampler eval: %s", hipGetErrorString(e));
+    return RGK_OK;
 }
 
 } // extern "C"

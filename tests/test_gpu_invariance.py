@@ -5,7 +5,7 @@ baseline is compared once with the oracle, so the matrix is tied to the referenc
 
 The batch sizes are picked from rgk_render_round's sizing loop so that the pass plans hit the edges: pixel ranges that need
 several sample passes (an odd number of them too), pixel ranges that are no multiple of the 8-pixel entry group
-(RGK_ENTRY_PIX), and both again with the two halves of the pixel list on two streams (tuning "two_lanes")."""
+(RGK_ENTRY_PIX), and several pixel ranges that each need several sample passes."""
 import math
 import os
 
@@ -63,12 +63,11 @@ def against_oracle(oracle, wl, prm, tiles, acc, cnt, n_tiles, name, rel_max=1e-3
 
 
 # ----------------------------------------------------------------------- pass plans
-# Cornell 512 x 512 x 16 (P = 262 144 pixels, P * spp = 2^22: just enough for two lanes).  Pass plans with two lanes on:
-#   2 097 152: 2 pixel ranges x 2 sample passes (8 spp each)
-#   1 572 864: 2 ranges x 3 sample passes (6, 6, 4 spp): an odd count, so consecutive passes alternate between the lanes
-#     524 288: 2 ranges x 8 sample passes
-#     200 006: a lane's 100 003 paths are no whole number of 1024-pixel blocks (nor of 8-pixel entry groups)
-# and with one lane the same batches give ranges of the whole list (or of 200 006 pixels) split over samples.
+# Cornell 512 x 512 x 16 (P = 262 144 pixels).  Pass plans:
+#   2 097 152: the whole list x 2 sample passes (8 spp each)
+#   1 572 864: the whole list x 3 sample passes (6, 6, 4 spp): an odd count
+#     524 288: the whole list x 8 sample passes (2 spp each)
+#     200 006: 2 pixel ranges (the first no multiple of the 8-pixel entry group) x 16 single-sample passes
 CORNELL_BATCHES = (2097152, 1572864, 524288, 200006)
 
 
@@ -82,8 +81,8 @@ def test_pass_plans_do_not_change_the_image_cornell(rd, oracle):
     assert (base[0][1] == 16).all()
     assert_same_bits(base[0], base[1], "baseline: second round of the frame")
     against_oracle(oracle, wl, prm, tiles, base[0][0], base[0][1], 64, "test_pass_plans_do_not_change_the_image_cornell:baseline-vs-oracle")
-    variants = [dict(two_lanes=lanes, batch_paths=b) for lanes in (1, 0) for b in CORNELL_BATCHES]
-    variants += [dict(two_lanes=1, batch_paths=1572864, sample_group=grp) for grp in (0, 6)]   # k_resolve / k_resolve_tiled under two lanes
+    variants = [dict(batch_paths=b) for b in CORNELL_BATCHES]
+    variants += [dict(batch_paths=1572864, sample_group=grp) for grp in (0, 6)]   # k_resolve / k_resolve_tiled
     for tv in variants:
         for r, got in enumerate(render_fresh(rd, wl, prm, tiles, rounds=2, **tv)):
             assert_same_bits(base[r], got, (tv, "round", r))
@@ -92,7 +91,7 @@ def test_pass_plans_do_not_change_the_image_cornell(rd, oracle):
 
 def test_pass_plans_do_not_change_the_image_sponza(rd, oracle):
     """Point light, all per-frame lists on (camera entry nodes, their caps from the frame's second round on, light-side entry
-    nodes and their boxes): two lanes or one, sample passes split or pixel ranges that straddle entry groups, and every camera
+    nodes and their boxes): sample passes split or pixel ranges that straddle entry groups, and every camera
     walker (beam 0: per ray, 1: bundles while uncapped, 2: bundles against capped lists too)."""
     from rgk_amd.workloads import Workload
     wl = Workload("sponza-1080p", scale=0.5, spp=16)
@@ -103,15 +102,14 @@ def test_pass_plans_do_not_change_the_image_sponza(rd, oracle):
     assert_same_bits(base[0], base[1], "baseline: second round of the frame")
     against_oracle(oracle, wl, prm, tiles, base[0][0], base[0][1], 64, "test_pass_plans_do_not_change_the_image_sponza:baseline-vs-oracle")
     n = 0
-    for lanes in (0, 1):
-        # 2 097 152: 4 sample passes of 4 spp (two lanes: 2 ranges); 200 006: single-sample passes over ranges of 200 006 or
-        # (two lanes) about 100 000 pixels -- no multiple of 8 unless the plan rounds it
-        for batch in (2097152, 200006):
-            for beam in (0, 1, 2):
-                tv = dict(two_lanes=lanes, batch_paths=batch, beam=beam, entry_points=1, entry_cap=1, light_entry=1)
-                for r, got in enumerate(render_fresh(rd, wl, prm, tiles, rounds=2, **tv)):
-                    assert_same_bits(base[r], got, (tv, "round", r))
-                n += 1
+    # 2 097 152: the whole list x 4 sample passes of 4 spp; 200 006: 3 pixel ranges (200 006 pixels: no multiple of 8) x 16
+    # single-sample passes
+    for batch in (2097152, 200006):
+        for beam in (0, 1, 2):
+            tv = dict(batch_paths=batch, beam=beam, entry_points=1, entry_cap=1, light_entry=1)
+            for r, got in enumerate(render_fresh(rd, wl, prm, tiles, rounds=2, **tv)):
+                assert_same_bits(base[r], got, (tv, "round", r))
+            n += 1
     record_parity("test_pass_plans_do_not_change_the_image_sponza", variants=n, size="960x540x16", bit_identical=1.0)
 
 
@@ -126,7 +124,7 @@ def test_deep_paths_small_batches(rd, oracle):
     assert (base[1] == 32).all()
     against_oracle(oracle, wl, prm, tiles, base[0], base[1], 32, "test_deep_paths_small_batches:baseline-vs-oracle")
     # 50 000 paths: ranges of 50 000 pixels (no multiple of 8), 32 single-sample passes each; 300 000: 8 sample passes of 4
-    for tv in (dict(batch_paths=50000), dict(batch_paths=300000), dict(batch_paths=50000, two_lanes=1)):
+    for tv in (dict(batch_paths=50000), dict(batch_paths=300000)):
         assert_same_bits(base, render_fresh(rd, wl, prm, tiles, **tv)[0], tv)
 
 
