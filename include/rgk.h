@@ -251,6 +251,8 @@ typedef struct rgk_scene_info {
     uint32_t n_leaf_refs;
     uint32_t n_float_textures;      /* RGK_TEX_RGB32F textures handed over ...                                          */
     uint32_t n_palettized_textures; /* ... and how many of them are stored as bytes + value table (<= 256 distinct values) */
+    uint32_t const_light; /* 1: the scene's only light is ONE point light of size 0 that every path provably picks, so unidirectional
+                           * rounds take it as a launch constant (see rgk_scene_set_tuning "const_light"); 0: the per-path pick */
 } rgk_scene_info;
 
 typedef struct rgk_hit {
@@ -294,8 +296,15 @@ int rgk_scene_get_progress(const rgk_scene *scene, rgk_progress *out);
 /* Tuning switches of ONE scene; none of them changes a result (the tests render with each and compare bits).  Keys:
  * "entry_points", "entry_cap", "light_entry" (0 / 1: where camera rays and first shadow rays start their walk), "sample_group"
  * (log2 of the samples of a pixel that sit side by side in the path-slot order, 0..6; -1: default), "batch_paths" (paths per
- * pass; 0: sized from the free memory), "workspace_gb" (0: default), "beam" (0 / 1: camera rays of a pixel walk the tree together).  Their initial values are read from the environment
- * (RGK_ENTRY_POINTS, RGK_ENTRY_CAP, RGK_LIGHT_ENTRY, RGK_SAMPLE_GROUP, RGK_BATCH_PATHS, RGK_WORKSPACE_GB) ONCE, in
+ * pass; 0: sized from the free memory), "workspace_gb" (0: default), "beam" (0 / 1: camera rays of a pixel walk the tree together),
+ * "const_light" (0 / 1, default 1: in a scene that reports rgk_scene_info.const_light == 1, unidirectional rounds (reverse == 0)
+ * do not sample, store and re-read "the path's light" per path -- it is the same {position, light 0} for every path -- but take
+ * position, colour and intensity as launch constants, and their shadow rays are queued without the origin and near distance all
+ * of them share; 0: the per-path route.  The scene qualifies when it has exactly one point light and no emitting triangle, the
+ * light's size is 0, no component of its position is -0.0 (pos + 0 * v must give back pos bit for bit), and GetRandomLight's
+ * own two float comparisons, evaluated with its own expressions for the largest number the sampler returns, 1 - 2^-24, select
+ * light 0: rounding is monotone, so every smaller sample selects it too.  Same bits either way).  Their initial values are read from the environment
+ * (RGK_ENTRY_POINTS, RGK_ENTRY_CAP, RGK_LIGHT_ENTRY, RGK_CONST_LIGHT, RGK_SAMPLE_GROUP, RGK_BATCH_PATHS, RGK_WORKSPACE_GB) ONCE, in
  * rgk_scene_create; a round never reads the environment.  Not while a round is in flight on this scene. */
 int rgk_scene_set_tuning(rgk_scene *scene, const char *key, double value);
 

@@ -111,7 +111,8 @@ class SceneInfo(C.Structure):
                 ("total_areal_power", C.c_float), ("total_point_power", C.c_float),
                 ("n_nodes", C.c_uint32), ("node_bytes", C.c_uint32), ("tri_bytes", C.c_uint32),
                 ("max_depth", C.c_uint32), ("n_leaf_refs", C.c_uint32),
-                ("n_float_textures", C.c_uint32), ("n_palettized_textures", C.c_uint32)]
+                ("n_float_textures", C.c_uint32), ("n_palettized_textures", C.c_uint32),
+                ("const_light", C.c_uint32)]
 
 
 class Progress(C.Structure):

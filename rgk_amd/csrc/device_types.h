@@ -139,6 +139,9 @@ struct DevScene {
     const uint16_t* hperm;
     uint32_t n_pointlights, n_areal;
     float total_point_power, total_areal_power;
+    // the constant-light route (rgk.h rgk_scene_info::const_light): pointlights[0] as kernel arguments -- wave-uniform, in SGPRs --
+    // for the launches that take every path's light from here instead of picking, storing and re-reading it per path
+    float cl_pos[3], cl_intensity, cl_color[3];
     float epsilon;
     float bb_min[3], bb_max[3];
     uint32_t has_texcoords;

@@ -809,6 +809,17 @@ __device__ __forceinline__ DLight light_from_code(const DevScene& sc, f3 pos, ui
     L.intensity = pl->intensity; L.size = pl->size;
     return L;
 }
+// What light_from_code(sc, pointlights[0].pos, 0) returns in a scene on the constant-light route (size == 0 is part of its
+// eligibility), from the kernel arguments instead of a load through a per-lane code.
+__device__ __forceinline__ DLight light_constant(const DevScene& sc) {
+    DLight L;
+    L.pos = mk3(sc.cl_pos[0], sc.cl_pos[1], sc.cl_pos[2]);
+    L.color = mk3(sc.cl_color[0], sc.cl_color[1], sc.cl_color[2]);
+    L.normal = mk3(0.f, 0.f, 0.f);
+    L.intensity = sc.cl_intensity; L.size = 0.f; L.index = 0;
+    L.type = 0;
+    return L;
+}
 // Scene::GetSkyboxRay, reference src/scene.cpp:748-763
 __device__ __forceinline__ f3 skybox(const DevScene& sc, f3 direction) {
     if (sc.sky_mode == 0) return mk3(sc.sky_color[0], sc.sky_color[1], sc.sky_color[2]) * mk3(sc.sky_intensity, sc.sky_intensity, sc.sky_intensity);

@@ -487,13 +487,14 @@ struct DevBuf {
 extern "C" __attribute__((visibility("hidden"))) int rgk_internal_fail(int code, const char* msg) { return fail(code, "%s", msg); }
 
 // Tuning switches of one scene (nothing here changes a result).  Filled ONCE, in rgk_scene_create, from the environment
-// (RGK_ENTRY_POINTS, RGK_ENTRY_CAP, RGK_LIGHT_ENTRY, RGK_SAMPLE_GROUP, RGK_BATCH_PATHS, RGK_WORKSPACE_GB, RGK_DEBUG_BVH,
+// (RGK_ENTRY_POINTS, RGK_ENTRY_CAP, RGK_LIGHT_ENTRY, RGK_CONST_LIGHT, RGK_SAMPLE_GROUP, RGK_BATCH_PATHS, RGK_WORKSPACE_GB, RGK_DEBUG_BVH,
 // RGK_DEBUG_UTIL); afterwards only rgk_scene_set_tuning changes them -- a round never reads the environment (round 2 did, per
 // round: process-global state under a host that may render from two threads).
 struct RgkTuning {
     bool entry_points = true; // camera rays start at their pixel group's entry nodes (k_entry_points)
     bool entry_cap = true;    // ... capped behind the group's first hits from a frame's second round on
     bool light_entry = true;  // first-vertex shadow rays of a single-light scene start at light-side entry nodes
+    bool const_light = true;  // eligible scenes (rgk_scene_info::const_light): unidirectional rounds take the light as a launch constant
     int sample_group = -1;    // log2 of the samples of a pixel side by side in the slot order; -1: the compiled default
     size_t batch_paths = 0;   // paths per pass; 0: sized from the memory that is free
     double workspace_gb = 0;  // ... or from this many GB; 0: 96 (160 for bidirectional rounds), at most 60 % of what is free
@@ -501,6 +502,31 @@ struct RgkTuning {
                               // entry lists are uncapped (a frame's first round), 2: always, 0: never
     bool debug_bvh = false, debug_util = false;
 };
+
+// The constant-light route's eligibility (rgk.h rgk_scene_info::const_light): does random_light (rgk_device.h) return point
+// light 0, at its own position, for EVERY sample?  One point light of size 0 and no areal light; no -0.0 in the position
+// (light_code's pos + 0 * v would make it +0.0 for some v); and random_light's own two comparisons, in float with its own
+// expressions, select light 0 for the largest `choice.x` the sampler returns, 1 - 2^-24.  Rounding is monotone: choice.x *
+// total_power does not grow when choice.x shrinks, nor does q - intensity * 4 pi when q shrinks, so every smaller sample passes
+// both comparisons too.  (A NaN or infinite power fails them and stays on the per-path route.)
+static uint32_t const_light_eligible(const DevScene& ds, const DevPointLight* pls) {
+    if (ds.n_pointlights != 1 || ds.n_areal != 0) return 0;
+    const DevPointLight& pl = pls[0];
+    if (pl.size != 0.0f) return 0;
+    for (int k = 0; k < 3; k++)
+        if (pl.pos[k] == 0.0f && std::signbit(pl.pos[k])) return 0;
+    const float PI_F = 3.14159265358979323846264338327950288f; // RGK_PI_F
+    volatile float total_power = ds.total_point_power + ds.total_areal_power; // (volatile: each step rounded to float, as on the device)
+    if (total_power <= 0.0f) return 0;
+    const float choice_max = 0x1.fffffep-1f;
+    volatile float q = choice_max * total_power;
+    if (!(q < ds.total_point_power)) return 0;
+    volatile float step = pl.intensity * 4.0f;
+    step = step * PI_F;
+    q = q - step;
+    if (!(q <= 0.0f)) return 0;
+    return 1;
+}
 
 struct rgk_scene {
     int device = 0;
@@ -519,6 +545,7 @@ struct rgk_scene {
     DevBuf<uint32_t> texels8;
     DevBuf<float> luts;
     DevBuf<DevPointLight> pointlights;
+    DevPointLight h_light0{}; // pointlights[0] (const_light_eligible after a refit)
     DevBuf<DevArealLight> areal;
     DevBuf<DevArealTri> areal_tris;
     DevBuf<float4> ltc;
@@ -830,6 +857,7 @@ int rgk_scene_create(const rgk_scene_desc* d, int device, rgk_scene** out) {
         auto off = [](const char* name) { const char* e = std::getenv(name); return e && e[0] == '0'; };
         RgkTuning& t = s->tune;
         t.entry_points = !off("RGK_ENTRY_POINTS"); t.entry_cap = !off("RGK_ENTRY_CAP"); t.light_entry = !off("RGK_LIGHT_ENTRY");
+        t.const_light = !off("RGK_CONST_LIGHT");
         if (const char* e = std::getenv("RGK_SAMPLE_GROUP")) t.sample_group = std::min(6, std::max(0, std::atoi(e)));
         if (const char* e = std::getenv("RGK_BATCH_PATHS")) t.batch_paths = std::max<size_t>(1024, strtoull(e, nullptr, 10));
         if (const char* e = std::getenv("RGK_WORKSPACE_GB")) t.workspace_gb = atof(e);
@@ -1191,6 +1219,11 @@ int rgk_scene_create(const rgk_scene_desc* d, int device, rgk_scene** out) {
     ds.ltc = s->ltc.p; ds.hdims = s->hdims.p; ds.hperm = s->hperm.p;
     ds.n_pointlights = (uint32_t)pls.size(); ds.n_areal = (uint32_t)als.size();
     ds.total_point_power = total_point; ds.total_areal_power = total_areal;
+    if (!pls.empty()) {
+        s->h_light0 = pls[0];
+        for (int k = 0; k < 3; k++) { ds.cl_pos[k] = pls[0].pos[k]; ds.cl_color[k] = pls[0].color[k]; }
+        ds.cl_intensity = pls[0].intensity;
+    }
     ds.has_texcoords = d->texcoords ? 1u : 0u;
     ds.sky_mode = d->sky_mode;
     for (int k = 0; k < 3; k++) ds.sky_color[k] = d->sky_color[k];
@@ -1206,6 +1239,7 @@ int rgk_scene_create(const rgk_scene_desc* d, int device, rgk_scene** out) {
     inf.n_nodes = n_nodes; inf.node_bytes = RGK_NODE_BYTES; inf.tri_bytes = RGK_TRI_BYTES;
     inf.max_depth = max_depth; inf.n_leaf_refs = n_refs;
     inf.n_float_textures = n_float_tex; inf.n_palettized_textures = n_palettized;
+    inf.const_light = const_light_eligible(ds, &s->h_light0);
     guard.s = nullptr;
     *out = s;
     return RGK_OK;
@@ -1251,6 +1285,7 @@ int rgk_scene_refit(rgk_scene* s, const float* vertices, const float* normals, c
     for (int a = 0; a < 3; a++) { ds.bb_min[a] = mn[a] - eps; ds.bb_max[a] = mx[a] + eps; }
     if (hipMemcpy(s->self.p, &ds, sizeof(DevScene), hipMemcpyHostToDevice) != hipSuccess) return fail(RGK_ERR_DEVICE, "hipMemcpy(DevScene)");
     s->info.epsilon = eps; s->info.total_areal_power = total_areal;
+    s->info.const_light = const_light_eligible(ds, &s->h_light0);
     for (int a = 0; a < 3; a++) { s->info.bbox_min[a] = ds.bb_min[a]; s->info.bbox_max[a] = ds.bb_max[a]; }
     s->entry_key = 0; s->entry_n = 0; s->entry_capped = 0; s->lentry_done = 0; // per-frame lists were made for the old boxes
     return RGK_OK;
@@ -1280,6 +1315,7 @@ int rgk_scene_set_tuning(rgk_scene* s, const char* key, double value) {
     if (k == "entry_points") t.entry_points = value != 0;
     else if (k == "entry_cap") t.entry_cap = value != 0;
     else if (k == "light_entry") t.light_entry = value != 0;
+    else if (k == "const_light") t.const_light = value != 0;
     else if (k == "sample_group") t.sample_group = value < 0 ? -1 : (int)std::min(6.0, value);
     else if (k == "batch_paths") t.batch_paths = value <= 0 ? 0 : std::max<size_t>(1024, (size_t)value);
     else if (k == "workspace_gb") t.workspace_gb = value <= 0 ? 0.0 : value;
@@ -1581,7 +1617,7 @@ int queue_first_hit_lists(rgk_scene* s, KernelLog& kl, const DevCamera& cam, Pas
 // One pass, queued on the scene's stream: the light sub-path (reverse > 0), the camera path's bounces, the resolve into the
 // accumulator, a progress mark behind every bounce (`stage`: the round's stages before this pass), and the copy of the pass's
 // counter blocks into h_counters.
-int queue_pass(rgk_scene* s, KernelLog& kl, const DevCamera& cam, PassParams& pp, size_t P, bool light_entry, float* d_accum_rgb,
+int queue_pass(rgk_scene* s, KernelLog& kl, const DevCamera& cam, PassParams& pp, size_t P, bool light_entry, bool const_light, float* d_accum_rgb,
                uint32_t* d_accum_count, uint32_t stage) {
     hipStream_t st = s->stream;
     const RgkTraceCfg& tc = s->tcfg;
@@ -1633,10 +1669,15 @@ int queue_pass(rgk_scene* s, KernelLog& kl, const DevCamera& cam, PassParams& pp
         else
             rc = kl.run(RGK_K_TRACE_CLOSEST, [&] { rgk_launch_trace_closest(st, s->dev, tc, count_stats, rayA[q], rayB[q], nullptr, hit, cn + RGK_CNT_QUEUE + b, cn + RGK_CNT_FETCH_T + b, s->stats.p); });
         if (rc || (b == 0 && (rc = queue_first_hit_lists(s, kl, cam, pp, (uint32_t)P, cap_entries, light_entry)))) return rc;
-        if ((rc = kl.run(b == 0 ? RGK_K_SHADE_FIRST : RGK_K_SHADE, [&] { rgk_launch_shade(st, s->dev, cam, pp, b, rayA[q], rayB[q], hit, thr, tot, rayA[q ^ 1], rayB[q ^ 1], shA, shB, shC, cn, R > 0); })) ||
+        if ((rc = kl.run(b == 0 ? RGK_K_SHADE_FIRST : RGK_K_SHADE, [&] { rgk_launch_shade(st, s->dev, cam, pp, b, rayA[q], rayB[q], hit, thr, tot, rayA[q ^ 1], rayB[q ^ 1], shA, shB, shC, cn, R > 0, const_light); })) ||
             (R > 0 && (rc = kl.run(RGK_K_CONNECT, [&] { rgk_launch_connect(st, s->dev, pp, b, s->jobs.p, s->rads.p, cn); }))))
             return rc;
-        if (b == 0 && light_entry)
+        // (the constant-light route: the shading launches above left 32-byte records, shA = {d, far}, shB = {radiance, slot})
+        if (const_light && rgk_const_light_records() && b == 0 && light_entry)
+            rc = kl.run(RGK_K_SHADOW_FIRST, [&] { rgk_launch_trace_shadow_first_cl(st, s->dev, pp, tc, count_stats, shA, shB, tot, cn + RGK_CNT_SHADOW + b, cn + RGK_CNT_FETCH_S + b, s->stats.p); });
+        else if (const_light && rgk_const_light_records())
+            rc = kl.run(RGK_K_SHADOW, [&] { rgk_launch_trace_shadow_cl(st, s->dev, tc, count_stats, shA, shB, tot, cn + RGK_CNT_SHADOW + b, cn + RGK_CNT_FETCH_S + b, s->stats.p); });
+        else if (b == 0 && light_entry)
             rc = kl.run(RGK_K_SHADOW_FIRST, [&] { rgk_launch_trace_shadow_first(st, s->dev, pp, tc, count_stats, shA, shB, shC, tot, cn + RGK_CNT_SHADOW + b, cn + RGK_CNT_FETCH_S + b, s->stats.p); });
         else
             rc = kl.run(RGK_K_SHADOW, [&] { rgk_launch_trace_shadow(st, s->dev, tc, count_stats, shA, shB, shC, tot, nullptr, RGK_SHADOW_ADD, nullptr, cn + RGK_CNT_SHADOW + b, cn + RGK_CNT_FETCH_S + b, s->stats.p); });
@@ -1699,6 +1740,8 @@ int rgk_render_round_device(rgk_scene* s, const rgk_camera* camera, const rgk_pa
     pp.entry_cap = s->entry_cap.p;
     // one point / sphere light and nothing else that emits: every first-vertex shadow ray starts there (k_entry_points_light)
     const bool light_entry = s->entry.p && s->tune.light_entry && s->dev.n_pointlights == 1 && s->dev.n_areal == 0;
+    // ... and if that light is provably every path's light, at its own position, a unidirectional round takes it as a constant
+    const bool const_light = s->info.const_light == 1 && s->tune.const_light && R == 0;
     if (light_entry) {
         const size_t groups = ((size_t)P + RGK_ENTRY_PIX - 1) / RGK_ENTRY_PIX + 1;
         if ((rc = s->lentry.alloc(groups * RGK_ENTRY_K)) || (rc = s->trange.alloc(groups * 2)) || (rc = s->lbox.alloc(groups * 2))) return rc;
@@ -1715,7 +1758,7 @@ int rgk_render_round_device(rgk_scene* s, const rgk_camera* camera, const rgk_pa
         for (uint32_t s0 = 0; s0 < prm->multisample; s0 += ns_pass, stage += pass_stages) {
             pp.s0 = s0;
             pp.ns = std::min(ns_pass, prm->multisample - s0);
-            if ((rc = queue_pass(s, kl, cam, pp, P, light_entry, d_accum_rgb, d_accum_count, stage))) return rc;
+            if ((rc = queue_pass(s, kl, cam, pp, P, light_entry, const_light, d_accum_rgb, d_accum_count, stage))) return rc;
             HIPCHK(hipStreamSynchronize(s->stream));
             add_pass_counters(s->h_counters, pp, light_entry, tot);
         }

@@ -60,7 +60,7 @@ struct PassParams {
     const uint32_t* pix_xy;   // x | y << 16, per pixel of the round
     const uint32_t* pix_seed; // PathTracer::samplerSeed for that pixel (a2)
     const float* htab;        // halton_raw(hdim, s) for hdim < 192, s < multisample: htab[hdim * multisample + s]
-    float4* light;            // per slot: the path's light {pos.xyz, code}, written by the first vertex of a path that goes on
+    float4* light;            // per slot: the path's light {pos.xyz, code}, written by the first vertex of a path that goes on (not on the constant-light route)
     const float4* lbox;       // ... and the box {lo, hi} per group inside which a shadow ray must END to use them
     const int* lentry;        // first-vertex shadow rays of a single-light scene: entry nodes per pixel group (k_entry_points_light), or null
     const float* entry_cap;   // ... and per group the distance up to which that list is complete (+inf: all the way)
@@ -122,7 +122,14 @@ void rgk_launch_trace_shadow_jobs(hipStream_t st, const DevScene& sc, const Pass
                                   float4* tot, const uint32_t* count_ptr, uint32_t* fetch, unsigned long long* stats);
 void rgk_launch_shade(hipStream_t st, const DevScene& sc, const DevCamera& cam, const PassParams& pp, uint32_t bounce, const float4* rayA,
                       const float4* rayB, const float4* hit, float4* thr, float4* tot, float4* nextA, float4* nextB, float4* shA,
-                      float4* shB, float4* shC, uint32_t* counters, bool bdpt = false);
+                      float4* shB, float4* shC, uint32_t* counters, bool bdpt = false, bool const_light = false);
+// the constant-light route (rgk.h rgk_scene_info::const_light; never with bdpt): rgk_launch_shade(const_light = true) queues shadow
+// rays as shA = {d.xyz, far}, shB = {radiance.rgb, slot} when rgk_const_light_records() says so, and these two trace them
+bool rgk_const_light_records();
+void rgk_launch_trace_shadow_cl(hipStream_t st, const DevScene& sc, const RgkTraceCfg& tc, bool count_stats, const float4* shA, const float4* shB,
+                                float4* tot, const uint32_t* count_ptr, uint32_t* fetch, unsigned long long* stats);
+void rgk_launch_trace_shadow_first_cl(hipStream_t st, const DevScene& sc, const PassParams& pp, const RgkTraceCfg& tc, bool count_stats, const float4* shA, const float4* shB,
+                                      float4* tot, const uint32_t* count_ptr, uint32_t* fetch, unsigned long long* stats);
 void rgk_launch_resolve(hipStream_t st, const PassParams& pp, const float4* tot, float4* pixsum, float* accum_rgb, uint32_t* accum_count);
 void rgk_launch_pack_rays(hipStream_t st, uint32_t n, const float* rays, const int32_t* ignore, float4* rayA, float4* rayB, float2* nearfar);
 void rgk_launch_pack_visibility(hipStream_t st, const DevScene& sc, uint32_t n, const float* a, const float* b, float4* shA, float4* shB,

@@ -28,6 +28,9 @@
 #ifndef RGK_SKIP_DEAD_NEE
 #define RGK_SKIP_DEAD_NEE 1
 #endif
+#ifndef RGK_CL_REC32
+#define RGK_CL_REC32 1 // constant-light route: shadow rays queued as 32-byte records (0: the three-array records, for measuring the two parts apart)
+#endif
 
 // ------------------------------------------------------------------ K1: ray generation (camera_ray, camera_ray_of_slot: rgk_trace.h)
 // (Unidirectional rounds have no ray-generation kernel: bounce 0 derives the camera ray from the slot number in the traversal
@@ -46,7 +49,14 @@
 // (pp.conn[c * batch + i], i = its queue index, listed in pp.connlist) for k_connect (rgk_bdpt.h), which evaluates the
 // connections and queues the vertex for k_trace_shadow_jobs.  Most slots have no light vertex (a light far outside the
 // geometry: its first ray must hit the scene at all), and those vertices are shaded exactly like a unidirectional one.
-template <bool GENERIC, bool FIRST, bool BDPT = false>
+// CL = true: the constant-light route of a unidirectional round (rgk.h rgk_scene_info::const_light).  "The path's light" is the
+// same {pointlights[0].pos, code 0} for every path -- the host has checked that the pick below can have no other outcome -- so
+// it is neither picked (five sampler dimensions, the selection loop, sphere_uniform times size == 0) nor kept per slot nor
+// looked up through a per-lane code: position, colour and intensity come from the kernel arguments (sc.cl_*, SGPRs), the DLight
+// has the member values light_from_code would have filled in, and everything computed from it is computed as before.  The shadow
+// ray leaves as {d.xyz, far}{radiance.rgb, slot}: its origin and near distance are the same for every ray (k_trace_shadow<CL>).
+// Both launches of a pass, fast and GENERIC, take the same route: nobody writes pp.light on this one.
+template <bool GENERIC, bool FIRST, bool BDPT = false, bool CL = false>
 __global__ __launch_bounds__((FIRST ? RGK_SHADE_BLOCK : RGK_SHADE_BLOCK_LATER), RGK_SHADE_WAVES) void k_shade(const DevScene sc, const DevCamera cam, const PassParams pp, const uint32_t bounce,
                                                             const float4* __restrict__ rayA, const float4* __restrict__ rayB,
                                                             const float4* __restrict__ hit, float4* __restrict__ thr, float4* __restrict__ tot,
@@ -84,7 +94,7 @@ __global__ __launch_bounds__((FIRST ? RGK_SHADE_BLOCK : RGK_SHADE_BLOCK_LATER), 
                 o = mk3(a.x, a.y, a.z); d = mk3(a.w, b.x, b.y);
             }
             const float4 st = FIRST ? make_float4(1.f, 1.f, 1.f, __uint_as_float(1u << 16)) : thr[slot];
-            const float4 li_slot = FIRST ? make_float4(0.f, 0.f, 0.f, 0.f) : pp.light[slot]; // (asked for with the path state, not where it is first used: later vertices 21.75 -> 21.3 ms)
+            const float4 li_slot = (FIRST || CL) ? make_float4(0.f, 0.f, 0.f, 0.f) : pp.light[slot]; // (asked for with the path state, not where it is first used: later vertices 21.75 -> 21.3 ms)
             f3 tot0 = mk3(0.f, 0.f, 0.f); // FIRST, fast launch: what this vertex adds to the (so far empty) sum of its slot
             float4 li_keep = make_float4(0.f, 0.f, 0.f, 0.f);
             f3 cum = mk3(st.x, st.y, st.z);
@@ -167,14 +177,15 @@ __global__ __launch_bounds__((FIRST ? RGK_SHADE_BLOCK : RGK_SHADE_BLOCK_LATER), 
                     // 55.9 ms of shading per round: the lanes that could stop early wait for their wave anyway.)
                     const bool ends = last;
                     float4 li; // the path's light {pos, code}: sampled by the first vertex, carried in pp.light after it
-                    if (FIRST) {
+                    if (CL) li = make_float4(sc.cl_pos[0], sc.cl_pos[1], sc.cl_pos[2], __uint_as_float(0u));
+                    else if (FIRST) {
                         f3 lpos;
                         const uint32_t lcode = light_code(sc, sample2d_t(tb, seed, s, base2d + 2u), sample1d_t(tb, seed, s, 0u), sample2d_t(tb, seed, s, base2d), lpos);
                         li = make_float4(lpos.x, lpos.y, lpos.z, __uint_as_float(lcode));
                     } else li = li_slot;
                     bool nee_dead = false;
                     if (RGK_SKIP_DEAD_NEE && ends && !GENERIC) {
-                        const DLight L0 = light_from_code(sc, mk3(li.x, li.y, li.z), __float_as_uint(li.w));
+                        const DLight L0 = CL ? light_constant(sc) : light_from_code(sc, mk3(li.x, li.y, li.z), __float_as_uint(li.w));
                         if (L0.type < 0) nee_dead = true;
                         else {
                             const f3 df = pos - L0.pos;
@@ -205,7 +216,7 @@ __global__ __launch_bounds__((FIRST ? RGK_SHADE_BLOCK : RGK_SHADE_BLOCK_LATER), 
                     // ---- phase 3 for this vertex: NEE to the path's light, :427-460,485-496
                     {
                         li_keep = li;
-                        const DLight L = light_from_code(sc, mk3(li.x, li.y, li.z), __float_as_uint(li.w));
+                        const DLight L = CL ? light_constant(sc) : light_from_code(sc, mk3(li.x, li.y, li.z), __float_as_uint(li.w));
                         f3 e_front = mk3(0.f, 0.f, 0.f);
                         if (dot3(faceN, Vr) > 0) e_front = mk3(mat.emission[0], mat.emission[1], mat.emission[2]);
                         const bool has_e = (e_front.x != 0.f) || (e_front.y != 0.f) || (e_front.z != 0.f);
@@ -237,9 +248,14 @@ __global__ __launch_bounds__((FIRST ? RGK_SHADE_BLOCK : RGK_SHADE_BLOCK_LATER), 
                                 f3 rad = has_e ? A - B : A;
                                 if (rad.x != 0.f || rad.y != 0.f || rad.z != 0.f) {
                                     shadow = true;
-                                    sA = make_float4(L.pos.x, L.pos.y, L.pos.z, sd.x);
-                                    sB = make_float4(sd.y, sd.z, slen - eps * 20.0f, __uint_as_float(slot));
-                                    sC = make_float4(rad.x, rad.y, rad.z, 0.0f + eps * 20.0f);
+                                    if (CL && RGK_CL_REC32) {
+                                        sA = make_float4(sd.x, sd.y, sd.z, slen - eps * 20.0f);
+                                        sB = make_float4(rad.x, rad.y, rad.z, __uint_as_float(slot));
+                                    } else {
+                                        sA = make_float4(L.pos.x, L.pos.y, L.pos.z, sd.x);
+                                        sB = make_float4(sd.y, sd.z, slen - eps * 20.0f, __uint_as_float(slot));
+                                        sC = make_float4(rad.x, rad.y, rad.z, 0.0f + eps * 20.0f);
+                                    }
                                 }
                             }
                         }
@@ -272,7 +288,7 @@ __global__ __launch_bounds__((FIRST ? RGK_SHADE_BLOCK : RGK_SHADE_BLOCK_LATER), 
                         thr[slot] = make_float4(cum.x, cum.y, cum.z, __uint_as_float((n & 0xffffu) | (c1 << 16)));
                     }
                     // the path's light: later vertices read it (and k_connect, for the NEE ray of a vertex on the record route)
-                    if (FIRST && (go || conn)) pp.light[slot] = li_keep;
+                    if (FIRST && !CL && (go || conn)) pp.light[slot] = li_keep;
                 }
                 } // !defer
             }
@@ -308,7 +324,8 @@ __global__ __launch_bounds__((FIRST ? RGK_SHADE_BLOCK : RGK_SHADE_BLOCK_LATER), 
             }
             if (shadow) {
                 uint32_t p = s_base[1] + s_cnt[1][w] + __popcll(ms & ((1ull << lane) - 1ull));
-                shA[p] = sA; shB[p] = sB; shC[p] = sC;
+                shA[p] = sA; shB[p] = sB;
+                if (!(CL && RGK_CL_REC32)) shC[p] = sC;
             }
             __syncthreads(); // s_cnt / s_base are rewritten by the next iteration
         }
@@ -872,9 +889,21 @@ void rgk_launch_trace_shadow_first(hipStream_t st, const DevScene& sc, const Pas
     RGK_TRACE_DISPATCH(k_trace_shadow_first, g_bound_shadow, sc, pp, shA, shB, shC, tot, count_ptr, fetch, stats, tc.ovf)
 }
 
+// The same two for the 32-byte records of the constant-light route: shA = {d.xyz, far}, shB = {radiance.rgb, slot}; every ray
+// starts at sc.cl_pos with near = 20 eps.
+bool rgk_const_light_records() { return RGK_CL_REC32 != 0; }
+void rgk_launch_trace_shadow_cl(hipStream_t st, const DevScene& sc, const RgkTraceCfg& tc, bool count_stats, const float4* shA, const float4* shB,
+                                float4* tot, const uint32_t* count_ptr, uint32_t* fetch, unsigned long long* stats) {
+    RGK_TRACE_DISPATCH(k_trace_shadow_cl, g_bound_shadow, sc, shA, shB, tot, count_ptr, fetch, stats, tc.ovf)
+}
+void rgk_launch_trace_shadow_first_cl(hipStream_t st, const DevScene& sc, const PassParams& pp, const RgkTraceCfg& tc, bool count_stats, const float4* shA, const float4* shB,
+                                      float4* tot, const uint32_t* count_ptr, uint32_t* fetch, unsigned long long* stats) {
+    RGK_TRACE_DISPATCH(k_trace_shadow_first_cl, g_bound_shadow, sc, pp, shA, shB, tot, count_ptr, fetch, stats, tc.ovf)
+}
+
 void rgk_launch_shade(hipStream_t st, const DevScene& sc, const DevCamera& cam, const PassParams& pp, uint32_t bounce, const float4* rayA,
                       const float4* rayB, const float4* hit, float4* thr, float4* tot, float4* nextA, float4* nextB, float4* shA,
-                      float4* shB, float4* shC, uint32_t* counters, bool bdpt) {
+                      float4* shB, float4* shC, uint32_t* counters, bool bdpt, bool const_light) {
     const int blk = bounce == 0 ? RGK_SHADE_BLOCK : RGK_SHADE_BLOCK_LATER;
     const int g1 = bounded_grid(256 * 4 * 512 / blk, g_bound, blk), g2 = bounded_grid(256 * 2 * 512 / blk, g_bound, blk);
     // the second launch shades the vertices the first one listed (materials on the generic BxDF route); it returns at once when there are none
@@ -884,6 +913,12 @@ void rgk_launch_shade(hipStream_t st, const DevScene& sc, const DevCamera& cam, 
     } else if (bdpt) {
         k_shade<false, false, true><<<g1, blk, RGK_LDS_SHADE_BYTES, st>>>(sc, cam, pp, bounce, rayA, rayB, hit, thr, tot, nextA, nextB, shA, shB, shC, counters);
         k_shade<true, false, true><<<g2, blk, RGK_LDS_SHADE_BYTES, st>>>(sc, cam, pp, bounce, rayA, rayB, hit, thr, tot, nextA, nextB, shA, shB, shC, counters);
+    } else if (const_light && bounce == 0) {
+        k_shade<false, true, false, true><<<g1, blk, RGK_LDS_SHADE_BYTES, st>>>(sc, cam, pp, bounce, rayA, rayB, hit, thr, tot, nextA, nextB, shA, shB, shC, counters);
+        k_shade<true, true, false, true><<<g2, blk, RGK_LDS_SHADE_BYTES, st>>>(sc, cam, pp, bounce, rayA, rayB, hit, thr, tot, nextA, nextB, shA, shB, shC, counters);
+    } else if (const_light) {
+        k_shade<false, false, false, true><<<g1, blk, RGK_LDS_SHADE_BYTES, st>>>(sc, cam, pp, bounce, rayA, rayB, hit, thr, tot, nextA, nextB, shA, shB, shC, counters);
+        k_shade<true, false, false, true><<<g2, blk, RGK_LDS_SHADE_BYTES, st>>>(sc, cam, pp, bounce, rayA, rayB, hit, thr, tot, nextA, nextB, shA, shB, shC, counters);
     } else if (bounce == 0) {
         k_shade<false, true><<<g1, blk, RGK_LDS_SHADE_BYTES, st>>>(sc, cam, pp, bounce, rayA, rayB, hit, thr, tot, nextA, nextB, shA, shB, shC, counters);
         k_shade<true, true><<<g2, blk, RGK_LDS_SHADE_BYTES, st>>>(sc, cam, pp, bounce, rayA, rayB, hit, thr, tot, nextA, nextB, shA, shB, shC, counters);

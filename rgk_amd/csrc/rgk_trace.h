@@ -174,7 +174,12 @@ __device__ __forceinline__ int lds_pop(const int* p) {
     asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"((uint32_t)(uintptr_t)p) : "memory");
     return v;
 }
-template <bool ANY, bool COUNT, int STACK, int LDSN, bool RAYGEN = false, bool JOB = false>
+// CLO (any hit, the constant-light route of a unidirectional round): every ray starts at the scene's one point light with
+// near = 20 eps, so the queue holds q0 = {d.xyz, far}, q1 = {radiance.rgb, slot} only.  (Origin and near distance are still kept
+// per lane, copied from the kernel arguments at each refill behind an empty asm: left visible as loop invariants, everything that
+// depends on them alone -- the scene box relative to the origin, for one -- is hoisted out of the walk and held in VGPRs for the
+// whole kernel, 63 -> 70 of them; behind the asm the kernel has the registers of k_trace_shadow.)
+template <bool ANY, bool COUNT, int STACK, int LDSN, bool RAYGEN = false, bool JOB = false, bool CLO = false>
 __device__ __forceinline__ void trace_persistent(const DevScene& sc, const float4* __restrict__ q0, const float4* __restrict__ q1,
                                                  const float4* __restrict__ q2, const float2* __restrict__ nearfar,
                                                  float4* __restrict__ hit, float4* __restrict__ tot, uint8_t* __restrict__ vis_out,
@@ -279,6 +284,14 @@ __device__ __forceinline__ void trace_persistent(const DevScene& sc, const float
                     } else
                     if (RAYGEN) {
                         camera_ray_of_slot(*cam, *pp, idx, o, d, &pixel_j);
+                        ignore = 0xffffffffu;
+                    } else if (CLO) {
+                        const float4 a = q0[idx], b = q1[idx];
+                        o = mk3(sc.cl_pos[0], sc.cl_pos[1], sc.cl_pos[2]);
+                        d = mk3(a.x, a.y, a.z); tf = a.w;
+                        rad = mk3(b.x, b.y, b.z); slot = __float_as_uint(b.w);
+                        tn = 0.0f + eps * 20.0f; // Ray(light.pos, p.pos, 20 eps), src/ray.hpp:15-22
+                        asm volatile("" : "+v"(o.x), "+v"(o.y), "+v"(o.z), "+v"(tn));
                         ignore = 0xffffffffu;
                     } else {
                         const float4 a = q0[idx], b = q1[idx];
@@ -830,6 +843,21 @@ __global__ __launch_bounds__(RGK_TRACE_BLOCK, (LDSN <= 16 ? RGK_TRACE_WAVES : 5)
         atomicAdd(&stats[3], (unsigned long long)n_tris);
     }
 }
+// ... with the 32-byte records of the constant-light route: shA = (d.xyz, far)  shB = (radiance.rgb, slot); o = sc.cl_pos, near = 20 eps
+template <bool COUNT, int STACK, int LDSN>
+__global__ __launch_bounds__(RGK_TRACE_BLOCK, (LDSN <= 16 ? RGK_TRACE_WAVES : 5)) void k_trace_shadow_cl(const DevScene sc, const float4* __restrict__ shA,
+                                                                   const float4* __restrict__ shB, float4* __restrict__ tot,
+                                                                   const uint32_t* __restrict__ count_ptr, uint32_t* __restrict__ fetch,
+                                                                   unsigned long long* __restrict__ stats, int* __restrict__ ovf) {
+    __shared__ int lds_stack[LDSN * RGK_TRACE_BLOCK];
+    uint32_t n_nodes = 0, n_tris = 0;
+    trace_persistent<true, COUNT, STACK, LDSN, false, false, true>(sc, shA, shB, nullptr, nullptr, nullptr, tot, nullptr, RGK_SHADOW_ADD, nullptr, *count_ptr, fetch,
+                                         lds_stack + threadIdx.x, ovf + (blockIdx.x * RGK_TRACE_BLOCK + threadIdx.x), gridDim.x * RGK_TRACE_BLOCK, n_nodes, n_tris);
+    if (COUNT) {
+        atomicAdd(&stats[2], (unsigned long long)n_nodes);
+        atomicAdd(&stats[3], (unsigned long long)n_tris);
+    }
+}
 
 // K5 for bidirectional rounds: one queue entry per camera-path vertex (JOB above).  jobs = {vertex}{contribution, mask}{emission},
 // rads = one radiance per ray (k_connect wrote both, and counted the rays).
@@ -863,6 +891,22 @@ __global__ __launch_bounds__(RGK_TRACE_BLOCK, (LDSN <= 16 ? RGK_TRACE_WAVES : 5)
     __shared__ int lds_stack[LDSN * RGK_TRACE_BLOCK];
     uint32_t n_nodes = 0, n_tris = 0;
     trace_persistent<true, COUNT, STACK, LDSN>(sc, shA, shB, shC, nullptr, nullptr, tot, nullptr, RGK_SHADOW_ADD, nullptr, *count_ptr, fetch,
+                                         lds_stack + threadIdx.x, ovf + (blockIdx.x * RGK_TRACE_BLOCK + threadIdx.x), gridDim.x * RGK_TRACE_BLOCK, n_nodes, n_tris, nullptr, &pp);
+    if (COUNT) {
+        atomicAdd(&stats[2], (unsigned long long)n_nodes);
+        atomicAdd(&stats[3], (unsigned long long)n_tris);
+    }
+}
+
+// ... with the 32-byte records of the constant-light route (k_trace_shadow_cl)
+template <bool COUNT, int STACK, int LDSN>
+__global__ __launch_bounds__(RGK_TRACE_BLOCK, (LDSN <= 16 ? RGK_TRACE_WAVES : 5)) void k_trace_shadow_first_cl(const DevScene sc, const PassParams pp, const float4* __restrict__ shA,
+                                                                   const float4* __restrict__ shB, float4* __restrict__ tot,
+                                                                   const uint32_t* __restrict__ count_ptr, uint32_t* __restrict__ fetch,
+                                                                   unsigned long long* __restrict__ stats, int* __restrict__ ovf) {
+    __shared__ int lds_stack[LDSN * RGK_TRACE_BLOCK];
+    uint32_t n_nodes = 0, n_tris = 0;
+    trace_persistent<true, COUNT, STACK, LDSN, false, false, true>(sc, shA, shB, nullptr, nullptr, nullptr, tot, nullptr, RGK_SHADOW_ADD, nullptr, *count_ptr, fetch,
                                          lds_stack + threadIdx.x, ovf + (blockIdx.x * RGK_TRACE_BLOCK + threadIdx.x), gridDim.x * RGK_TRACE_BLOCK, n_nodes, n_tris, nullptr, &pp);
     if (COUNT) {
         atomicAdd(&stats[2], (unsigned long long)n_nodes);

@@ -66,7 +66,12 @@ class Scene:
 
     def set_tuning(self, **kw):
         """rgk_scene_set_tuning: per-scene tuning switches (entry_points, entry_cap, light_entry, sample_group, batch_paths,
-        workspace_gb); none changes a result."""
+        workspace_gb, beam, const_light); none changes a result.
+
+        const_light (default 1): where info().const_light == 1 -- one point light of size 0, nothing else that emits, no -0.0 in
+        its position, and the light pick's own float comparisons select it for the largest sample 1 - 2^-24 -- unidirectional
+        rounds take the light as launch constants instead of sampling, storing and re-reading it per path, and queue 32-byte
+        shadow records without the shared origin.  Exact: the pick has one outcome, and pos + 0 * v == pos.  0: per-path route."""
         for k, v in kw.items():
             capi.check(self.lib, self.lib.rgk_scene_set_tuning(self.h, k.encode(), float(v)))
         return self
