@@ -6,15 +6,16 @@
 struct RgkBuildPrim { // one reference: the (possibly clipped) box of a triangle and the triangle it stands for
     float bmin[3], bmax[3];
     uint32_t tri;
-    float pb[4]; // the piece in the triangle's own coordinates (rgk_host.cpp Prim::pb), carried to the leaf order for refits
+    float pb[4]; // the piece in the triangle's own coordinates (rgk_commit.h Prim::pb), carried to the leaf order for refits
 };
 
 // h_prims: n references on the host.  d_recs: TriIsect per ORIGINAL triangle id, on the device.  d_nodes (capacity n QNodes) and
-// d_leaf_recs (n records) are filled.  rotate: passes of the refit's quality step (tree rotations; 0 = plain LBVH).  Returns 0, or a negative
-// rgk_status with *err set.
+// d_leaf_recs (n records) are filled.  rotate: passes of the refit's quality step (tree rotations; 0 = plain LBVH); ploc_radius: places
+// on either side in which a cluster looks for its partner (0 = the Karras hierarchy); morton_bits: at most this many key bits per axis.
+// Each of the three: -1 = the build's default (BuildOptions::lbvh_*, rgk_commit.h).  Returns 0, or a negative rgk_status with *err set.
 int rgk_build_bvh4_device(hipStream_t st, const RgkBuildPrim* h_prims, uint32_t n, const float smin[3], const float smax[3], float pad,
-                          uint32_t max_leaf, int rotate, const TriIsect* d_recs, QNode* d_nodes, TriIsect* d_leaf_recs, float4* d_leaf_pb, uint32_t* n_nodes,
-                          uint32_t* n_levels, const char** err);
+                          uint32_t max_leaf, int rotate, int ploc_radius, int morton_bits, const TriIsect* d_recs, QNode* d_nodes, TriIsect* d_leaf_recs,
+                          float4* d_leaf_pb, uint32_t* n_nodes, uint32_t* n_levels, const char** err);
 
 // Refit for moved vertices (rgk_scene_refit): the references' intersection records recomputed from d_vertices (TriIsect.tri names the
 // triangle of each), their boxes, then every node of the 4-wide tree bottom-up -- child boxes, node box, 8-bit codes; the

@@ -1,5 +1,5 @@
 // Accelerator build on the device (replaces the reference's CPU kd build, src/scene.cpp:401-657, as the host
-// builder of rgk_host.cpp does -- results are compared, never the structure).
+// builder of rgk_commit.cpp does -- results are compared, never the structure).
 //
 //   1. Morton key per reference box (the centroid inside the scene box at as many bits per axis as the 64-bit key leaves beside
 //      the reference index -- 14 at a million references; the index below them: unique keys)
@@ -23,7 +23,6 @@
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
-#include <cstdlib>
 
 #include "device_types.h"
 #include "rgk_build.h"
@@ -133,6 +132,9 @@ __global__ void k_refit(const RgkBuildPrim* __restrict__ prims, const unsigned l
     }
 }
 
+#ifndef RGK_LBVH_ROTATE_PASSES
+#define RGK_LBVH_ROTATE_PASSES 4 // passes of the rotation step over the Karras hierarchy when nothing else is asked for
+#endif
 #ifndef RGK_PLOC_RADIUS
 #define RGK_PLOC_RADIUS 6 // places of the current order on either side in which a cluster looks for its partner (2..8: the same; 16 and more: worse)
 #endif
@@ -294,7 +296,7 @@ __global__ void k_ploc_rename(int n, int* __restrict__ left, int* __restrict__ r
 }
 
 // quantise one axis of up to four child boxes against the node box: the smallest power-of-two step whose outward-rounded codes
-// fit 8 bits, verified with the kernels' decode fma(q, step, p) -- the host builder's loop (rgk_host.cpp QbvhBuilder)
+// fit 8 bits, verified with the kernels' decode fma(q, step, p) -- the host builder's loop (rgk_commit.cpp QbvhBuilder)
 __device__ void quantise_axis(const BBox* ch, int nch, int a, float p, float ext, float& step, uint8_t* qlo, uint8_t* qhi) {
     int e = -126;
     if (ext > 0.f) { (void)frexpf(ext / 255.0f, &e); }
@@ -391,7 +393,7 @@ __global__ void k_refit_recs(const float* __restrict__ vertices, const uint32_t*
         float v[3][3];
         for (int c = 0; c < 3; c++) { const uint32_t vi = idx[3 * tri + c]; for (int a = 0; a < 3; a++) v[c][a] = vertices[3 * (size_t)vi + a]; }
         const float d0[3] = {v[1][0] - v[0][0], v[1][1] - v[0][1], v[1][2] - v[0][2]}, d1[3] = {v[2][0] - v[0][0], v[2][1] - v[0][1], v[2][2] - v[0][2]};
-        // crossv(d1, d0), normv, -dotv(n, v0): rgk_host.cpp's helpers spelled out
+        // crossv(d1, d0), normv, -dotv(n, v0): rgk_commit.h's helpers spelled out
         const float cx = d1[1] * d0[2] - d0[1] * d1[2], cy = d1[2] * d0[0] - d0[2] * d1[0], cz = d1[0] * d0[1] - d0[0] * d1[1];
         const float tx = cx * cx, ty = cy * cy, tz = cz * cz;
         const float inv = 1.0f / __builtin_sqrtf(tx + ty + tz);
@@ -525,8 +527,8 @@ int rgk_refit_bvh4_device(hipStream_t st, uint32_t n_refs, uint32_t n_nodes, uin
 #define BCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { *err = hipGetErrorString(e_); return e_ == hipErrorOutOfMemory ? -3 : -2; } } while (0)
 
 int rgk_build_bvh4_device(hipStream_t st, const RgkBuildPrim* h_prims, uint32_t n, const float smin[3], const float smax[3], float pad,
-                          uint32_t max_leaf, int rotate, const TriIsect* d_recs, QNode* d_nodes, TriIsect* d_leaf_recs, float4* d_leaf_pb, uint32_t* n_nodes,
-                          uint32_t* n_levels, const char** err) {
+                          uint32_t max_leaf, int rotate, int ploc_radius, int morton_bits, const TriIsect* d_recs, QNode* d_nodes, TriIsect* d_leaf_recs,
+                          float4* d_leaf_pb, uint32_t* n_nodes, uint32_t* n_levels, const char** err) {
     *err = "";
     if (n < 2 || n <= max_leaf) { *err = "too few references for the device build"; return -5; }
     Tmp<RgkBuildPrim> prims;
@@ -546,7 +548,7 @@ int rgk_build_bvh4_device(hipStream_t st, const RgkBuildPrim* h_prims, uint32_t 
     int ibits = 1;
     while (ibits < 32 && (1ull << ibits) < (unsigned long long)n) ibits++;
     int mbits = std::min(21, (64 - ibits) / 3);
-    if (const char* e = std::getenv("RGK_LBVH_MORTON_BITS")) mbits = std::max(1, std::min(mbits, std::atoi(e))); // experiments (10 = round 2's keys)
+    if (morton_bits >= 0) mbits = std::max(1, std::min(mbits, morton_bits)); // experiments (10 = round 2's keys)
     k_morton<<<grid, 256, 0, st>>>(prims.p, n, mn, inv, mbits, ibits, keys.p);
     {
         size_t tmp_bytes = 0;
@@ -557,9 +559,8 @@ int rgk_build_bvh4_device(hipStream_t st, const RgkBuildPrim* h_prims, uint32_t 
         BCHK(hipStreamSynchronize(st)); // tmp goes out of scope
     }
     BCHK(hipMemsetAsync(arrived.p, 0, (size_t)n * sizeof(int), st));
-    int ploc_radius = RGK_PLOC_RADIUS;
-    if (const char* e = std::getenv("RGK_LBVH_PLOC")) ploc_radius = std::max(0, std::min(256, std::atoi(e))); // 0: the Karras hierarchy
-    if (ploc_radius && !std::getenv("RGK_LBVH_ROTATE")) rotate = 0; // (rotations on top of the clustered tree: measured, nothing -- tools/gpu_lbvh_morton_sweep.py)
+    if (ploc_radius < 0) ploc_radius = RGK_PLOC_RADIUS; // 0: the Karras hierarchy
+    if (rotate < 0) rotate = ploc_radius ? 0 : RGK_LBVH_ROTATE_PASSES; // (rotations on top of the clustered tree: measured, nothing -- tools/gpu_lbvh_morton_sweep.py)
     unsigned long long* order = keys_sorted.p; // the reference behind every leaf position (low bits of the key)
     Tmp<unsigned long long> keys_tree;
     Tmp<int> leaf_parent_tree;

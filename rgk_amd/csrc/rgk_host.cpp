@@ -1,48 +1,30 @@
 // Host runtime behind the C ABI of include/rgk.h.
 //
-//   * scene commit: the OUTPUTS of Scene::Commit the hot path reads (reference
-//     src/scene.cpp:294-400): triangle planes, areal-light tables sorted by area,
-//     light powers, epsilon = 1e-5 * bbox diagonal, epsilon-padded bbox;
-//   * the build's own accelerator (binned-SAH BVH2 over pre-split references, collapsed to a
-//     quantised 4-wide BVH with one 64-byte line per node) -- the reference's
-//     kd-tree construction (scene.cpp:431-657) is out of scope, only its nearest-hit
-//     semantics are kept;
+//   * scene objects: rgk_scene_create takes what the GPU-free commit unit computes (rgk_commit.h: bounds and epsilon,
+//     triangle records, the SAH accelerator, shading tables), or has the accelerator built on the device (rgk_build.h),
+//     and uploads it; rgk_scene_refit, tuning, progress;
 //   * the round driver: tiles -> per-pixel seeds (a2) -> passes of paths resident in
 //     HBM -> raygen / trace / shade / shadow / resolve launches on one HIP stream.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <array>
-#include <iterator>
 #include <atomic>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <limits>
 #include <string>
 #include <vector>
-#include <functional>
-#include <random>
 
 #include "../../include/rgk.h"
 #include "device_types.h"
+#include "rgk_commit.h"
 #include "rgk_kernels.h"
 #include "rgk_build.h"
 
 namespace {
 
-thread_local std::string g_err;
-int fail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
 #define HIPCHK(x)                                                                                     \
     do {                                                                                              \
         hipError_t e_ = (x);                                                                          \
@@ -50,398 +32,6 @@ int fail(int code, const char* fmt, ...) {
             return fail(e_ == hipErrorOutOfMemory ? RGK_ERR_OOM : RGK_ERR_DEVICE, "%s: %s (%s:%d)", #x, \
                         hipGetErrorString(e_), __FILE__, __LINE__);                                   \
     } while (0)
-
-struct V3 {
-    float x, y, z;
-};
-inline V3 sub(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-inline V3 crossv(V3 x, V3 y) { return {x.y * y.z - y.y * x.z, x.z * y.x - y.z * x.x, x.x * y.y - y.x * x.y}; }
-inline float dotv(V3 a, V3 b) {
-    float tx = a.x * b.x, ty = a.y * b.y, tz = a.z * b.z;
-    return tx + ty + tz;
-}
-inline V3 scale(V3 a, float s) { return {a.x * s, a.y * s, a.z * s}; }
-inline V3 normv(V3 v) { return scale(v, 1.0f / std::sqrt(dotv(v, v))); }
-inline float comp(V3 v, int i) { return i == 0 ? v.x : (i == 1 ? v.y : v.z); }
-
-// ------------------------------------------------------------------ BVH build
-struct Prim {
-    float bmin[3], bmax[3], c[3];
-    uint32_t tri;
-    uint32_t ref;  // this reference's number (prims are shuffled by the builders; the leaf order lists these)
-    float pb[4];   // the piece of the triangle this reference stands for, as a box in the triangle's own coordinates: P = v0 + b (v1 - v0) + c (v2 - v0)
-                   // with b in [pb[0], pb[1]], c in [pb[2], pb[3]] -- (0, 1, 0, 1): the whole triangle.  A moved triangle maps its pieces
-                   // affinely, so rgk_scene_refit re-boxes a reference from these four numbers instead of from the whole triangle
-};
-struct Box {
-    float mn[3], mx[3];
-    void reset() { for (int i = 0; i < 3; i++) { mn[i] = std::numeric_limits<float>::infinity(); mx[i] = -mn[i]; } }
-    void grow(const float* a, const float* b) { for (int i = 0; i < 3; i++) { mn[i] = std::min(mn[i], a[i]); mx[i] = std::max(mx[i], b[i]); } }
-    void grow(const Box& o) { grow(o.mn, o.mx); }
-    float area() const {
-        float dx = mx[0] - mn[0], dy = mx[1] - mn[1], dz = mx[2] - mn[2];
-        if (dx < 0 || dy < 0 || dz < 0) return 0.f;
-        return 2.f * (dx * dy + dy * dz + dz * dx);
-    }
-};
-
-// Early split clipping of large triangles (reference-splitting before the build): a triangle whose box is longer
-// than `lmax` on some axis enters the build as several references, one per piece of the triangle clipped at the
-// box midpoint, each with the tight box of its piece.  The pieces tile the triangle, so every hit point lies in
-// the (eps-padded) box of a reference; the leaf records are whole triangles, so a hit is what it was -- the tree
-// just stops dragging wall- and floor-sized boxes through its upper levels.
-struct RefSplitter {
-    struct P3 { double x[3]; };
-    float lmax;
-    size_t budget; // extra references still allowed
-    std::vector<Prim>* out;
-    double tv[3][3]; // the triangle being split (for the pieces' parameter boxes)
-    void param_box(const std::vector<P3>& poly, float pb[4]) const {
-        double e1[3], e2[3], a11 = 0, a12 = 0, a22 = 0;
-        for (int k = 0; k < 3; k++) { e1[k] = tv[1][k] - tv[0][k]; e2[k] = tv[2][k] - tv[0][k]; a11 += e1[k] * e1[k]; a12 += e1[k] * e2[k]; a22 += e2[k] * e2[k]; }
-        const double det = a11 * a22 - a12 * a12;
-        double b0 = 1, b1 = 0, c0 = 1, c1 = 0;
-        if (!(det > 0)) { pb[0] = 0.f; pb[1] = 1.f; pb[2] = 0.f; pb[3] = 1.f; return; }
-        for (const P3& v : poly) {
-            double r1 = 0, r2 = 0;
-            for (int k = 0; k < 3; k++) { const double w = v.x[k] - tv[0][k]; r1 += e1[k] * w; r2 += e2[k] * w; }
-            const double b = (a22 * r1 - a12 * r2) / det, c = (a11 * r2 - a12 * r1) / det;
-            b0 = std::min(b0, b); b1 = std::max(b1, b); c0 = std::min(c0, c); c1 = std::max(c1, c);
-        }
-        const double pad = 1e-5; // (the solve's rounding; the pieces overlap by this much)
-        pb[0] = (float)std::max(0.0, b0 - pad); pb[1] = (float)std::min(1.0, b1 + pad); pb[2] = (float)std::max(0.0, c0 - pad); pb[3] = (float)std::min(1.0, c1 + pad);
-    }
-    static void clip(const std::vector<P3>& in, int ax, double plane, bool keep_below, std::vector<P3>& res) {
-        res.clear();
-        const size_t n = in.size();
-        for (size_t i = 0; i < n; i++) {
-            const P3 &a = in[i], &b = in[(i + 1) % n];
-            const bool ia = keep_below ? a.x[ax] <= plane : a.x[ax] >= plane, ib = keep_below ? b.x[ax] <= plane : b.x[ax] >= plane;
-            if (ia) res.push_back(a);
-            if (ia != ib) {
-                const double t = (plane - a.x[ax]) / (b.x[ax] - a.x[ax]);
-                P3 m;
-                for (int k = 0; k < 3; k++) m.x[k] = a.x[k] + t * (b.x[k] - a.x[k]);
-                m.x[ax] = plane;
-                res.push_back(m);
-            }
-        }
-    }
-    void emit(const std::vector<P3>& poly, const float* bmin, const float* bmax, uint32_t tri, int depth) {
-        // tight box of the piece: polygon bounds (outward-rounded to float) within the parent's box
-        Prim p;
-        for (int a = 0; a < 3; a++) {
-            double lo = std::numeric_limits<double>::infinity(), hi = -lo;
-            for (const P3& v : poly) { lo = std::min(lo, v.x[a]); hi = std::max(hi, v.x[a]); }
-            float fl = (float)lo, fh = (float)hi;
-            if ((double)fl > lo) fl = std::nextafterf(fl, -std::numeric_limits<float>::infinity());
-            if ((double)fh < hi) fh = std::nextafterf(fh, std::numeric_limits<float>::infinity());
-            p.bmin[a] = std::max(fl, bmin[a]); p.bmax[a] = std::min(fh, bmax[a]);
-            if (p.bmin[a] > p.bmax[a]) p.bmin[a] = p.bmax[a] = 0.5f * (bmin[a] + bmax[a]);
-        }
-        int ax = 0;
-        for (int a = 1; a < 3; a++) if (p.bmax[a] - p.bmin[a] > p.bmax[ax] - p.bmin[ax]) ax = a;
-        if (!(p.bmax[ax] - p.bmin[ax] > lmax) || depth >= 12 || budget == 0 || poly.size() < 3) {
-            for (int a = 0; a < 3; a++) p.c[a] = 0.5f * (p.bmin[a] + p.bmax[a]);
-            p.tri = tri;
-            p.ref = (uint32_t)out->size();
-            if (depth == 0) { p.pb[0] = 0.f; p.pb[1] = 1.f; p.pb[2] = 0.f; p.pb[3] = 1.f; } else param_box(poly, p.pb);
-            out->push_back(p);
-            return;
-        }
-        budget--;
-        const double mid = 0.5 * ((double)p.bmin[ax] + (double)p.bmax[ax]);
-        std::vector<P3> lo, hi;
-        clip(poly, ax, mid, true, lo);
-        clip(poly, ax, mid, false, hi);
-        float cmax[3] = {p.bmax[0], p.bmax[1], p.bmax[2]}, cmin[3] = {p.bmin[0], p.bmin[1], p.bmin[2]};
-        cmax[ax] = std::nextafterf((float)mid, std::numeric_limits<float>::infinity());
-        cmin[ax] = std::nextafterf((float)mid, -std::numeric_limits<float>::infinity());
-        if (lo.size() >= 3) emit(lo, p.bmin, cmax, tri, depth + 1);
-        if (hi.size() >= 3) emit(hi, cmin, p.bmax, tri, depth + 1);
-    }
-};
-
-struct BvhBuilder {
-    std::vector<Prim>& prims;
-    std::vector<BvhNode> nodes;
-    std::vector<uint32_t> order; // reference numbers (Prim::ref) in leaf order
-    uint32_t max_depth = 0;
-    float pad;
-    static constexpr int NBINS = 16;
-    int MAX_LEAF = 4;                      // leaf encoding allows up to 16
-    float C_TRAV = 1.0f, C_ISECT = 1.0f;   // SAH: one node step vs one triangle test (swept on MI355X: 1.0 best)
-    BvhBuilder(std::vector<Prim>& p, float pad_) : prims(p), pad(pad_) {
-        if (const char* e = getenv("RGK_BVH_MAXLEAF")) MAX_LEAF = std::min(16, std::max(1, atoi(e)));
-        if (const char* e = getenv("RGK_BVH_CISECT")) C_ISECT = (float)atof(e);
-    }
-
-    int make_leaf(size_t b, size_t e) {
-        uint32_t first = order.size();
-        for (size_t i = b; i < e; i++) order.push_back(prims[i].ref);
-        uint32_t cnt = (uint32_t)(e - b);
-        return (int)~((first << 4) | (cnt - 1));
-    }
-    // returns the child code for prims[b,e) and its (padded) box
-    int build(size_t b, size_t e, uint32_t depth, Box& box) {
-        max_depth = std::max(max_depth, depth);
-        box.reset();
-        Box cb;
-        cb.reset();
-        for (size_t i = b; i < e; i++) { box.grow(prims[i].bmin, prims[i].bmax); cb.grow(prims[i].c, prims[i].c); }
-        size_t n = e - b;
-        size_t mid = 0;
-        bool leaf = (n == 1);
-        if (!leaf) {
-            float best = std::numeric_limits<float>::infinity();
-            int best_axis = -1, best_bin = -1;
-            float parent_area = box.area();
-            for (int ax = 0; ax < 3; ax++) {
-                float lo = cb.mn[ax], hi = cb.mx[ax];
-                if (!(hi > lo)) continue;
-                Box bb[NBINS];
-                uint32_t cnt[NBINS] = {0};
-                for (auto& x : bb) x.reset();
-                float k = NBINS / (hi - lo);
-                for (size_t i = b; i < e; i++) {
-                    int bi = std::min(NBINS - 1, std::max(0, (int)((prims[i].c[ax] - lo) * k)));
-                    cnt[bi]++;
-                    bb[bi].grow(prims[i].bmin, prims[i].bmax);
-                }
-                float ra[NBINS];
-                uint32_t rc[NBINS];
-                Box acc;
-                acc.reset();
-                uint32_t c = 0;
-                for (int i = NBINS - 1; i > 0; i--) { acc.grow(bb[i]); c += cnt[i]; ra[i] = acc.area(); rc[i] = c; }
-                acc.reset();
-                c = 0;
-                for (int i = 0; i < NBINS - 1; i++) {
-                    acc.grow(bb[i]);
-                    c += cnt[i];
-                    if (c == 0 || rc[i + 1] == 0) continue;
-                    float cost = C_TRAV + C_ISECT * (acc.area() * c + ra[i + 1] * rc[i + 1]) / std::max(parent_area, 1e-30f);
-                    if (cost < best) { best = cost; best_axis = ax; best_bin = i; }
-                }
-            }
-            if (best_axis >= 0 && (n > (size_t)MAX_LEAF || best < C_ISECT * n)) {
-                float lo = cb.mn[best_axis], hi = cb.mx[best_axis];
-                float k = NBINS / (hi - lo);
-                auto it = std::partition(prims.begin() + b, prims.begin() + e, [&](const Prim& p) {
-                    int bi = std::min(NBINS - 1, std::max(0, (int)((p.c[best_axis] - lo) * k)));
-                    return bi <= best_bin;
-                });
-                mid = it - prims.begin();
-                if (mid == b || mid == e) best_axis = -1;
-            } else if (best_axis >= 0) {
-                leaf = true; // SAH prefers a leaf and it fits
-                best_axis = 0;
-            }
-            if (!leaf && best_axis < 0) {
-                if (n <= (size_t)MAX_LEAF) leaf = true;
-                else { // coincident centroids: median split by index
-                    int ax = 0;
-                    float ex = -1;
-                    for (int a = 0; a < 3; a++) if (box.mx[a] - box.mn[a] > ex) { ex = box.mx[a] - box.mn[a]; ax = a; }
-                    mid = b + n / 2;
-                    std::nth_element(prims.begin() + b, prims.begin() + mid, prims.begin() + e,
-                                     [ax](const Prim& p, const Prim& q) { return p.c[ax] < q.c[ax]; });
-                }
-            }
-        }
-        for (int i = 0; i < 3; i++) { box.mn[i] -= pad; box.mx[i] += pad; }
-        if (leaf) return make_leaf(b, e);
-        int idx = (int)nodes.size();
-        nodes.emplace_back();
-        Box lb, rb;
-        int l = build(b, mid, depth + 1, lb);
-        int r = build(mid, e, depth + 1, rb);
-        BvhNode& nd = nodes[idx];
-        for (int i = 0; i < 3; i++) { nd.lmin[i] = lb.mn[i]; nd.lmax[i] = lb.mx[i]; nd.rmin[i] = rb.mn[i]; nd.rmax[i] = rb.mx[i]; }
-        nd.left = l; nd.right = r; nd.pad[0] = nd.pad[1] = 0;
-        return idx;
-    }
-};
-
-// ------------------------------------------------------------------ BVH2 optimisation by reinsertion
-// The binned top-down build decides every split with local information; afterwards single subtrees are taken out and put back
-// where the surface-area cost of the whole tree grows least (insertion-based optimisation, Bittner, Hapala, Havran 2013, in its
-// simplest form: the largest nodes first, branch-and-bound search from the root).  Same triangles, same leaves, so the same
-// hits; on the Sponza proxy 8 rounds over half of the nodes cut the surface-area cost by 4 % and the node visits per ray by
-// 4 % (diffuse bounce rays) to 9 % (camera rays) -- tools/probe_wide_bvh.py measures it on the CPU.
-static void optimise_bvh2(std::vector<BvhNode>& nodes, std::vector<uint32_t>& order, int rounds, float frac) {
-    const int NI = (int)nodes.size();
-    if (NI < 8 || rounds <= 0) return;
-    std::vector<Box> box; std::vector<int> l, r, par, leaf_code;
-    box.reserve(2 * NI + 1); l.assign(NI, -1); r.assign(NI, -1);
-    box.resize(NI);
-    auto side_box = [](const BvhNode& n, bool left) { Box b; for (int a = 0; a < 3; a++) { b.mn[a] = left ? n.lmin[a] : n.rmin[a]; b.mx[a] = left ? n.lmax[a] : n.rmax[a]; } return b; };
-    for (int i = 0; i < NI; i++) {
-        for (int sd = 0; sd < 2; sd++) {
-            const int code = sd == 0 ? nodes[i].left : nodes[i].right;
-            const Box b = side_box(nodes[i], sd == 0);
-            int id;
-            if (code >= 0) { id = code; box[id] = b; }
-            else { id = (int)box.size(); box.push_back(b); l.push_back(-1); r.push_back(-1); leaf_code.resize(box.size(), 0); leaf_code[id] = code; }
-            (sd == 0 ? l[i] : r[i]) = id;
-        }
-    }
-    leaf_code.resize(box.size(), 0);
-    const int N = (int)box.size();
-    par.assign(N, -1);
-    for (int i = 0; i < NI; i++) { par[l[i]] = i; par[r[i]] = i; }
-    box[0] = box[l[0]]; box[0].grow(box[r[0]]);
-    auto refit_up = [&](int n) { while (n >= 0) { Box b = box[l[n]]; b.grow(box[r[n]]); box[n] = b; n = par[n]; } };
-    std::mt19937 rng(7);
-    const auto heap_cmp = [](const std::pair<float, int>& a, const std::pair<float, int>& b) { return a.first > b.first; };
-    std::vector<std::pair<float, int>> pq;
-    for (int it = 0; it < rounds; it++) {
-        std::vector<int> cand;
-        const auto larger = [&](int a, int b) { const float x = box[a].area(), y = box[b].area(); return x > y || (x == y && a < b); };
-        if (!(it & 1)) { // the largest nodes (they cost the most); bounded work per round: a 1 M-triangle tree moves its largest nodes only
-            for (int i = 1; i < N; i++) if (par[i] > 0) cand.push_back(i);
-            const size_t take = std::min<size_t>((size_t)(cand.size() * frac), 65536);
-            std::nth_element(cand.begin(), cand.begin() + take, cand.end(), larger);
-            cand.resize(take);
-            std::sort(cand.begin(), cand.end(), larger);
-        } else { // every other round: any nodes
-            const size_t take = std::min<size_t>((size_t)(N * frac), 65536);
-            for (size_t k = 0; k < take; k++) { const int i = (int)(rng() % (uint32_t)N); if (par[i] > 0) cand.push_back(i); }
-        }
-        for (int n : cand) {
-            const int p = par[n];
-            if (p <= 0) continue;
-            const int g = par[p];
-            const int sib = l[p] == n ? r[p] : l[p];
-            (l[g] == p ? l[g] : r[g]) = sib; // n and its parent leave the tree: the sibling moves up
-            par[sib] = g;
-            refit_up(g);
-            const Box nb = box[n];
-            const float na = nb.area();
-            float best = std::numeric_limits<float>::infinity();
-            int bx = sib;
-            pq.clear(); pq.push_back({0.f, 0});
-            while (!pq.empty()) {
-                std::pop_heap(pq.begin(), pq.end(), heap_cmp);
-                const float ind = pq.back().first; const int x = pq.back().second;
-                pq.pop_back();
-                if (ind + na >= best) break;
-                Box u = box[x]; u.grow(nb);
-                const float total = ind + u.area();
-                if (total < best && par[x] >= 0) { best = total; bx = x; } // (not above the root: node 0 stays the root)
-                const float child_ind = total - box[x].area();
-                if (l[x] >= 0 && child_ind + na < best) {
-                    pq.push_back({child_ind, l[x]}); std::push_heap(pq.begin(), pq.end(), heap_cmp);
-                    pq.push_back({child_ind, r[x]}); std::push_heap(pq.begin(), pq.end(), heap_cmp);
-                }
-            }
-            const int xp = par[bx]; // p becomes the parent of (bx, n) where bx was
-            (l[xp] == bx ? l[xp] : r[xp]) = p;
-            par[p] = xp; l[p] = bx; r[p] = n; par[bx] = p; par[n] = p;
-            refit_up(p);
-        }
-    }
-    // back to the builder's form: inner nodes in depth-first order from node 0, leaves re-listed in that order
-    std::vector<BvhNode> out; out.reserve(NI);
-    std::vector<uint32_t> new_order; new_order.reserve(order.size());
-    std::function<int(int)> emit = [&](int n) -> int {
-        if (l[n] < 0) {
-            const uint32_t code = ~(uint32_t)leaf_code[n], first = code >> 4, cnt = (code & 15u) + 1u;
-            const uint32_t nf = (uint32_t)new_order.size();
-            for (uint32_t k = 0; k < cnt; k++) new_order.push_back(order[first + k]);
-            return (int)~((nf << 4) | (cnt - 1));
-        }
-        const int idx = (int)out.size();
-        out.emplace_back();
-        const int a = emit(l[n]), b = emit(r[n]);
-        BvhNode& nd = out[idx];
-        for (int k = 0; k < 3; k++) { nd.lmin[k] = box[l[n]].mn[k]; nd.lmax[k] = box[l[n]].mx[k]; nd.rmin[k] = box[r[n]].mn[k]; nd.rmax[k] = box[r[n]].mx[k]; }
-        nd.left = a; nd.right = b; nd.pad[0] = nd.pad[1] = 0;
-        return idx;
-    };
-    emit(0);
-    nodes.swap(out);
-    order.swap(new_order);
-}
-
-// ------------------------------------------------------------------ BVH2 -> quantised BVH4
-// Collapse the binary tree (always open the inner child with the largest surface until four
-// children) and quantise each child box to 8 bits per plane relative to the node's box, rounding
-// outward and re-checking the decode in float exactly as the kernel evaluates it.
-struct QbvhBuilder {
-    const std::vector<BvhNode>& bn;
-    std::vector<QNode> out;
-    uint32_t max_stack = 0, max_depth = 0;
-    explicit QbvhBuilder(const std::vector<BvhNode>& b) : bn(b) {}
-    struct Child { int ref; Box box; };
-
-    static bool valid(const Box& b) { return b.mn[0] <= b.mx[0] && b.mn[1] <= b.mx[1] && b.mn[2] <= b.mx[2]; }
-    void children_of(int node, Child& l, Child& r) const {
-        const BvhNode& n = bn[node];
-        l.ref = n.left; r.ref = n.right;
-        for (int a = 0; a < 3; a++) { l.box.mn[a] = n.lmin[a]; l.box.mx[a] = n.lmax[a]; r.box.mn[a] = n.rmin[a]; r.box.mx[a] = n.rmax[a]; }
-    }
-    // `stack_before`: entries a traversal may already hold when it reaches this node
-    int collapse(int node, uint32_t depth, uint32_t stack_before) {
-        std::vector<Child> ch(2);
-        children_of(node, ch[0], ch[1]);
-        ch.erase(std::remove_if(ch.begin(), ch.end(), [](const Child& c) { return !valid(c.box); }), ch.end());
-        while (ch.size() < 4) {
-            int best = -1;
-            float best_area = -1.f;
-            for (size_t i = 0; i < ch.size(); i++)
-                if (ch[i].ref >= 0 && ch[i].box.area() > best_area) { best_area = ch[i].box.area(); best = (int)i; }
-            if (best < 0) break;
-            Child a, b;
-            children_of(ch[best].ref, a, b);
-            ch.erase(ch.begin() + best);
-            if (valid(a.box)) ch.push_back(a);
-            if (valid(b.box)) ch.push_back(b);
-        }
-        int idx = (int)out.size();
-        out.emplace_back();
-        max_depth = std::max(max_depth, depth);
-        const uint32_t pushed = (uint32_t)ch.size() - 1;
-        max_stack = std::max(max_stack, stack_before + pushed);
-        Box nb;
-        nb.reset();
-        for (auto& c : ch) nb.grow(c.box);
-        QNode q;
-        std::memset(&q, 0, sizeof(q));
-        for (int a = 0; a < 3; a++) {
-            q.p[a] = nb.mn[a];
-            float ext = nb.mx[a] - nb.mn[a];
-            int e = 0;
-            if (ext > 0.f) { std::frexp(ext / 255.0f, &e); } else e = -126;
-            for (;; e++) { // find the smallest exponent whose outward-rounded codes all fit and verify
-                if (e < -126) e = -126;
-                const float scale = std::ldexp(1.0f, e);
-                bool ok = true;
-                uint8_t lo[4], hi[4];
-                for (size_t i = 0; i < ch.size() && ok; i++) {
-                    float fl = std::floor((ch[i].box.mn[a] - q.p[a]) / scale), fh = std::ceil((ch[i].box.mx[a] - q.p[a]) / scale);
-                    if (fl < 0.f) fl = 0.f;
-                    while (fl > 0.f && std::fmaf(fl, scale, q.p[a]) > ch[i].box.mn[a]) fl -= 1.f;
-                    while (fh <= 255.f && std::fmaf(fh, scale, q.p[a]) < ch[i].box.mx[a]) fh += 1.f;
-                    if (fh > 255.f || fl > 255.f) { ok = false; break; }
-                    lo[i] = (uint8_t)fl; hi[i] = (uint8_t)fh;
-                }
-                if (!ok) continue;
-                (a == 0 ? q.sx : (a == 1 ? q.sy : q.sz)) = scale;
-                for (size_t i = 0; i < 4; i++) { q.qlo[a][i] = i < ch.size() ? lo[i] : 255; q.qhi[a][i] = i < ch.size() ? hi[i] : 0; }
-                break;
-            }
-        }
-        for (size_t i = 0; i < 4; i++) q.child[i] = RGK_QNODE_EMPTY;
-        out[idx] = q;
-        for (size_t i = 0; i < ch.size(); i++) {
-            int ref = ch[i].ref;
-            if (ref >= 0) ref = collapse(ref, depth + 1, stack_before + pushed);
-            out[idx].child[i] = ref;
-        }
-        return idx;
-    }
-};
 
 // ------------------------------------------------------------------ scene object
 // A device allocation with one owner: freed by its destructor, never copied.
@@ -484,12 +74,11 @@ struct DevBuf {
 
 } // namespace
 
-extern "C" __attribute__((visibility("hidden"))) int rgk_internal_fail(int code, const char* msg) { return fail(code, "%s", msg); }
-
-// Tuning switches of one scene (nothing here changes a result).  Filled ONCE, in rgk_scene_create, from the environment
-// (RGK_ENTRY_POINTS, RGK_ENTRY_CAP, RGK_LIGHT_ENTRY, RGK_CONST_LIGHT, RGK_SAMPLE_GROUP, RGK_BATCH_PATHS, RGK_WORKSPACE_GB, RGK_DEBUG_BVH,
-// RGK_DEBUG_UTIL); afterwards only rgk_scene_set_tuning changes them -- a round never reads the environment (round 2 did, per
-// round: process-global state under a host that may render from two threads).
+// Tuning switches of one scene (nothing here changes a result).  Filled ONCE, by read_tuning in rgk_scene_create, from the
+// environment (RGK_ENTRY_POINTS, RGK_ENTRY_CAP, RGK_LIGHT_ENTRY, RGK_CONST_LIGHT, RGK_SAMPLE_GROUP, RGK_BATCH_PATHS, RGK_WORKSPACE_GB,
+// RGK_BEAM, RGK_DEBUG_BVH, RGK_DEBUG_UTIL); afterwards only rgk_scene_set_tuning changes them -- a round never reads the environment
+// (round 2 did, per round: process-global state under a host that may render from two threads).  The build switches are read
+// at the same moment, by read_build_options (rgk_commit.h).
 struct RgkTuning {
     bool entry_points = true; // camera rays start at their pixel group's entry nodes (k_entry_points)
     bool entry_cap = true;    // ... capped behind the group's first hits from a frame's second round on
@@ -502,31 +91,6 @@ struct RgkTuning {
                               // entry lists are uncapped (a frame's first round), 2: always, 0: never
     bool debug_bvh = false, debug_util = false;
 };
-
-// The constant-light route's eligibility (rgk.h rgk_scene_info::const_light): does random_light (rgk_device.h) return point
-// light 0, at its own position, for EVERY sample?  One point light of size 0 and no areal light; no -0.0 in the position
-// (light_code's pos + 0 * v would make it +0.0 for some v); and random_light's own two comparisons, in float with its own
-// expressions, select light 0 for the largest `choice.x` the sampler returns, 1 - 2^-24.  Rounding is monotone: choice.x *
-// total_power does not grow when choice.x shrinks, nor does q - intensity * 4 pi when q shrinks, so every smaller sample passes
-// both comparisons too.  (A NaN or infinite power fails them and stays on the per-path route.)
-static uint32_t const_light_eligible(const DevScene& ds, const DevPointLight* pls) {
-    if (ds.n_pointlights != 1 || ds.n_areal != 0) return 0;
-    const DevPointLight& pl = pls[0];
-    if (pl.size != 0.0f) return 0;
-    for (int k = 0; k < 3; k++)
-        if (pl.pos[k] == 0.0f && std::signbit(pl.pos[k])) return 0;
-    const float PI_F = 3.14159265358979323846264338327950288f; // RGK_PI_F
-    volatile float total_power = ds.total_point_power + ds.total_areal_power; // (volatile: each step rounded to float, as on the device)
-    if (total_power <= 0.0f) return 0;
-    const float choice_max = 0x1.fffffep-1f;
-    volatile float q = choice_max * total_power;
-    if (!(q < ds.total_point_power)) return 0;
-    volatile float step = pl.intensity * 4.0f;
-    step = step * PI_F;
-    q = q - step;
-    if (!(q <= 0.0f)) return 0;
-    return 1;
-}
 
 struct rgk_scene {
     int device = 0;
@@ -640,122 +204,167 @@ int ensure_workspace(rgk_scene* s, size_t paths, uint32_t reverse = 0) {
     return 0;
 }
 
-void build_halton(std::vector<DevHaltonDim>& dims, std::vector<uint16_t>& perm) {
-    // Faure permutations: the standard recursive construction the reference uses
-    // (external/halton_sampler.h:574-604), one permutation per prime base.
-    const unsigned max_base = 1619u;
-    std::vector<std::vector<uint16_t>> perms(max_base + 1);
-    for (unsigned k = 1; k <= 3; ++k) { perms[k].resize(k); for (unsigned i = 0; i < k; ++i) perms[k][i] = i; }
-    for (unsigned base = 4; base <= max_base; ++base) {
-        perms[base].resize(base);
-        unsigned b = base / 2;
-        if (base & 1) {
-            for (unsigned i = 0; i + 1 < base; ++i) {
-                uint16_t v = perms[base - 1][i];
-                perms[base][i + (i >= b)] = v + (v >= b);
-            }
-            perms[base][b] = b;
-        } else {
-            for (unsigned i = 0; i < b; ++i) { perms[base][i] = 2 * perms[b][i]; perms[base][b + i] = 2 * perms[b][i] + 1; }
-        }
-    }
-    for (unsigned p = 2; dims.size() < 256; p++) {
-        bool prime = true;
-        for (unsigned d = 2; d * d <= p; d++) if (p % d == 0) { prime = false; break; }
-        if (!prime) continue;
-        DevHaltonDim hd{};
-        hd.base = p;
-        uint64_t bk = p; unsigned k = 1;
-        while (bk * p <= 500) { bk *= p; k++; }  // digits per table lookup in the reference
-        uint64_t tot = bk; unsigned G = 1;
-        while (tot * bk < (1ull << 32)) { tot *= bk; G++; } // lookups per sample
-        hd.digits = k * G;
-        hd.scale = float(0x1.fffffcp-1 / (double)tot);
-        hd.perm_off = (uint32_t)perm.size();
-        if (p > 2) { // exact u32 division by p: q = (t + ((n - t) >> 1)) >> (l - 1), t = mulhi(m, n)
-            unsigned l = 0;
-            while ((1u << l) < p) l++;
-            hd.magic = (uint32_t)(((1ull << 32) * ((1ull << l) - p)) / p + 1);
-            hd.shift = l - 1;
-        }
-        perm.insert(perm.end(), perms[p].begin(), perms[p].end());
-        dims.push_back(hd);
-    }
-}
-
-int validate_desc(const rgk_scene_desc* d) {
-    if (!d) return fail(RGK_ERR_INVALID, "null scene descriptor");
-    if (d->n_triangles == 0 || d->n_vertices == 0) return fail(RGK_ERR_INVALID, "scene has no geometry");
-    if (!d->vertices || !d->normals || !d->tangents || !d->tri_indices || !d->tri_material)
-        return fail(RGK_ERR_INVALID, "null geometry pointer");
-    if (d->n_materials == 0 || !d->materials) return fail(RGK_ERR_INVALID, "scene has no materials");
-    for (uint32_t i = 0; i < d->n_triangles; i++) {
-        for (int k = 0; k < 3; k++)
-            if (d->tri_indices[3 * i + k] >= d->n_vertices) return fail(RGK_ERR_INVALID, "triangle %u: vertex index out of range", i);
-        if (d->tri_material[i] >= d->n_materials) return fail(RGK_ERR_INVALID, "triangle %u: material index out of range", i);
-    }
-    bool ggx = false, bek = false;
-    for (uint32_t i = 0; i < d->n_materials; i++) {
-        const rgk_material& m = d->materials[i];
-        if (m.kind > RGK_BXDF_LTC_GGX_DIFFUSE) return fail(RGK_ERR_INVALID, "material %u: unknown bxdf kind %u", i, m.kind);
-        const int32_t t[3] = {m.tex_diffuse, m.tex_color, m.tex_bump};
-        for (int k = 0; k < 3; k++)
-            if (t[k] >= (int32_t)d->n_textures) return fail(RGK_ERR_INVALID, "material %u: texture index out of range", i);
-        if (m.kind == RGK_BXDF_MIX && (m.mix_m1 < 0 || m.mix_m2 < 0 || m.mix_m1 >= (int32_t)d->n_materials || m.mix_m2 >= (int32_t)d->n_materials))
-            return fail(RGK_ERR_INVALID, "material %u: mix children out of range", i);
-        if (m.kind == RGK_BXDF_LTC_GGX || m.kind == RGK_BXDF_LTC_GGX_DIFFUSE) ggx = true;
-        if (m.kind == RGK_BXDF_LTC_BECKMANN || m.kind == RGK_BXDF_LTC_BECKMANN_DIFFUSE) bek = true;
-    }
-    {   // BxDFMix recurses (bxdf.cpp:235-249); the kernels evaluate a mix of mixes of leaves (two levels) without recursion.
-        // Anything deeper, or a mix that reaches itself, is refused here rather than rendered wrong.
-        std::vector<int> depth(d->n_materials, -1); // -1 unvisited, -2 on the current walk
-        struct Walk {
-            const rgk_scene_desc* d; std::vector<int>& depth;
-            int go(uint32_t i) {
-                if (d->materials[i].kind != RGK_BXDF_MIX) return depth[i] = 0;
-                if (depth[i] == -2) return -1; // cycle
-                if (depth[i] >= 0) return depth[i];
-                depth[i] = -2;
-                const int a = go((uint32_t)d->materials[i].mix_m1), b = go((uint32_t)d->materials[i].mix_m2);
-                if (a < 0 || b < 0) return -1;
-                return depth[i] = 1 + std::max(a, b);
-            }
-        } walk{d, depth};
-        for (uint32_t i = 0; i < d->n_materials; i++) {
-            const int k = walk.go(i);
-            if (k < 0) return fail(RGK_ERR_INVALID, "material %u: mix materials form a cycle", i);
-            if (k > 2) return fail(RGK_ERR_UNSUPPORTED, "material %u: mix nested %d levels deep (at most 2 are evaluated)", i, k);
-        }
-    }
-    if (ggx && !d->ltc_ggx) return fail(RGK_ERR_INVALID, "LTC GGX material without ltc_ggx table");
-    if (bek && !d->ltc_beckmann) return fail(RGK_ERR_INVALID, "LTC Beckmann material without ltc_beckmann table");
-    for (uint32_t i = 0; i < d->n_textures; i++) {
-        const rgk_texture& t = d->textures[i];
-        if (t.kind == RGK_TEX_RGB32F && (!t.texels || t.width == 0 || t.height == 0)) return fail(RGK_ERR_INVALID, "texture %u: empty image", i);
-        if (t.kind == RGK_TEX_RGB8 && (!t.texels8 || !t.lut || t.width == 0 || t.height == 0)) return fail(RGK_ERR_INVALID, "texture %u: empty 8-bit image", i);
-        if (t.kind > RGK_TEX_RGB8) return fail(RGK_ERR_INVALID, "texture %u: unknown kind", i);
-    }
-    for (uint32_t i = 0; i < d->n_areal_lights; i++)
-        for (uint32_t j = d->areal_offsets[i]; j < d->areal_offsets[i + 1]; j++)
-            if (d->areal_tris[j] >= d->n_triangles) return fail(RGK_ERR_INVALID, "areal light %u: triangle out of range", i);
-    if (d->sky_mode == RGK_SKY_ENVMAP && (d->sky_texture < 0 || d->sky_texture >= (int32_t)d->n_textures))
-        return fail(RGK_ERR_INVALID, "sky envmap texture out of range");
-    return 0;
-}
-
-} // namespace
-
-namespace {
 template <typename T>
 int down(T* dst, const DevBuf<T>& b, size_t count) {
     if (hipMemcpy(dst, b.p, count * sizeof(T), hipMemcpyDeviceToHost) != hipSuccess) return fail(RGK_ERR_DEVICE, "hipMemcpy D2H failed");
     return 0;
 }
+
+RgkTuning read_tuning() {
+    auto off = [](const char* name) { const char* e = std::getenv(name); return e && e[0] == '0'; };
+    RgkTuning t;
+    t.entry_points = !off("RGK_ENTRY_POINTS"); t.entry_cap = !off("RGK_ENTRY_CAP"); t.light_entry = !off("RGK_LIGHT_ENTRY");
+    t.const_light = !off("RGK_CONST_LIGHT");
+    if (const char* e = std::getenv("RGK_SAMPLE_GROUP")) t.sample_group = std::min(6, std::max(0, std::atoi(e)));
+    if (const char* e = std::getenv("RGK_BATCH_PATHS")) t.batch_paths = std::max<size_t>(1024, strtoull(e, nullptr, 10));
+    if (const char* e = std::getenv("RGK_WORKSPACE_GB")) t.workspace_gb = atof(e);
+    if (const char* e = std::getenv("RGK_BEAM")) t.beam = std::min(2, std::max(0, std::atoi(e)));
+    t.debug_bvh = std::getenv("RGK_DEBUG_BVH") != nullptr; t.debug_util = std::getenv("RGK_DEBUG_UTIL") != nullptr;
+    return t;
+}
+
+// The per-frame lists (entry nodes, their caps, light-side entries) were made for the old boxes or switches: the next round rebuilds them.
+void invalidate_frame_lists(rgk_scene* s) { s->entry_key = 0; s->entry_n = 0; s->entry_capped = 0; s->lentry_done = 0; }
+
+// Epsilon and the epsilon-padded box of commit_bounds, where the kernels and rgk_scene_get_info read them.
+void set_bounds(rgk_scene* s, const float mn[3], const float mx[3], float eps) {
+    DevScene& ds = s->dev;
+    ds.epsilon = eps;
+    s->info.epsilon = eps;
+    for (int a = 0; a < 3; a++) {
+        ds.bb_min[a] = mn[a] - eps; ds.bb_max[a] = mx[a] + eps;
+        s->info.bbox_min[a] = ds.bb_min[a]; s->info.bbox_max[a] = ds.bb_max[a];
+    }
+}
+
+// What rgk_scene_create knows about the tree once it is built, by either builder.
+struct AccelInfo {
+    uint32_t n_nodes = 0, n_refs = 0, max_depth = 0, max_stack = 0;
+    bool on_device = false; // nodes and leaf records are on the device already
+};
+
+// LBVH on the GPU (rgk_build.hip): the references go up, nodes and leaf-ordered records stay on the device
+int build_accel_device(rgk_scene* s, const std::vector<Prim>& prims, const std::vector<TriIsect>& recs, const float mn[3], const float mx[3], float eps,
+                       const BuildOptions& opt, AccelInfo& acc) {
+    std::vector<RgkBuildPrim> bp(prims.size());
+    for (size_t i = 0; i < prims.size(); i++) {
+        for (int a = 0; a < 3; a++) { bp[i].bmin[a] = prims[i].bmin[a]; bp[i].bmax[a] = prims[i].bmax[a]; }
+        bp[i].tri = prims[i].tri;
+        for (int a = 0; a < 4; a++) bp[i].pb[a] = prims[i].pb[a];
+    }
+    int rc;
+    DevBuf<TriIsect> d_recs;
+    if ((rc = d_recs.upload(recs.data(), recs.size())) || (rc = s->nodes.alloc(prims.size())) || (rc = s->tris.alloc(prims.size())) || (rc = s->leaf_pb.alloc(prims.size()))) return rc;
+    uint32_t levels = 0;
+    const char* err = "";
+    acc.n_refs = (uint32_t)prims.size();
+    rc = rgk_build_bvh4_device(s->stream, bp.data(), acc.n_refs, mn, mx, eps, (uint32_t)opt.max_leaf_dev, opt.lbvh_rotate, opt.lbvh_ploc, opt.lbvh_morton_bits, d_recs.p,
+                               s->nodes.p, s->tris.p, s->leaf_pb.p, &acc.n_nodes, &levels, &err);
+    if (rc) return fail(rc, "device BVH build: %s", err);
+    acc.max_depth = levels;
+    acc.max_stack = 3 * levels; // three pushes per level at most
+    acc.on_device = true;
+    return 0;
+}
+
+#ifndef RGK_BUILD_AUTO_DEVICE_REFS
+#define RGK_BUILD_AUTO_DEVICE_REFS 500000
+#endif
+// Which builder: asked for explicitly, or (RGK_BUILD_AUTO) by size -- from half a million references on, the host's SAH build
+// takes seconds (1.5 s at 1.05 M) where the device build takes 0.15 s and traces within 2 % of it.  The host build's tables
+// stay in `host` until upload_tables.
+int build_accel(rgk_scene* s, uint32_t build_flags, std::vector<Prim>& prims, const std::vector<TriIsect>& recs, const float mn[3], const float mx[3], float eps,
+                const BuildOptions& opt, HostAccel& host, AccelInfo& acc) {
+    if (prims.empty()) return fail(RGK_ERR_INVALID, "every triangle is degenerate");
+    if (prims.size() >= (1u << 25)) return fail(RGK_ERR_UNSUPPORTED, "too many triangles (32-bit byte offsets into the triangle tables: < 2^25)");
+    const bool want_device = (build_flags & RGK_BUILD_DEVICE) || (!(build_flags & RGK_BUILD_HOST_SAH) && prims.size() >= (size_t)RGK_BUILD_AUTO_DEVICE_REFS);
+    if (want_device && prims.size() > (size_t)opt.max_leaf_dev) return build_accel_device(s, prims, recs, mn, mx, eps, opt, acc);
+    if (int rc = build_host_accel(prims, recs, eps, opt, host)) return rc;
+    acc.n_nodes = (uint32_t)host.qnodes.size(); acc.n_refs = (uint32_t)host.leaf_recs.size();
+    acc.max_depth = host.max_depth; acc.max_stack = host.max_stack;
+    return 0;
+}
+
+// Traversal stack: 16 entries per lane in LDS + per-lane overflow in global memory (rgk_kernels.hip RGK_TRACE_DISPATCH)
+int configure_stack(rgk_scene* s, uint32_t max_stack, const BuildOptions& opt) {
+    if (max_stack + 1 + RGK_ENTRY_K > 256) return fail(RGK_ERR_UNSUPPORTED, "BVH needs %u traversal-stack entries (max 256)", max_stack + 1);
+    const int need = (int)max_stack + 1 + RGK_ENTRY_K; // (+ the entry nodes a camera ray starts with)
+    if (!opt.stack_ovf && need <= 32) { s->tcfg.stack = 32; s->tcfg.lds = 32; }
+    else { s->tcfg.stack = 256; s->tcfg.lds = opt.stack_lds; }
+    s->tcfg.ovf = nullptr;
+    if (s->tcfg.lds < s->tcfg.stack) {
+        const size_t per_lane = (size_t)std::max(need - std::min(s->tcfg.lds, 8), 1); // (k_trace_camera_beam keeps 8 entries in LDS)
+        if (int rc = s->ovf.alloc((size_t)rgk_trace_grid(s->tcfg.lds) * RGK_TRACE_BLOCK * per_lane)) return rc;
+        s->tcfg.ovf = s->ovf.p;
+    }
+    return 0;
+}
+
+// Keeps what rgk_scene_refit needs of the descriptor, then uploads every table; the host build's tree goes up here too.
+int upload_tables(rgk_scene* s, const rgk_scene_desc* d, const AccelInfo& acc, const HostAccel& host, const ShadingTables& sh) {
+    const uint32_t nt = d->n_triangles;
+    s->n_textures = d->n_textures; s->n_materials = d->n_materials;
+    s->n_vertices = d->n_vertices; s->n_triangles = nt; s->n_refs = acc.n_refs; s->n_nodes = acc.n_nodes;
+    s->h_idx.assign(d->tri_indices, d->tri_indices + 3 * (size_t)nt);
+    s->h_tri_mat.assign(d->tri_material, d->tri_material + nt);
+    s->h_mats.assign(d->materials, d->materials + d->n_materials);
+    s->h_normals.assign(d->normals, d->normals + 3 * (size_t)d->n_vertices);
+    if (d->n_areal_lights) {
+        s->h_areal_off.assign(d->areal_offsets, d->areal_offsets + d->n_areal_lights + 1);
+        s->h_areal_tris.assign(d->areal_tris, d->areal_tris + d->areal_offsets[d->n_areal_lights]);
+    }
+    int rc;
+    if ((rc = s->d_idx.upload(s->h_idx.data(), s->h_idx.size()))) return rc;
+    if ((rc = s->texrefs.upload(sh.tex.refs.data(), sh.tex.refs.size()))) return rc;
+    if (!acc.on_device && ((rc = s->nodes.upload(host.qnodes.data(), host.qnodes.size())) || (rc = s->tris.upload(host.leaf_recs.data(), host.leaf_recs.size())) ||
+                           (rc = s->leaf_pb.upload(host.leaf_pb.data(), host.leaf_pb.size()))))
+        return rc;
+    if ((rc = s->tri_shade.upload(sh.tri_shade.data(), sh.tri_shade.size())) || (rc = s->materials.upload(sh.materials.data(), sh.materials.size())) ||
+        (rc = s->texels.upload(sh.tex.texels.data(), sh.tex.texels.size())) || (rc = s->texels8.upload(sh.tex.texels8.data(), sh.tex.texels8.size())) ||
+        (rc = s->luts.upload(sh.tex.luts.data(), sh.tex.luts.size())) || (rc = s->pointlights.upload(sh.pointlights.data(), sh.pointlights.size())) ||
+        (rc = s->areal.upload(sh.areal.data(), sh.areal.size())) || (rc = s->areal_tris.upload(sh.areal_tris.data(), sh.areal_tris.size())) ||
+        (rc = s->hdims.upload(sh.hdims.data(), sh.hdims.size())) || (rc = s->hperm.upload(sh.hperm.data(), sh.hperm.size())) || (rc = s->ltc.upload(sh.ltc.data(), sh.ltc.size())))
+        return rc;
+    return 0;
+}
+
+// DevScene (host copy and device copy) and the rest of rgk_scene_info, once every table is on the device.
+int fill_dev_scene(rgk_scene* s, const rgk_scene_desc* d, const AccelInfo& acc, const ShadingTables& sh, const BuildOptions& opt) {
+    DevScene& ds = s->dev;
+    ds.nodes = s->nodes.p;
+    ds.walk_q = opt.walk_q;
+    ds.tris = s->tris.p; ds.tri_shade = s->tri_shade.p;
+    ds.materials = s->materials.p; ds.texels = s->texels.p; ds.texels8 = s->texels8.p; ds.luts = s->luts.p; ds.n_lut_floats = (uint32_t)sh.tex.luts.size(); ds.n_materials = (uint32_t)sh.materials.size();
+    ds.pointlights = s->pointlights.p; ds.areal = s->areal.p; ds.areal_tris = s->areal_tris.p;
+    ds.ltc = s->ltc.p; ds.hdims = s->hdims.p; ds.hperm = s->hperm.p;
+    ds.n_pointlights = (uint32_t)sh.pointlights.size(); ds.n_areal = (uint32_t)sh.areal.size();
+    ds.total_point_power = sh.total_point_power; ds.total_areal_power = sh.total_areal_power;
+    if (!sh.pointlights.empty()) {
+        const DevPointLight& l0 = sh.pointlights[0];
+        s->h_light0 = l0;
+        for (int k = 0; k < 3; k++) { ds.cl_pos[k] = l0.pos[k]; ds.cl_color[k] = l0.color[k]; }
+        ds.cl_intensity = l0.intensity;
+    }
+    ds.has_texcoords = d->texcoords ? 1u : 0u;
+    ds.sky_mode = d->sky_mode;
+    for (int k = 0; k < 3; k++) ds.sky_color[k] = d->sky_color[k];
+    ds.sky_intensity = d->sky_intensity; ds.sky_rotate = d->sky_rotate; ds.sky_tex = tex_ref(sh.tex.refs, d->sky_mode == RGK_SKY_ENVMAP ? d->sky_texture : -1);
+    if (int rc = s->self.alloc(1)) return rc;
+    ds.self = s->self.p;
+    if (hipMemcpy(s->self.p, &ds, sizeof(DevScene), hipMemcpyHostToDevice) != hipSuccess) return fail(RGK_ERR_DEVICE, "hipMemcpy(DevScene)");
+
+    rgk_scene_info& inf = s->info;
+    inf.total_areal_power = sh.total_areal_power; inf.total_point_power = sh.total_point_power;
+    inf.n_nodes = acc.n_nodes; inf.node_bytes = RGK_NODE_BYTES; inf.tri_bytes = RGK_TRI_BYTES;
+    inf.max_depth = acc.max_depth; inf.n_leaf_refs = acc.n_refs;
+    inf.n_float_textures = sh.tex.n_float; inf.n_palettized_textures = sh.tex.n_palettized;
+    inf.const_light = const_light_eligible(ds, &s->h_light0);
+    return 0;
+}
+
 } // namespace
 
 extern "C" {
-
-const char* rgk_last_error(void) { return g_err.c_str(); }
 
 int rgk_device_count(void) {
     int n = 0;
@@ -763,81 +372,8 @@ int rgk_device_count(void) {
     return n;
 }
 
-// RGK_DEBUG_DESC=1: one line per table of the descriptor with an FNV-1a digest of its bytes, on stderr -- lets a host binding
-// be checked against a known-good one ("did my flattening hand over the same scene?") without a debugger.
-static void debug_desc(const rgk_scene_desc* d) {
-    auto h = [](const void* p, size_t n) { uint64_t x = 1469598103934665603ull; const unsigned char* b = (const unsigned char*)p; for (size_t i = 0; p && i < n; i++) { x ^= b[i]; x *= 1099511628211ull; } return (unsigned long long)x; };
-    std::fprintf(stderr, "[rgk desc] vertices %u %016llx normals %016llx tangents %016llx texcoords %016llx\n", d->n_vertices, h(d->vertices, 12ull * d->n_vertices),
-                 h(d->normals, 12ull * d->n_vertices), h(d->tangents, 12ull * d->n_vertices), h(d->texcoords, 8ull * d->n_vertices));
-    std::fprintf(stderr, "[rgk desc] triangles %u idx %016llx mat %016llx\n", d->n_triangles, h(d->tri_indices, 12ull * d->n_triangles), h(d->tri_material, 4ull * d->n_triangles));
-    for (uint32_t i = 0; i < d->n_materials; i++) {
-        const rgk_material& m = d->materials[i];
-        std::fprintf(stderr, "[rgk desc] material %u kind %u flags %u emission %g %g %g rough %.9g ior %.9g amount %.9g tex %d %d %d mix %d %d\n", i, m.kind, m.flags, m.emission[0], m.emission[1],
-                     m.emission[2], m.roughness, m.ior, m.amount, m.tex_diffuse, m.tex_color, m.tex_bump, m.mix_m1, m.mix_m2);
-    }
-    for (uint32_t i = 0; i < d->n_textures; i++) {
-        const rgk_texture& t = d->textures[i];
-        const size_t n = (size_t)t.width * t.height;
-        std::fprintf(stderr, "[rgk desc] texture %u kind %u %ux%u color %.9g %.9g %.9g texels %016llx\n", i, t.kind, t.width, t.height, t.color[0], t.color[1], t.color[2],
-                     t.kind == RGK_TEX_RGB32F ? h(t.texels, 12 * n) : (t.kind == RGK_TEX_RGB8 ? h(t.texels8, 3 * n) ^ h(t.lut, 1024) : 0ull));
-    }
-    std::fprintf(stderr, "[rgk desc] pointlights %u %016llx areal %u offsets %016llx tris %016llx\n", d->n_pointlights, h(d->pointlights, sizeof(rgk_pointlight) * (size_t)d->n_pointlights),
-                 d->n_areal_lights, h(d->areal_offsets, 4ull * (d->n_areal_lights + 1)), h(d->areal_tris, d->n_areal_lights ? 4ull * d->areal_offsets[d->n_areal_lights] : 0));
-    std::fprintf(stderr, "[rgk desc] sky mode %u color %.9g %.9g %.9g intensity %.9g rotate %.9g tex %d ltc %016llx %016llx\n", d->sky_mode, d->sky_color[0], d->sky_color[1], d->sky_color[2],
-                 d->sky_intensity, d->sky_rotate, d->sky_texture, h(d->ltc_ggx, 4096 * 20), h(d->ltc_beckmann, 4096 * 20));
-}
-
 #ifndef RGK_SAMPLE_GROUP_DEFAULT
 #define RGK_SAMPLE_GROUP_DEFAULT 3 // 8 samples of a pixel side by side: swept 0..6 on the Sponza proxy (154.2, -, 149.6, 148.4, 148.1, 150.3, 150.0 ms per round)
-#endif
-// Scene::Commit's areal-light tables (src/scene.cpp:323-344): per emissive object its triangles sorted by area (descending), the
-// total area, power = area * (r + g + b).  Used by rgk_scene_create and, for moved vertices, by rgk_scene_refit.
-static void build_areal_tables(const float* vertices, const float* normals, const uint32_t* tri_indices, const uint32_t* tri_material, const rgk_material* materials,
-                               uint32_t n_areal, const uint32_t* areal_offsets, const uint32_t* areal_tris, std::vector<DevArealLight>& als,
-                               std::vector<DevArealTri>& ats, float& total_areal) {
-    auto vert = [&](uint32_t i) { return V3{vertices[3 * i], vertices[3 * i + 1], vertices[3 * i + 2]}; };
-    als.clear(); ats.clear(); total_areal = 0.f;
-    for (uint32_t i = 0; i < n_areal; i++) {
-        uint32_t b = areal_offsets[i], e = areal_offsets[i + 1];
-        if (e <= b) continue;
-        std::vector<std::pair<float, uint32_t>> twa;
-        float total_area = 0.f;
-        for (uint32_t j = b; j < e; j++) {
-            uint32_t t = areal_tris[j];
-            V3 A = vert(tri_indices[3 * t]), B = vert(tri_indices[3 * t + 1]), C = vert(tri_indices[3 * t + 2]);
-            V3 c = crossv(sub(A, B), sub(C, B)); // Triangle::GetArea primitives.cpp:38-45
-            float area = 0.5f * std::sqrt(dotv(c, c));
-            twa.push_back({area, t});
-            total_area += area;
-        }
-        const rgk_material& m0 = materials[tri_material[twa[0].second]];
-        std::sort(twa.rbegin(), twa.rend()); // descending by (area, index)
-        DevArealLight al{};
-        al.total_area = total_area;
-        for (int k = 0; k < 3; k++) al.emission[k] = m0.emission[k];
-        al.power = total_area * (m0.emission[0] + m0.emission[1] + m0.emission[2]);
-        al.first = (uint32_t)ats.size();
-        al.count = (uint32_t)twa.size();
-        for (auto& p : twa) {
-            DevArealTri at{};
-            at.area = p.first; at.tri = p.second; at.light = (uint32_t)als.size();
-            uint32_t ia = tri_indices[3 * p.second], ib = tri_indices[3 * p.second + 1], ic = tri_indices[3 * p.second + 2];
-            for (int k = 0; k < 3; k++) {
-                at.a[k] = vertices[3 * ia + k]; at.b[k] = vertices[3 * ib + k]; at.c[k] = vertices[3 * ic + k];
-                at.normal_a[k] = normals[3 * ia + k];
-            }
-            ats.push_back(at);
-        }
-        total_areal += al.power;
-        als.push_back(al);
-    }
-}
-
-#ifndef RGK_BUILD_AUTO_DEVICE_REFS
-#define RGK_BUILD_AUTO_DEVICE_REFS 500000
-#endif
-#ifndef RGK_LBVH_ROTATE_PASSES
-#define RGK_LBVH_ROTATE_PASSES 4
 #endif
 int rgk_scene_create(const rgk_scene_desc* d, int device, rgk_scene** out) {
     if (!out) return fail(RGK_ERR_INVALID, "null output pointer");
@@ -853,393 +389,31 @@ int rgk_scene_create(const rgk_scene_desc* d, int device, rgk_scene** out) {
     s->device = device;
     struct Guard { rgk_scene* s; ~Guard() { delete s; } } guard{s};
     HIPCHK(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-    {
-        auto off = [](const char* name) { const char* e = std::getenv(name); return e && e[0] == '0'; };
-        RgkTuning& t = s->tune;
-        t.entry_points = !off("RGK_ENTRY_POINTS"); t.entry_cap = !off("RGK_ENTRY_CAP"); t.light_entry = !off("RGK_LIGHT_ENTRY");
-        t.const_light = !off("RGK_CONST_LIGHT");
-        if (const char* e = std::getenv("RGK_SAMPLE_GROUP")) t.sample_group = std::min(6, std::max(0, std::atoi(e)));
-        if (const char* e = std::getenv("RGK_BATCH_PATHS")) t.batch_paths = std::max<size_t>(1024, strtoull(e, nullptr, 10));
-        if (const char* e = std::getenv("RGK_WORKSPACE_GB")) t.workspace_gb = atof(e);
-        if (const char* e = std::getenv("RGK_BEAM")) t.beam = std::min(2, std::max(0, std::atoi(e)));
-        t.debug_bvh = std::getenv("RGK_DEBUG_BVH") != nullptr; t.debug_util = std::getenv("RGK_DEBUG_UTIL") != nullptr;
-    }
+    s->tune = read_tuning();
+    const BuildOptions opt = read_build_options();
 
-    const uint32_t nt = d->n_triangles;
-    auto vert = [&](uint32_t i) { return V3{d->vertices[3 * i], d->vertices[3 * i + 1], d->vertices[3 * i + 2]}; };
-
-    // ---- Commit: bounds, epsilon (scene.cpp:364-395)
-    float mn[3], mx[3];
-    for (int a = 0; a < 3; a++) { mn[a] = std::numeric_limits<float>::infinity(); mx[a] = -mn[a]; }
-    for (uint32_t i = 0; i < nt; i++)
-        for (int k = 0; k < 3; k++) {
-            V3 v = vert(d->tri_indices[3 * i + k]);
-            for (int a = 0; a < 3; a++) { float c = comp(v, a); if (c < mn[a]) mn[a] = c; if (c > mx[a]) mx[a] = c; }
-        }
-    float xs = mx[0] - mn[0], ys = mx[1] - mn[1], zs = mx[2] - mn[2];
-    float diameter = std::sqrt(xs * xs + ys * ys + zs * zs);
-    float eps = 0.00001f * diameter;
-    if (!(eps == eps) || !(diameter < std::numeric_limits<float>::infinity())) return fail(RGK_ERR_INVALID, "non-finite vertex coordinates");
-    DevScene& ds = s->dev;
-    ds.epsilon = eps;
-    for (int a = 0; a < 3; a++) { ds.bb_min[a] = mn[a] - eps; ds.bb_max[a] = mx[a] + eps; }
-
-    // ---- planes + intersection records (primitives.cpp:24-36, 75-166)
-    std::vector<TriIsect> recs(nt);
+    // ---- Commit: bounds, epsilon; planes, intersection records and the build's references
+    float mn[3], mx[3], eps;
+    if ((rc = commit_bounds(d->vertices, d->tri_indices, d->n_triangles, mn, mx, &eps))) return rc;
+    set_bounds(s, mn, mx, eps);
+    std::vector<TriIsect> recs;
     std::vector<Prim> prims;
-    prims.reserve(nt);
-    RefSplitter splitter;
-    {   // RGK_BVH_SPLIT = longest box side, as a fraction of the scene diagonal, above which a triangle is pre-split
-        const char* e = std::getenv("RGK_BVH_SPLIT");
-        const float f = e ? (float)std::atof(e) : 0.1f; // swept on the Sponza proxy: 0.08..0.15 best (-7 % node visits); finer splits deepen the tree
-        splitter.lmax = f > 0.f ? f * (eps * 1e5f) : 0.f; // eps = 1e-5 * diagonal
-        splitter.budget = (size_t)nt; // at most 2x references
-        splitter.out = &prims;
-    }
-    for (uint32_t i = 0; i < nt; i++) {
-        V3 v0 = vert(d->tri_indices[3 * i]), v1 = vert(d->tri_indices[3 * i + 1]), v2 = vert(d->tri_indices[3 * i + 2]);
-        V3 d0 = sub(v1, v0), d1 = sub(v2, v0);
-        V3 n = normv(crossv(d1, d0));
-        float dd = -dotv(n, v0);
-        TriIsect& r = recs[i];
-        r.n[0] = n.x; r.n[1] = n.y; r.n[2] = n.z; r.d = dd;
-        int i1, i2;
-        float ax = std::fabs(n.x), ay = std::fabs(n.y), az = std::fabs(n.z);
-        if (ax > ay && ax > az) { i1 = 1; i2 = 2; }
-        else if (ay > az) { i1 = 0; i2 = 2; }
-        else { i1 = 0; i2 = 1; }
-        r.v0a = comp(v0, i1); r.v0b = comp(v0, i2);
-        r.q1x = comp(v1, i1) - comp(v0, i1); r.q1y = comp(v1, i2) - comp(v0, i2);
-        r.q2x = comp(v2, i1) - comp(v0, i1); r.q2y = comp(v2, i2) - comp(v0, i2);
-        r.axes = (uint32_t)i1 | ((uint32_t)i2 << 2);
-        r.tri = i;
-        if (n.x == n.x && n.y == n.y && n.z == n.z) { // a NaN plane can never be hit (primitives.cpp:90)
-            Prim p;
-            for (int a = 0; a < 3; a++) {
-                p.bmin[a] = std::min(comp(v0, a), std::min(comp(v1, a), comp(v2, a)));
-                p.bmax[a] = std::max(comp(v0, a), std::max(comp(v1, a), comp(v2, a)));
-                p.c[a] = 0.5f * (p.bmin[a] + p.bmax[a]);
-            }
-            p.tri = i;
-            p.pb[0] = 0.f; p.pb[1] = 1.f; p.pb[2] = 0.f; p.pb[3] = 1.f;
-            if (splitter.lmax > 0.f) {
-                std::vector<RefSplitter::P3> poly(3);
-                for (int a = 0; a < 3; a++) { poly[0].x[a] = comp(v0, a); poly[1].x[a] = comp(v1, a); poly[2].x[a] = comp(v2, a); }
-                for (int c = 0; c < 3; c++) for (int a = 0; a < 3; a++) splitter.tv[c][a] = poly[c].x[a];
-                splitter.emit(poly, p.bmin, p.bmax, i, 0);
-            } else {
-                p.ref = (uint32_t)prims.size();
-                prims.push_back(p);
-            }
-        }
-    }
-    // ---- accelerator
-    if (prims.empty()) return fail(RGK_ERR_INVALID, "every triangle is degenerate");
-    if (prims.size() >= (1u << 25)) return fail(RGK_ERR_UNSUPPORTED, "too many triangles (32-bit byte offsets into the triangle tables: < 2^25)");
-    std::vector<QNode> qnodes;
-    std::vector<TriIsect> leaf_recs;
-    std::vector<float4> leaf_pb; // per leaf reference: its piece of the triangle in the triangle's own coordinates (Prim::pb), for rgk_scene_refit
-    std::vector<uint32_t> ref_tri(prims.size());
-    std::vector<float4> ref_pb(prims.size());
-    for (const Prim& p : prims) { ref_tri[p.ref] = p.tri; ref_pb[p.ref] = make_float4(p.pb[0], p.pb[1], p.pb[2], p.pb[3]); }
-    uint32_t max_depth = 0, max_stack = 0, n_nodes = 0, n_refs = (uint32_t)prims.size();
-    bool on_device = false;
-    // leaves of the device build: at most 2 references (Morton-adjacent triangles make loose leaves: with 4, a ray tests twice the
-    // triangles the host tree makes it test -- measured with 1 / 2 / 3 / 4 on the 1.05 M-triangle scene, closest-hit + shadow ms of
-    // a round: 7.69 / 7.48 / 7.59 / 8.10, host SAH 7.36: tools/gpu_lbvh_rotate_sweep.py)
-    int MAX_LEAF_DEV = 2;
-    if (const char* e = std::getenv("RGK_BVH_MAXLEAF_DEV")) MAX_LEAF_DEV = std::min(16, std::max(1, std::atoi(e)));
-    // which builder: asked for explicitly, or (RGK_BUILD_AUTO) by size -- from half a million references on, the host's SAH build
-    // takes seconds (1.5 s at 1.05 M) where the device build takes 0.15 s and traces within 2 % of it
-    const bool want_device = (d->build_flags & RGK_BUILD_DEVICE) || (!(d->build_flags & RGK_BUILD_HOST_SAH) && prims.size() >= (size_t)RGK_BUILD_AUTO_DEVICE_REFS);
-    if (want_device && prims.size() > (size_t)MAX_LEAF_DEV) {
-        // LBVH on the GPU (rgk_build.hip): the references go up, nodes and leaf-ordered records stay on the device
-        std::vector<RgkBuildPrim> bp(prims.size());
-        for (size_t i = 0; i < prims.size(); i++) {
-            for (int a = 0; a < 3; a++) { bp[i].bmin[a] = prims[i].bmin[a]; bp[i].bmax[a] = prims[i].bmax[a]; }
-            bp[i].tri = prims[i].tri;
-            for (int a = 0; a < 4; a++) bp[i].pb[a] = prims[i].pb[a];
-        }
-        DevBuf<TriIsect> d_recs;
-        if ((rc = d_recs.upload(recs.data(), recs.size())) || (rc = s->nodes.alloc(prims.size())) || (rc = s->tris.alloc(prims.size())) || (rc = s->leaf_pb.alloc(prims.size()))) return rc;
-        uint32_t levels = 0;
-        const char* err = "";
-        const char* rot = std::getenv("RGK_LBVH_ROTATE"); // passes of the rotation step; 0: the plain LBVH (for comparisons)
-        rc = rgk_build_bvh4_device(s->stream, bp.data(), n_refs, mn, mx, eps, (uint32_t)MAX_LEAF_DEV, rot ? std::max(0, std::min(32, std::atoi(rot))) : RGK_LBVH_ROTATE_PASSES, d_recs.p, s->nodes.p, s->tris.p, s->leaf_pb.p, &n_nodes, &levels, &err);
-        if (rc) return fail(rc, "device BVH build: %s", err);
-        max_depth = levels;
-        max_stack = 3 * levels; // three pushes per level at most
-        on_device = true;
-    } else {
-        std::vector<BvhNode> nodes;
-        BvhBuilder bb(prims, eps);
-        Box rootbox;
-        bb.nodes.reserve(prims.size());
-        bb.nodes.emplace_back(); // node 0 = root, filled below if the whole scene is one leaf
-        int code;
-        if (prims.size() <= (size_t)bb.MAX_LEAF) {
-            code = bb.build(0, prims.size(), 1, rootbox);
-            BvhNode& r = bb.nodes[0];
-            for (int a = 0; a < 3; a++) {
-                r.lmin[a] = rootbox.mn[a]; r.lmax[a] = rootbox.mx[a];
-                r.rmin[a] = std::numeric_limits<float>::infinity(); r.rmax[a] = -std::numeric_limits<float>::infinity();
-            }
-            r.left = code; r.right = code; r.pad[0] = r.pad[1] = 0;
-        } else {
-            bb.nodes.pop_back();
-            code = bb.build(0, prims.size(), 0, rootbox);
-            if (code != 0) return fail(RGK_ERR_DEVICE, "internal: BVH root is not node 0");
-            const char* e = std::getenv("RGK_BVH_OPT"); // reinsertion rounds (0 = off)
-            optimise_bvh2(bb.nodes, bb.order, e ? std::atoi(e) : 8, 0.5f);
-        }
-        nodes.swap(bb.nodes);
-        leaf_recs.reserve(bb.order.size());
-        leaf_pb.reserve(bb.order.size());
-        for (uint32_t r : bb.order) { leaf_recs.push_back(recs[ref_tri[r]]); leaf_pb.push_back(ref_pb[r]); }
-        QbvhBuilder qb(nodes);
-        qb.out.reserve(nodes.size() / 2 + 1);
-        if (qb.collapse(0, 0, 0) != 0) return fail(RGK_ERR_DEVICE, "internal: QBVH root is not node 0");
-        qnodes.swap(qb.out);
-        max_depth = qb.max_depth; max_stack = qb.max_stack; n_nodes = (uint32_t)qnodes.size(); n_refs = (uint32_t)leaf_recs.size();
-    }
-    if (max_stack + 1 + RGK_ENTRY_K > 256) return fail(RGK_ERR_UNSUPPORTED, "BVH needs %u traversal-stack entries (max 256)", max_stack + 1);
-    {   // traversal stack: 16 entries per lane in LDS + per-lane overflow in global memory (rgk_kernels.hip RGK_TRACE_DISPATCH)
-        const int need = (int)max_stack + 1 + RGK_ENTRY_K; // (+ the entry nodes a camera ray starts with)
-        const char* e = std::getenv("RGK_STACK_OVF");
-        const char* l = std::getenv("RGK_STACK_LDS");
-        if (e && e[0] == '0' && need <= 32) { s->tcfg.stack = 32; s->tcfg.lds = 32; }
-        else { s->tcfg.stack = 256; s->tcfg.lds = (l && std::atoi(l) == 32) ? 32 : 16; }
-        s->tcfg.ovf = nullptr;
-        if (s->tcfg.lds < s->tcfg.stack) {
-            const size_t per_lane = (size_t)std::max(need - std::min(s->tcfg.lds, 8), 1); // (k_trace_camera_beam keeps 8 entries in LDS)
-            if ((rc = s->ovf.alloc((size_t)rgk_trace_grid(s->tcfg.lds) * RGK_TRACE_BLOCK * per_lane))) return rc;
-            s->tcfg.ovf = s->ovf.p;
-        }
-    }
+    commit_triangles(d->vertices, d->tri_indices, d->n_triangles, split_threshold(opt, eps), recs, prims);
 
-    // ---- shading arrays
-    std::vector<TriShade> tsh(nt);
-    for (uint32_t i = 0; i < nt; i++) {
-        TriShade& t = tsh[i];
-        std::memset(&t, 0, sizeof(t));
-        const uint32_t v[3] = {d->tri_indices[3 * i], d->tri_indices[3 * i + 1], d->tri_indices[3 * i + 2]};
-        float uvs[6];
-        for (int k = 0; k < 3; k++) {
-            for (int a = 0; a < 3; a++) { t.q[k][a] = d->normals[3 * v[k] + a]; t.q[3 + k][a] = d->tangents[3 * v[k] + a]; }
-            uvs[2 * k] = d->texcoords ? d->texcoords[2 * v[k]] : 0.f;
-            uvs[2 * k + 1] = d->texcoords ? d->texcoords[2 * v[k] + 1] : 0.f;
-        }
-        for (int k = 0; k < 6; k++) t.q[k][3] = uvs[k]; // uvA.x uvA.y uvB.x uvB.y uvC.x uvC.y
-        t.mat = d->tri_material[i];
-    }
-    // textures: image texels into one float4 pool (float textures) or one dword pool + byte -> float tables (8-bit ones);
-    // a TexRef per (material, slot)
-    std::vector<float4> pool;
-    std::vector<uint32_t> pool8;
-    std::vector<float> luts;
-    std::vector<TexRef> trefs(d->n_textures);
-    // A float texture whose channel values are at most 256 distinct floats is what a loader leaves that decodes an 8-bit
-    // file to floats and keeps only those (the reference: Color(byte / 255).gammaDecode(2.2) per channel,
-    // src/texture.cpp:203,252-254, every FileTexture it holds).  Such a texture is stored as bytes + the table of its values --
-    // bit-identical by construction (the table holds the very floats), a quarter of the texel traffic, and the table sits in LDS.
-    // Textures share a table while the union of their value sets fits 256 entries (one table for all of Sponza's 17 images).
-    struct Palette { std::vector<uint32_t> vals; bool fixed; uint32_t lut_off; }; // sorted bit patterns; fixed: a caller-supplied table
-    std::vector<Palette> palettes;
-    std::vector<int> tex_palette(d->n_textures, -1);
-    uint32_t n_float_tex = 0, n_palettized = 0;
-    auto bits_of = [](float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; };
-    for (uint32_t i = 0; i < d->n_textures; i++) { // caller-supplied tables first: a float texture whose values all occur in one shares it
-        const rgk_texture& t = d->textures[i];
-        if (t.kind != RGK_TEX_RGB8) continue;
-        bool have = false;
-        for (const Palette& p : palettes) if (std::memcmp(&luts[p.lut_off], t.lut, 256 * sizeof(float)) == 0) { have = true; break; }
-        if (have) continue;
-        Palette p; p.fixed = true; p.lut_off = (uint32_t)luts.size();
-        luts.insert(luts.end(), t.lut, t.lut + 256);
-        for (int k = 0; k < 256; k++) p.vals.push_back(bits_of(t.lut[k]));
-        std::sort(p.vals.begin(), p.vals.end());
-        p.vals.erase(std::unique(p.vals.begin(), p.vals.end()), p.vals.end());
-        palettes.push_back(std::move(p));
-    }
-    if (!(d->build_flags & RGK_BUILD_KEEP_FLOAT_TEXTURES))
-        for (uint32_t i = 0; i < d->n_textures; i++) {
-            const rgk_texture& t = d->textures[i];
-            if (t.kind != RGK_TEX_RGB32F || t.width > 65535 || t.height > 65535) continue;
-            // distinct channel values, giving up at the 257th (open addressing, 1024 slots)
-            std::vector<uint32_t> slots(1024, 0u);
-            std::vector<uint8_t> used(1024, 0);
-            std::vector<uint32_t> vals;
-            const size_t n = (size_t)3 * t.width * t.height;
-            bool ok = true;
-            for (size_t k = 0; k < n && ok; k++) {
-                const uint32_t u = bits_of(t.texels[k]);
-                uint32_t h = (u * 2654435761u) >> 22;
-                while (used[h] && slots[h] != u) h = (h + 1) & 1023u;
-                if (!used[h]) { used[h] = 1; slots[h] = u; vals.push_back(u); if (vals.size() > 256) ok = false; }
-            }
-            if (!ok) continue;
-            std::sort(vals.begin(), vals.end());
-            int pick = -1;
-            for (size_t p = 0; p < palettes.size() && pick < 0; p++) // all of it already in a table?
-                if (std::includes(palettes[p].vals.begin(), palettes[p].vals.end(), vals.begin(), vals.end())) pick = (int)p;
-            for (size_t p = 0; p < palettes.size() && pick < 0; p++) { // a table of this scene's that can take the new values?
-                if (palettes[p].fixed) continue;
-                std::vector<uint32_t> u;
-                std::set_union(palettes[p].vals.begin(), palettes[p].vals.end(), vals.begin(), vals.end(), std::back_inserter(u));
-                if (u.size() <= 256) { palettes[p].vals.swap(u); pick = (int)p; }
-            }
-            if (pick < 0) { Palette p; p.fixed = false; p.lut_off = 0; p.vals = vals; palettes.push_back(std::move(p)); pick = (int)palettes.size() - 1; }
-            tex_palette[i] = pick;
-        }
-    for (Palette& p : palettes) // this scene's own tables: the sorted values, padded with zeros
-        if (!p.fixed) {
-            p.lut_off = (uint32_t)luts.size();
-            for (size_t k = 0; k < 256; k++) { float f = 0.f; if (k < p.vals.size()) std::memcpy(&f, &p.vals[k], 4); luts.push_back(f); }
-        }
-    for (uint32_t i = 0; i < d->n_textures; i++) {
-        const rgk_texture& t = d->textures[i];
-        TexRef& o = trefs[i];
-        o.kind = t.kind; o.a = o.b = o.c = 0;
-        if (t.kind == RGK_TEX_SOLID) {
-            std::memcpy(&o.a, &t.color[0], 4); std::memcpy(&o.b, &t.color[1], 4); std::memcpy(&o.c, &t.color[2], 4);
-        } else if (t.kind == RGK_TEX_RGB8 || tex_palette[i] >= 0) {
-            if (t.width > 65535 || t.height > 65535) return fail(RGK_ERR_UNSUPPORTED, "texture %u larger than 65535 texels on a side", i);
-            const size_t n = (size_t)t.width * t.height;
-            // byte texels lie in tiles of 8 x 4 (one 128-byte line; rgk_device.h tex_row / tex_col), the image padded up to whole tiles
-            const size_t tiles_x = ((size_t)t.width + 7) / 8, tiles_y = ((size_t)t.height + 3) / 4, n_padded = RGK_TEX_TILED ? tiles_x * tiles_y * 32 : n;
-            if (pool8.size() + n_padded >= (1ull << 30)) return fail(RGK_ERR_UNSUPPORTED, "8-bit texel pool exceeds 2^30 texels"); // 32-bit byte offsets
-            o.kind = RGK_TEX_RGB8;
-            o.a = t.width | (t.height << 16);
-            while (pool8.size() % 32) pool8.push_back(0u); // a tile = a line: the pool itself is 128-byte aligned
-            o.b = (uint32_t)pool8.size();
-            const size_t pool_at = pool8.size();
-            pool8.resize(pool_at + n_padded, 0u);
-            auto put = [&](size_t k, uint32_t w) { // texel k = y * width + x  ->  its place in the tiled order
-                const size_t x = k % t.width, y = k / t.width;
-                pool8[pool_at + (RGK_TEX_TILED ? ((y >> 2) * tiles_x + (x >> 3)) * 32 + ((y & 3) << 3) + (x & 7) : k)] = w;
-            };
-            if (t.kind == RGK_TEX_RGB8) {
-                for (const Palette& p : palettes) if (p.fixed && std::memcmp(&luts[p.lut_off], t.lut, 256 * sizeof(float)) == 0) { o.c = p.lut_off; break; }
-                for (size_t k = 0; k < n; k++)
-                    put(k, (uint32_t)t.texels8[3 * k] | ((uint32_t)t.texels8[3 * k + 1] << 8) | ((uint32_t)t.texels8[3 * k + 2] << 16));
-            } else { // a float texture with few distinct values: its texels as indices into the table (the first entry holding the value)
-                n_float_tex++; n_palettized++;
-                const Palette& p = palettes[(size_t)tex_palette[i]];
-                o.c = p.lut_off;
-                std::vector<std::pair<uint32_t, uint8_t>> idx; // (bit pattern, table index), sorted by pattern
-                for (int k = 255; k >= 0; k--) idx.push_back({bits_of(luts[p.lut_off + (size_t)k]), (uint8_t)k});
-                std::stable_sort(idx.begin(), idx.end(), [](const std::pair<uint32_t, uint8_t>& a, const std::pair<uint32_t, uint8_t>& b) { return a.first < b.first || (a.first == b.first && a.second < b.second); });
-                auto index_of = [&](float f) -> uint32_t {
-                    const uint32_t u = bits_of(f);
-                    auto it = std::lower_bound(idx.begin(), idx.end(), std::make_pair(u, (uint8_t)0));
-                    return it->second; // present by construction
-                };
-                for (size_t k = 0; k < n; k++)
-                    put(k, index_of(t.texels[3 * k]) | (index_of(t.texels[3 * k + 1]) << 8) | (index_of(t.texels[3 * k + 2]) << 16));
-            }
-        } else {
-            n_float_tex++;
-            if (t.width > 65535 || t.height > 65535) return fail(RGK_ERR_UNSUPPORTED, "texture %u larger than 65535 texels on a side", i);
-            const size_t n = (size_t)t.width * t.height;
-            if (pool.size() + n >= (1ull << 28)) return fail(RGK_ERR_UNSUPPORTED, "float texel pool exceeds 2^28 texels"); // 32-bit byte offsets
-            o.a = t.width | (t.height << 16);
-            o.b = (uint32_t)pool.size();
-            pool.reserve(pool.size() + n);
-            for (size_t k = 0; k < n; k++) pool.push_back(make_float4(t.texels[3 * k], t.texels[3 * k + 1], t.texels[3 * k + 2], 0.f));
-        }
-    }
-    auto tref = [&](int32_t id) { TexRef r; r.kind = RGK_TEXREF_NONE; r.a = r.b = r.c = 0; return id < 0 ? r : trefs[id]; };
-    std::vector<DevMaterial> mats(d->n_materials);
-    for (uint32_t i = 0; i < d->n_materials; i++) {
-        const rgk_material& m = d->materials[i];
-        DevMaterial& o = mats[i];
-        std::memset(&o, 0, sizeof(o));
-        o.kind = m.kind; o.flags = m.flags;
-        for (int k = 0; k < 3; k++) o.emission[k] = m.emission[k];
-        o.roughness = m.roughness; o.ior = m.ior; o.amount = m.amount;
-        o.t_diffuse = tref(m.tex_diffuse); o.t_color = tref(m.tex_color); o.t_bump = tref(m.tex_bump);
-        o.mix_m1 = m.mix_m1; o.mix_m2 = m.mix_m2;
-    }
-    // ---- lights (scene.cpp:323-344)
-    std::vector<DevPointLight> pls(d->n_pointlights);
-    float total_point = 0.f;
-    const float PI_F = 3.14159265358979323846264338327950288f;
-    for (uint32_t i = 0; i < d->n_pointlights; i++) {
-        const rgk_pointlight& l = d->pointlights[i];
-        DevPointLight& o = pls[i];
-        for (int k = 0; k < 3; k++) { o.pos[k] = l.pos[k]; o.color[k] = l.color[k]; }
-        o.intensity = l.intensity; o.size = l.size;
-        total_point += l.intensity * 4.0f * PI_F;
-    }
-    std::vector<DevArealLight> als;
-    std::vector<DevArealTri> ats;
-    float total_areal = 0.f;
-    build_areal_tables(d->vertices, d->normals, d->tri_indices, d->tri_material, d->materials, d->n_areal_lights, d->areal_offsets, d->areal_tris, als, ats, total_areal);
-    std::vector<DevHaltonDim> hd;
-    std::vector<uint16_t> hp;
-    build_halton(hd, hp);
+    // ---- accelerator and its traversal stack
+    HostAccel host;
+    AccelInfo acc;
+    if ((rc = build_accel(s, d->build_flags, prims, recs, mn, mx, eps, opt, host, acc))) return rc;
+    if ((rc = configure_stack(s, acc.max_stack, opt))) return rc;
 
-    // ---- upload
-    s->n_textures = d->n_textures; s->n_materials = d->n_materials;
-    s->n_vertices = d->n_vertices; s->n_triangles = nt; s->n_refs = n_refs; s->n_nodes = n_nodes;
-    s->h_idx.assign(d->tri_indices, d->tri_indices + 3 * (size_t)nt);
-    s->h_tri_mat.assign(d->tri_material, d->tri_material + nt);
-    s->h_mats.assign(d->materials, d->materials + d->n_materials);
-    s->h_normals.assign(d->normals, d->normals + 3 * (size_t)d->n_vertices);
-    if (d->n_areal_lights) {
-        s->h_areal_off.assign(d->areal_offsets, d->areal_offsets + d->n_areal_lights + 1);
-        s->h_areal_tris.assign(d->areal_tris, d->areal_tris + d->areal_offsets[d->n_areal_lights]);
-    }
-    if ((rc = s->d_idx.upload(s->h_idx.data(), s->h_idx.size()))) return rc;
-    if ((rc = s->texrefs.upload(trefs.data(), trefs.size()))) return rc;
-    if (!on_device && ((rc = s->nodes.upload(qnodes.data(), qnodes.size())) || (rc = s->tris.upload(leaf_recs.data(), leaf_recs.size())) ||
-                       (rc = s->leaf_pb.upload(leaf_pb.data(), leaf_pb.size()))))
-        return rc;
-    if ((rc = s->tri_shade.upload(tsh.data(), tsh.size())) ||
-        (rc = s->materials.upload(mats.data(), mats.size())) || (rc = s->texels.upload(pool.data(), pool.size())) || (rc = s->texels8.upload(pool8.data(), pool8.size())) ||
-        (rc = s->luts.upload(luts.data(), luts.size())) || (rc = s->pointlights.upload(pls.data(), pls.size())) || (rc = s->areal.upload(als.data(), als.size())) ||
-        (rc = s->areal_tris.upload(ats.data(), ats.size())) || (rc = s->hdims.upload(hd.data(), hd.size())) || (rc = s->hperm.upload(hp.data(), hp.size())))
-        return rc;
-    { // both LTC tables in one buffer, {m0,m2,m4,m6}{amp,0,0,0} per entry (two 16-byte loads): GGX, then Beckmann
-        std::vector<float4> t(2 * 2 * 4096, make_float4(0.f, 0.f, 0.f, 0.f));
-        const float* src[2] = {d->ltc_ggx, d->ltc_beckmann};
-        for (int w = 0; w < 2; w++)
-            for (int k = 0; src[w] && k < 4096; k++) {
-                t[(size_t)w * 8192 + 2 * k] = make_float4(src[w][5 * k], src[w][5 * k + 1], src[w][5 * k + 2], src[w][5 * k + 3]);
-                t[(size_t)w * 8192 + 2 * k + 1] = make_float4(src[w][5 * k + 4], 0.f, 0.f, 0.f);
-            }
-        if ((rc = s->ltc.upload(t.data(), t.size()))) return rc;
-    }
-    ds.nodes = s->nodes.p;
-    { const char* e = std::getenv("RGK_WALK_Q"); ds.walk_q = e ? (uint32_t)std::atoi(e) : 3u; }
-    if (s->tune.debug_bvh) std::fprintf(stderr, "[rgk] bvh4 (%s) nodes %u max_stack %u max_depth %u refs %u of %u triangles\n", on_device ? "device LBVH" : "host SAH", n_nodes, max_stack, max_depth, n_refs, nt);
-    ds.tris = s->tris.p; ds.tri_shade = s->tri_shade.p;
-    ds.materials = s->materials.p; ds.texels = s->texels.p; ds.texels8 = s->texels8.p; ds.luts = s->luts.p; ds.n_lut_floats = (uint32_t)luts.size(); ds.n_materials = (uint32_t)mats.size();
-    ds.pointlights = s->pointlights.p; ds.areal = s->areal.p; ds.areal_tris = s->areal_tris.p;
-    ds.ltc = s->ltc.p; ds.hdims = s->hdims.p; ds.hperm = s->hperm.p;
-    ds.n_pointlights = (uint32_t)pls.size(); ds.n_areal = (uint32_t)als.size();
-    ds.total_point_power = total_point; ds.total_areal_power = total_areal;
-    if (!pls.empty()) {
-        s->h_light0 = pls[0];
-        for (int k = 0; k < 3; k++) { ds.cl_pos[k] = pls[0].pos[k]; ds.cl_color[k] = pls[0].color[k]; }
-        ds.cl_intensity = pls[0].intensity;
-    }
-    ds.has_texcoords = d->texcoords ? 1u : 0u;
-    ds.sky_mode = d->sky_mode;
-    for (int k = 0; k < 3; k++) ds.sky_color[k] = d->sky_color[k];
-    ds.sky_intensity = d->sky_intensity; ds.sky_rotate = d->sky_rotate; ds.sky_tex = tref(d->sky_mode == RGK_SKY_ENVMAP ? d->sky_texture : -1);
-    if ((rc = s->self.alloc(1))) return rc;
-    ds.self = s->self.p;
-    if (hipMemcpy(s->self.p, &ds, sizeof(DevScene), hipMemcpyHostToDevice) != hipSuccess) return fail(RGK_ERR_DEVICE, "hipMemcpy(DevScene)");
-
-    rgk_scene_info& inf = s->info;
-    inf.epsilon = eps;
-    for (int a = 0; a < 3; a++) { inf.bbox_min[a] = ds.bb_min[a]; inf.bbox_max[a] = ds.bb_max[a]; }
-    inf.total_areal_power = total_areal; inf.total_point_power = total_point;
-    inf.n_nodes = n_nodes; inf.node_bytes = RGK_NODE_BYTES; inf.tri_bytes = RGK_TRI_BYTES;
-    inf.max_depth = max_depth; inf.n_leaf_refs = n_refs;
-    inf.n_float_textures = n_float_tex; inf.n_palettized_textures = n_palettized;
-    inf.const_light = const_light_eligible(ds, &s->h_light0);
+    // ---- shading tables; upload; DevScene
+    ShadingTables sh;
+    if ((rc = build_shading_tables(d, sh))) return rc;
+    if ((rc = upload_tables(s, d, acc, host, sh))) return rc;
+    if (s->tune.debug_bvh)
+        std::fprintf(stderr, "[rgk] bvh4 (%s) nodes %u max_stack %u max_depth %u refs %u of %u triangles\n", acc.on_device ? "device LBVH" : "host SAH", acc.n_nodes, acc.max_stack,
+                     acc.max_depth, acc.n_refs, d->n_triangles);
+    if ((rc = fill_dev_scene(s, d, acc, sh, opt))) return rc;
     guard.s = nullptr;
     *out = s;
     return RGK_OK;
@@ -1250,19 +424,11 @@ int rgk_scene_refit(rgk_scene* s, const float* vertices, const float* normals, c
     if (s->prog_busy.load()) return fail(RGK_ERR_INVALID, "rgk_scene_refit while a round is in flight on this scene");
     HIPCHK(hipSetDevice(s->device));
     const uint32_t nt = s->n_triangles, nv = s->n_vertices;
-    // ---- Commit's scalars for the new positions: bounds, epsilon (scene.cpp:364-395)
-    float mn[3], mx[3];
-    for (int a = 0; a < 3; a++) { mn[a] = std::numeric_limits<float>::infinity(); mx[a] = -mn[a]; }
-    for (size_t k = 0; k < 3 * (size_t)nt; k++) {
-        const float* v = vertices + 3 * (size_t)s->h_idx[k];
-        for (int a = 0; a < 3; a++) { if (v[a] < mn[a]) mn[a] = v[a]; if (v[a] > mx[a]) mx[a] = v[a]; }
-    }
-    const float xs = mx[0] - mn[0], ys = mx[1] - mn[1], zs = mx[2] - mn[2];
-    const float diameter = std::sqrt(xs * xs + ys * ys + zs * zs);
-    const float eps = 0.00001f * diameter;
-    if (!(eps == eps) || !(diameter < std::numeric_limits<float>::infinity())) return fail(RGK_ERR_INVALID, "non-finite vertex coordinates");
-    // ---- records, shading normals / tangents, and the tree's boxes: on the device
+    // ---- Commit's scalars for the new positions
     int rc;
+    float mn[3], mx[3], eps;
+    if ((rc = commit_bounds(vertices, s->h_idx.data(), nt, mn, mx, &eps))) return rc;
+    // ---- records, shading normals / tangents, and the tree's boxes: on the device
     if ((rc = s->scratch_f.upload(vertices, 3 * (size_t)nv))) return rc;
     DevBuf<float> d_n, d_t;
     if (normals && (rc = d_n.upload(normals, 3 * (size_t)nv))) return rc;
@@ -1281,13 +447,11 @@ int rgk_scene_refit(rgk_scene* s, const float* vertices, const float* normals, c
     if ((rc = s->areal.upload(als.data(), als.size())) || (rc = s->areal_tris.upload(ats.data(), ats.size()))) return rc;
     DevScene& ds = s->dev;
     ds.areal = s->areal.p; ds.areal_tris = s->areal_tris.p; ds.n_areal = (uint32_t)als.size(); ds.total_areal_power = total_areal;
-    ds.epsilon = eps;
-    for (int a = 0; a < 3; a++) { ds.bb_min[a] = mn[a] - eps; ds.bb_max[a] = mx[a] + eps; }
+    set_bounds(s, mn, mx, eps);
     if (hipMemcpy(s->self.p, &ds, sizeof(DevScene), hipMemcpyHostToDevice) != hipSuccess) return fail(RGK_ERR_DEVICE, "hipMemcpy(DevScene)");
-    s->info.epsilon = eps; s->info.total_areal_power = total_areal;
+    s->info.total_areal_power = total_areal;
     s->info.const_light = const_light_eligible(ds, &s->h_light0);
-    for (int a = 0; a < 3; a++) { s->info.bbox_min[a] = ds.bb_min[a]; s->info.bbox_max[a] = ds.bb_max[a]; }
-    s->entry_key = 0; s->entry_n = 0; s->entry_capped = 0; s->lentry_done = 0; // per-frame lists were made for the old boxes
+    invalidate_frame_lists(s);
     return RGK_OK;
 }
 
@@ -1321,8 +485,7 @@ int rgk_scene_set_tuning(rgk_scene* s, const char* key, double value) {
     else if (k == "workspace_gb") t.workspace_gb = value <= 0 ? 0.0 : value;
     else if (k == "beam") t.beam = (int)std::min(2.0, std::max(0.0, value));
     else return fail(RGK_ERR_INVALID, "unknown tuning key '%s'", key);
-    // per-frame lists were made under the old switches: the next round rebuilds them
-    s->entry_key = 0; s->entry_n = 0; s->entry_capped = 0; s->lentry_done = 0;
+    invalidate_frame_lists(s);
     return RGK_OK;
 }
 

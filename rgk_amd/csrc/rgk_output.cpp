@@ -10,7 +10,7 @@
 
 #include "../../include/rgk.h"
 
-extern "C" int rgk_internal_fail(int code, const char* msg); // rgk_host.cpp: sets rgk_last_error
+extern "C" int rgk_internal_fail(int code, const char* msg); // rgk_commit.cpp: sets rgk_last_error
 
 // float -> half with round-to-nearest-even, denormals, overflow to infinity, NaN kept: the value half(float)
 // of OpenEXR's half class produces.

@@ -464,7 +464,7 @@ __device__ __forceinline__ void trace_persistent(const DevScene& sc, const float
 #undef RGK_CSWAP
                 // misses carry te = inf / ref = SENTINEL and sort to the back; push far -> near.
                 // Branch-free: always write the next free entry, advance only for a real child (the host
-                // sized STACK above the deepest push sequence the tree can produce, rgk_host.cpp QbvhBuilder).
+                // sized STACK above the deepest push sequence the tree can produce, rgk_commit.cpp QbvhBuilder).
                 if (LDSN >= STACK || sp + 3 <= LDSN) { // all three possible entries fit the LDS part: one test instead of three
                     stack[sp * stride] = ref[3]; sp += (ref[3] != STACK_SENTINEL);
                     stack[sp * stride] = ref[2]; sp += (ref[2] != STACK_SENTINEL);
