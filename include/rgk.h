@@ -303,7 +303,8 @@ int rgk_scene_get_progress(const rgk_scene *scene, rgk_progress *out);
  * of them share; 0: the per-path route.  The scene qualifies when it has exactly one point light and no emitting triangle, the
  * light's size is 0, no component of its position is -0.0 (pos + 0 * v must give back pos bit for bit), and GetRandomLight's
  * own two float comparisons, evaluated with its own expressions for the largest number the sampler returns, 1 - 2^-24, select
- * light 0: rounding is monotone, so every smaller sample selects it too.  Same bits either way).  Their initial values are read from the environment
+ * light 0: rounding is monotone, so every smaller sample selects it too.  Same bits either way), "time_post" (0 / 1, default 0: HIP events
+ * around the launches of the feature pass and the denoiser, read with rgk_scene_get_post_timing).  Their initial values are read from the environment
  * (RGK_ENTRY_POINTS, RGK_ENTRY_CAP, RGK_LIGHT_ENTRY, RGK_CONST_LIGHT, RGK_SAMPLE_GROUP, RGK_BATCH_PATHS, RGK_WORKSPACE_GB) ONCE, in
  * rgk_scene_create; a round never reads the environment.  Not while a round is in flight on this scene. */
 int rgk_scene_set_tuning(rgk_scene *scene, const char *key, double value);
@@ -399,6 +400,55 @@ int rgk_bxdf_sample(rgk_scene *scene, uint32_t n, uint32_t route, const uint32_t
  * descriptor texture tex[i] (-1: EmptyTexture) at uv[i]. */
 int rgk_texture_sample(rgk_scene *scene, uint32_t n, const int32_t *tex, const float *uv, float *rgb, float *slope_right,
                        float *slope_bottom);
+
+/* ---- first-hit feature buffers and the guided denoiser (DESIGN.md "Feature buffers and the a-trous denoiser") ---- */
+
+/* One primary ray per pixel of the listed tiles through the pixel CENTRE (sub-pixel offset (0.5, 0.5)), leaving from
+ * camera->origin (the lens is ignored), near 0 / far 10000 as every camera ray; traced by the round's own closest-hit walker.
+ * params supplies xres, yres and bumpmap_scale (the sampler is not used).  Planes are row-major from the top row, P = xres * yres;
+ * pixels outside the tiles are not written.  Any output may be NULL.  DEVICE buffers on the scene's GPU; blocking.
+ *   miss:  tri = -1, depth = 0, normal = albedo = 0
+ *   hit:   tri = triangle id, depth = the ray's t, normal = the bump-tilted shading normal the integrator lights with (world
+ *          space, NOT flipped towards the viewer); a vertex the integrator drops (NaN / zero face normal) has normal = albedo = 0
+ *   albedo by material at the hit's uv: diffuse -> diffuse texture; ltc_* -> colour texture; ltc_*_diffuse -> diffuse + colour;
+ *          mirror, dielectric, transparent -> (1, 1, 1); mix -> amount * albedo(m1) + (1 - amount) * albedo(m2), a mix inside a mix
+ *          evaluated likewise and a third level as 0 (what the BxDF code does); emission does not enter.
+ * Not while a round is in flight on this scene.  A call between two rounds of a frame changes nothing those rounds compute. */
+int rgk_render_aov_device(rgk_scene *scene, const rgk_camera *camera, const rgk_params *params, const rgk_tile *tiles,
+                          uint32_t n_tiles, float *d_albedo /*3P*/, float *d_normal /*3P*/, float *d_depth /*P*/, int32_t *d_tri /*P*/);
+/* Same with HOST buffers (their contents are kept outside the tiles). */
+int rgk_render_aov(rgk_scene *scene, const rgk_camera *camera, const rgk_params *params, const rgk_tile *tiles, uint32_t n_tiles,
+                   float *albedo, float *normal, float *depth, int32_t *tri);
+
+/* Edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) of the accumulator's image, guided by the feature planes.
+ * c = accum_rgb / accum_count (0 where the count is 0); with `demodulate`, c is divided per channel by (albedo > 0 ? albedo : 1)
+ * before the filter and multiplied back after it.  Iteration i = 0 .. iterations - 1, step s = 2^i: 5 x 5 taps q = p + s * (dx, dy)
+ * (dy outer, dx inner, both -2 .. 2; taps outside the frame are skipped), h = {1/16, 1/4, 3/8, 1/4, 1/16},
+ *   w  = (((h[dy] * h[dx]) * wn) * wz) * wc
+ *   wn = max(0, n_p . n_q), squared normal_power_log2 times
+ *   wz = 1 / (1 + r * r),  r = |z_p - z_q| / (sigma_depth * (z_p + z_q) + 1e-20f)
+ *   wc = 1 / (1 + |c_p - c_q|^2 / sigma_i^2),  sigma_i = sigma_color * 2^-i      (sigma_color: in the image's radiance units)
+ *   out_p = sum(w * c_q) / sum(w)
+ * A pixel whose normal is zero (miss, dropped vertex) passes through unchanged and is never a tap of another pixel.
+ * iterations == 0: out = c (nothing is filtered, nothing is demodulated).  Only + - * / max in float32, no contraction: the
+ * same operations in the same order give the same bits on a CPU.  iterations, normal_power_log2 <= 16; sigma_color > 0,
+ * sigma_depth >= 0.  Arguments are checked before the scene or the device is touched. */
+typedef struct rgk_denoise_params {
+    uint32_t iterations;
+    float sigma_color, sigma_depth;
+    uint32_t normal_power_log2;
+    uint32_t demodulate;
+} rgk_denoise_params;
+/* accum_rgb / accum_count as a round leaves them and the three feature planes of rgk_render_aov_device (d_albedo may be NULL
+ * when demodulate == 0); out_rgb: 3P floats (not one of the inputs).  All DEVICE pointers on the scene's GPU; whole frame; blocking. */
+int rgk_denoise_device(rgk_scene *scene, uint32_t xres, uint32_t yres, const float *d_accum_rgb, const uint32_t *d_accum_count,
+                       const float *d_albedo, const float *d_normal, const float *d_depth, const rgk_denoise_params *params,
+                       float *d_out_rgb);
+
+/* HIP-event times of the launches of the LAST feature pass (which = 0: pixel list + ray generation, walker, gather) or denoise
+ * call (which = 1: preparation, one per iteration, finish) on this scene, in ms; recorded only while the tuning key "time_post"
+ * is 1.  *n: in, room in ms; out, entries the call had (those that fit are written). */
+int rgk_scene_get_post_timing(const rgk_scene *scene, uint32_t which, double *ms, uint32_t *n);
 
 /* The pinned transcendental functions of the path (include/rgk_libm.h) evaluated on the device, for the test that the GPU
  * and the CPU produce the same bits: fn 0 sin, 1 cos, 2 acos, 3 asin, 4 atan2(a[i], b[i]) (b may be NULL otherwise). */

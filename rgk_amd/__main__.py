@@ -14,6 +14,10 @@
                     frame has its own (F gets the frame number as a suffix); a checkpoint written for another scene, camera
                     or parameter set is refused
   --device N        GPU to use (default 0)
+  --aov             also writes the first-hit feature images, once per frame: the output name with the suffixes `albedo`,
+                    `normal` (world space, as lit) and `depth` (the ray's t in R, G and B; 0 where nothing is hit)
+  --denoise         also writes the output name with the suffix `denoised` after every round: the round's image through the
+                    feature-guided a-trous filter, normalised with the scale the plain output got.  The plain output is unchanged
 FILE is a .json or .rtc scene config.  One process drives one GPU; several GPUs: python -m torch.distributed.run ... bench.py.
 """
 import argparse
@@ -71,6 +75,8 @@ def main(argv=None):
     ap.add_argument("-q", action="count", default=0)
     ap.add_argument("--checkpoint", default=None)
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--aov", action="store_true")
+    ap.add_argument("--denoise", action="store_true")
     ap.add_argument("--frames", type=int, default=None, help="with -r: stop after this many frames (default: all 501)")
     args = ap.parse_args(argv)
     verbosity = max(0, 2 + args.v - args.q)
@@ -151,7 +157,9 @@ def main(argv=None):
         say(2, f"Writing to file {out}")
         timed = cfg.render_minutes is not None
         with FrameMonitor(scene, timed, cfg.render_rounds, cfg.render_minutes or 0, cfg.xres * cfg.yres, verbosity=verbosity) as mon:
-            drv.render_frame(rounds=max(0, cfg.render_rounds - drv.rounds_done) if not timed else None, output_file=out, checkpoint=ckpt)
+            drv.render_frame(rounds=max(0, cfg.render_rounds - drv.rounds_done) if not timed else None, output_file=out, checkpoint=ckpt,
+                             aov_files={k: insert_file_suffix(out, k) for k in ("albedo", "normal", "depth")} if args.aov else None,
+                             denoised_file=insert_file_suffix(out, "denoised") if args.denoise else None)
             mon.rays_done = sum(c.path_rays for c in drv.counters)
     return 0
 

@@ -125,6 +125,15 @@ class Hit(C.Structure):
                 ("c", C.c_float)]
 
 
+class DenoiseParams(C.Structure):
+    """rgk_denoise_params; the defaults are the shipped ones (sigma_color is chosen per image: RenderDriver.denoise)."""
+    _fields_ = [("iterations", C.c_uint32), ("sigma_color", C.c_float), ("sigma_depth", C.c_float),
+                ("normal_power_log2", C.c_uint32), ("demodulate", C.c_uint32)]
+
+    def __init__(self, iterations=5, sigma_color=1.0, sigma_depth=0.02, normal_power_log2=6, demodulate=1):
+        super().__init__(iterations, sigma_color, sigma_depth, normal_power_log2, demodulate)
+
+
 # every symbol include/rgk.h declares (tests check the .so exports all of them)
 EXPORTS = ["rgk_last_error", "rgk_device_count", "rgk_scene_create", "rgk_scene_destroy",
            "rgk_scene_get_info", "rgk_scene_get_progress", "rgk_scene_set_tuning", "rgk_scene_refit", "rgk_generate_task_list", "rgk_camera_init", "rgk_render_round",
@@ -133,7 +142,8 @@ EXPORTS = ["rgk_last_error", "rgk_device_count", "rgk_scene_create", "rgk_scene_
            "rgk_libm_eval", "rgk_sampler_eval", "rgk_output_normalize", "rgk_output_write_exr", "rgk_float_to_half",
            "rgk_accum_create", "rgk_accum_destroy", "rgk_accum_clear", "rgk_accum_rgb", "rgk_accum_count",
            "rgk_accum_download", "rgk_accum_upload", "rgk_accum_add", "rgk_accum_set_tag", "rgk_accum_save", "rgk_accum_load",
-           "rgk_shard_tiles", "rgk_comm_get_unique_id", "rgk_comm_create", "rgk_comm_destroy", "rgk_accum_reduce"]
+           "rgk_shard_tiles", "rgk_comm_get_unique_id", "rgk_comm_create", "rgk_comm_destroy", "rgk_accum_reduce",
+           "rgk_render_aov_device", "rgk_render_aov", "rgk_denoise_device", "rgk_scene_get_post_timing"]
 
 _p = C.POINTER
 
@@ -186,6 +196,12 @@ def _bind(lib):
     lib.rgk_comm_destroy.argtypes = [C.c_void_p]
     lib.rgk_comm_destroy.restype = None
     lib.rgk_accum_reduce.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int]
+    lib.rgk_render_aov_device.argtypes = [C.c_void_p, _p(Camera), _p(Params), _p(Tile), C.c_uint32,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rgk_render_aov.argtypes = lib.rgk_render_aov_device.argtypes
+    lib.rgk_denoise_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       _p(DenoiseParams), C.c_void_p]
+    lib.rgk_scene_get_post_timing.argtypes = [C.c_void_p, C.c_uint32, _p(C.c_double), _p(C.c_uint32)]
     lib.rgk_float_to_half.argtypes = [C.c_float]
     lib.rgk_float_to_half.restype = C.c_uint16
     return lib

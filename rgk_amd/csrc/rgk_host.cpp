@@ -90,6 +90,7 @@ struct RgkTuning {
     int beam = 1;             // pinhole cameras: bounce 0 walks the tree once per pixel for 8 samples (k_trace_camera_beam) -- 1: while the
                               // entry lists are uncapped (a frame's first round), 2: always, 0: never
     bool debug_bvh = false, debug_util = false;
+    bool time_post = false;   // feature pass / denoiser: HIP events around their launches (rgk_scene_get_post_timing)
 };
 
 struct rgk_scene {
@@ -149,6 +150,8 @@ struct rgk_scene {
     DevBuf<unsigned long long> stats;
     DevBuf<float> scratch_f;
     DevBuf<uint32_t> scratch_u;
+    DevBuf<float4> dn_col[2], dn_guide; // the denoiser's two colour planes and its guide plane {n.xyz, z}
+    std::vector<double> post_ms[2];     // launch times of the last feature pass [0] / denoise call [1] (tuning "time_post")
     std::vector<hipEvent_t> events;
     uint32_t* h_counters = nullptr; // pinned
     // progress, read by rgk_scene_get_progress from any thread
@@ -484,6 +487,7 @@ int rgk_scene_set_tuning(rgk_scene* s, const char* key, double value) {
     else if (k == "batch_paths") t.batch_paths = value <= 0 ? 0 : std::max<size_t>(1024, (size_t)value);
     else if (k == "workspace_gb") t.workspace_gb = value <= 0 ? 0.0 : value;
     else if (k == "beam") t.beam = (int)std::min(2.0, std::max(0.0, value));
+    else if (k == "time_post") { t.time_post = value != 0; return RGK_OK; } // (no launch of a round depends on it: the frame's lists stay)
     else return fail(RGK_ERR_INVALID, "unknown tuning key '%s'", key);
     invalidate_frame_lists(s);
     return RGK_OK;
@@ -1121,6 +1125,152 @@ int rgk_sampler_eval(uint32_t n, const uint32_t* seed, const uint32_t* index, co
     rgk_launch_sampler_eval(nullptr, sc, n, ds_.p, di.p, dd.p, is2d, dout.p);
     hipError_t e = hipMemcpy(out, dout.p, (size_t)2 * n * sizeof(float), hipMemcpyDeviceToHost);
     if (e != hipSuccess) return fail(RGK_ERR_DEVICE, "sampler eval: %s", hipGetErrorString(e));
+    return RGK_OK;
+}
+
+} // extern "C"
+
+// ------------------------------------------------------------------ feature buffers and the denoiser (kernels: rgk_post.hip)
+namespace {
+// HIP events around the launches of one feature pass / denoise call, when the scene's "time_post" switch is on.
+struct PostTimer {
+    rgk_scene* s;
+    bool on;
+    std::vector<hipEvent_t> ev;
+    PostTimer(rgk_scene* s_) : s(s_), on(s_->tune.time_post) {}
+    ~PostTimer() { for (auto e : ev) (void)hipEventDestroy(e); }
+    int mark() { // between two launches
+        if (!on) return 0;
+        hipEvent_t e;
+        HIPCHK(hipEventCreate(&e));
+        ev.push_back(e);
+        HIPCHK(hipEventRecord(e, s->stream));
+        return 0;
+    }
+    int fold(std::vector<double>& out) { // after the stream has been waited for
+        out.clear();
+        for (size_t i = 0; on && i + 1 < ev.size(); i++) {
+            float ms = 0.f;
+            HIPCHK(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
+            out.push_back(ms);
+        }
+        return 0;
+    }
+};
+
+int check_aov_args(const rgk_scene* s, const rgk_camera* camera, const rgk_params* prm, const rgk_tile* tiles, uint32_t n_tiles) {
+    if (!s || !camera || !prm || (!tiles && n_tiles)) return fail(RGK_ERR_INVALID, "null argument");
+    if (prm->xres == 0 || prm->yres == 0 || prm->xres > 65535 || prm->yres > 65535) return fail(RGK_ERR_INVALID, "resolution out of range");
+    for (uint32_t i = 0; i < n_tiles; i++) {
+        const rgk_tile& t = tiles[i];
+        if (t.x1 > prm->xres || t.y1 > prm->yres || t.x0 > t.x1 || t.y0 > t.y1) return fail(RGK_ERR_INVALID, "tile %u outside the frame", i);
+    }
+    return 0;
+}
+} // namespace
+
+extern "C" {
+
+int rgk_render_aov_device(rgk_scene* s, const rgk_camera* camera, const rgk_params* prm, const rgk_tile* tiles, uint32_t n_tiles, float* d_albedo,
+                          float* d_normal, float* d_depth, int32_t* d_tri) {
+    int rc;
+    if ((rc = check_aov_args(s, camera, prm, tiles, n_tiles))) return rc;
+    if (s->prog_busy.load()) return fail(RGK_ERR_INVALID, "rgk_render_aov_device while a round is in flight on this scene");
+    std::vector<uint32_t> toff(n_tiles + 1, 0u); // (read by a queued copy: lives until the stream has been waited for)
+    for (uint32_t i = 0; i < n_tiles; i++) {
+        const uint64_t total = (uint64_t)toff[i] + (uint64_t)(tiles[i].x1 - tiles[i].x0) * (tiles[i].y1 - tiles[i].y0);
+        if (total >= (1ull << 31)) return fail(RGK_ERR_UNSUPPORTED, "more than 2^31 pixels in one feature pass");
+        toff[i + 1] = (uint32_t)total;
+    }
+    const uint32_t n = toff[n_tiles];
+    s->post_ms[0].clear();
+    if (n == 0) return RGK_OK;
+    HIPCHK(hipSetDevice(s->device));
+    // The round's own buffers: its pixel list (rebuilt by every round before it is read), two ray planes and the hit plane of
+    // the workspace (written by every pass before they are read).  The frame's cached lists -- entry nodes, their caps, the
+    // light-side entries -- are neither read nor written here, so the rounds of a frame compute the same with or without this call.
+    if ((rc = ensure_workspace(s, n)) || (rc = s->pix_xy.alloc(n)) || (rc = s->pix_seed.alloc(n)) || (rc = s->tile_buf.alloc((size_t)n_tiles * 5 + n_tiles + 1))) return rc;
+    hipStream_t st = s->stream;
+    PostTimer tm(s);
+    HIPCHK(hipMemcpyAsync(s->tile_buf.p, tiles, (size_t)n_tiles * sizeof(rgk_tile), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(s->tile_buf.p + (size_t)n_tiles * 5, toff.data(), (n_tiles + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    DevCamera cam;
+    make_camera(camera, cam);
+    cam.lens_size = 0.0f; // every feature ray leaves from the camera's origin
+    if ((rc = tm.mark())) return rc;
+    rgk_launch_build_pixel_list(st, reinterpret_cast<const rgk_tile*>(s->tile_buf.p), s->tile_buf.p + (size_t)n_tiles * 5, n_tiles, s->pix_xy.p, s->pix_seed.p);
+    rgk_launch_init_counters(st, s->counters.p, n);
+    rgk_launch_aov_raygen(st, cam, prm->xres, prm->yres, s->pix_xy.p, n, s->rayA[0].p, s->rayB[0].p);
+    if ((rc = tm.mark())) return rc;
+    rgk_launch_set_bound(n, n);
+    rgk_launch_trace_closest(st, s->dev, s->tcfg, false, s->rayA[0].p, s->rayB[0].p, nullptr, s->hit.p, s->counters.p + RGK_CNT_QUEUE, s->counters.p + RGK_CNT_FETCH_T, s->stats.p);
+    if ((rc = tm.mark())) return rc;
+    rgk_launch_aov_gather(st, s->dev, prm->bumpmap_scale, prm->xres, s->pix_xy.p, n, s->rayA[0].p, s->rayB[0].p, s->hit.p, d_albedo, d_normal, d_depth, d_tri);
+    if ((rc = tm.mark())) return rc;
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    return tm.fold(s->post_ms[0]);
+}
+
+int rgk_render_aov(rgk_scene* s, const rgk_camera* camera, const rgk_params* prm, const rgk_tile* tiles, uint32_t n_tiles, float* albedo, float* normal,
+                   float* depth, int32_t* tri) {
+    int rc;
+    if ((rc = check_aov_args(s, camera, prm, tiles, n_tiles))) return rc;
+    HIPCHK(hipSetDevice(s->device));
+    const size_t P = (size_t)prm->xres * prm->yres;
+    DevBuf<float> d_alb, d_nrm, d_z;
+    DevBuf<int32_t> d_tri;
+    // (the planes go up first: pixels outside the tiles keep what the caller had there)
+    if ((albedo && (rc = d_alb.upload(albedo, 3 * P))) || (normal && (rc = d_nrm.upload(normal, 3 * P))) || (depth && (rc = d_z.upload(depth, P))) || (tri && (rc = d_tri.upload(tri, P))))
+        return rc;
+    if ((rc = rgk_render_aov_device(s, camera, prm, tiles, n_tiles, albedo ? d_alb.p : nullptr, normal ? d_nrm.p : nullptr, depth ? d_z.p : nullptr, tri ? d_tri.p : nullptr))) return rc;
+    if ((albedo && (rc = down(albedo, d_alb, 3 * P))) || (normal && (rc = down(normal, d_nrm, 3 * P))) || (depth && (rc = down(depth, d_z, P))) || (tri && (rc = down(tri, d_tri, P)))) return rc;
+    return RGK_OK;
+}
+
+int rgk_denoise_device(rgk_scene* s, uint32_t xres, uint32_t yres, const float* d_accum_rgb, const uint32_t* d_accum_count, const float* d_albedo,
+                       const float* d_normal, const float* d_depth, const rgk_denoise_params* dp, float* d_out_rgb) {
+    // (every check before the scene or the device is touched)
+    if (!s || !d_accum_rgb || !d_accum_count || !d_normal || !d_depth || !dp || !d_out_rgb) return fail(RGK_ERR_INVALID, "null argument");
+    if (dp->demodulate && !d_albedo) return fail(RGK_ERR_INVALID, "demodulate without an albedo plane");
+    if (xres == 0 || yres == 0 || xres > 65535 || yres > 65535) return fail(RGK_ERR_INVALID, "resolution out of range");
+    if (dp->iterations > 16 || dp->normal_power_log2 > 16) return fail(RGK_ERR_INVALID, "iterations and normal_power_log2 must be <= 16");
+    if (!(dp->sigma_color > 0.0f) || !(dp->sigma_depth >= 0.0f) || std::isinf(dp->sigma_color) || std::isinf(dp->sigma_depth)) return fail(RGK_ERR_INVALID, "sigma_color must be > 0 and sigma_depth >= 0, both finite");
+    if (d_out_rgb == d_accum_rgb || d_out_rgb == d_albedo || d_out_rgb == d_normal) return fail(RGK_ERR_INVALID, "out_rgb must not be one of the inputs");
+    float sigma2[16];
+    for (uint32_t i = 0; i < dp->iterations; i++) {
+        const float si = dp->sigma_color * std::ldexp(1.0f, -(int)i); // sigma_color * 2^-i
+        sigma2[i] = si * si;
+        if (!(sigma2[i] > 0.0f) || std::isinf(sigma2[i])) return fail(RGK_ERR_INVALID, "sigma_color^2 leaves the float range at iteration %u", i);
+    }
+    if (s->prog_busy.load()) return fail(RGK_ERR_INVALID, "rgk_denoise_device while a round is in flight on this scene");
+    HIPCHK(hipSetDevice(s->device));
+    const size_t P = (size_t)xres * yres;
+    const uint32_t it = dp->iterations, demod = (it && dp->demodulate) ? 1u : 0u; // no iteration: out = c, nothing to demodulate for
+    int rc;
+    if ((rc = s->dn_col[0].alloc(P)) || (it && ((rc = s->dn_col[1].alloc(P)) || (rc = s->dn_guide.alloc(P))))) return rc;
+    hipStream_t st = s->stream;
+    PostTimer tm(s);
+    s->post_ms[1].clear();
+    if ((rc = tm.mark())) return rc;
+    rgk_launch_dn_prepare(st, P, d_accum_rgb, d_accum_count, d_albedo, d_normal, d_depth, demod, s->dn_col[0].p, it ? s->dn_guide.p : nullptr);
+    if ((rc = tm.mark())) return rc;
+    for (uint32_t i = 0; i < it; i++) {
+        rgk_launch_dn_atrous(st, xres, yres, 1u << i, sigma2[i], dp->sigma_depth, dp->normal_power_log2, s->dn_guide.p, s->dn_col[i & 1].p, s->dn_col[(i & 1) ^ 1].p);
+        if ((rc = tm.mark())) return rc;
+    }
+    rgk_launch_dn_finish(st, P, s->dn_col[it & 1].p, d_albedo, demod, d_out_rgb);
+    if ((rc = tm.mark())) return rc;
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    return tm.fold(s->post_ms[1]);
+}
+
+int rgk_scene_get_post_timing(const rgk_scene* s, uint32_t which, double* ms, uint32_t* n) {
+    if (!s || !n || which > 1 || (!ms && *n)) return fail(RGK_ERR_INVALID, "bad argument");
+    const std::vector<double>& v = s->post_ms[which];
+    for (uint32_t i = 0; i < *n && i < v.size(); i++) ms[i] = v[i];
+    *n = (uint32_t)v.size();
     return RGK_OK;
 }
 

@@ -143,3 +143,13 @@ void rgk_launch_bxdf_sample(hipStream_t st, const DevScene& sc, uint32_t n, uint
                             float* out_dir, float* out_w, uint8_t* leak);
 void rgk_launch_texture_sample(hipStream_t st, const DevScene& sc, uint32_t n, const TexRef* refs, const int32_t* tex, const float* uv, float* rgb, float* sr, float* sb);
 void rgk_launch_libm_eval(hipStream_t st, int fn, uint32_t n, const float* a, const float* b, float* out);
+
+// post-processing (rgk_post.hip): the feature pass around rgk_launch_trace_closest, and the a-trous denoiser
+void rgk_launch_aov_raygen(hipStream_t st, const DevCamera& cam, uint32_t xres, uint32_t yres, const uint32_t* pix_xy, uint32_t n, float4* rayA, float4* rayB);
+void rgk_launch_aov_gather(hipStream_t st, const DevScene& sc, float bumpmap_scale, uint32_t xres, const uint32_t* pix_xy, uint32_t n, const float4* rayA,
+                           const float4* rayB, const float4* hit, float* albedo, float* normal, float* depth, int32_t* tri);
+void rgk_launch_dn_prepare(hipStream_t st, size_t P, const float* accum_rgb, const uint32_t* accum_count, const float* albedo, const float* normal, const float* depth,
+                           uint32_t demodulate, float4* col, float4* guide);
+void rgk_launch_dn_atrous(hipStream_t st, uint32_t xres, uint32_t yres, uint32_t step, float sigma2, float sigma_depth, uint32_t npow, const float4* guide,
+                          const float4* src, float4* dst);
+void rgk_launch_dn_finish(hipStream_t st, size_t P, const float4* col, const float* albedo, uint32_t demodulate, float* out_rgb);

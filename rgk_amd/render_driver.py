@@ -22,6 +22,10 @@ from . import capi
 
 TILE_SIZE = 32  # src/global_config.hpp:8
 SEEDSTART = 42  # src/render_driver.cpp:222
+# The denoiser's default sigma_color is DENOISE_SIGMA_K x the mean over pixels of the largest channel of the image: the k that
+# minimises the summed relative L2 error of the CPU sweep in DESIGN.md ("Feature buffers and the a-trous denoiser";
+# tools/denoise_sweep.py reproduces it).
+DENOISE_SIGMA_K = 6.0
 
 
 def generate_task_list(xres, yres, seedstart=SEEDSTART, seedcount_base=0, tile_size=TILE_SIZE, mid=None):
@@ -116,6 +120,35 @@ class Scene:
                                                        accum.ctypes.data, count.ctypes.data, C.byref(cnt)))
         return accum, count, cnt
 
+    def render_aov(self, camera, params, tiles, albedo=None, normal=None, depth=None, tri=None, sentinel=None):
+        """rgk_render_aov, host buffers: first-hit albedo / normal (y, x, 3) float32, depth (y, x) float32 and triangle id
+        (y, x) int32 of the tiles' pixels.  Planes that are not passed in are created (filled with `sentinel`, default 0)."""
+        y, x = params.yres, params.xres
+        fill = 0 if sentinel is None else sentinel
+        albedo = np.full((y, x, 3), fill, np.float32) if albedo is None else albedo
+        normal = np.full((y, x, 3), fill, np.float32) if normal is None else normal
+        depth = np.full((y, x), fill, np.float32) if depth is None else depth
+        tri = np.full((y, x), fill, np.int32) if tri is None else tri
+        capi.check(self.lib, self.lib.rgk_render_aov(self.h, C.byref(camera), C.byref(params), tiles, len(tiles), albedo.ctypes.data,
+                                                     normal.ctypes.data, depth.ctypes.data, tri.ctypes.data))
+        return albedo, normal, depth, tri
+
+    def render_aov_device(self, camera, params, tiles, d_albedo=None, d_normal=None, d_depth=None, d_tri=None):
+        """rgk_render_aov_device: DEVICE pointers (ints) on the scene's GPU; any may be None."""
+        capi.check(self.lib, self.lib.rgk_render_aov_device(self.h, C.byref(camera), C.byref(params), tiles, len(tiles),
+                                                            d_albedo, d_normal, d_depth, d_tri))
+
+    def denoise_device(self, xres, yres, d_accum_rgb, d_accum_count, d_albedo, d_normal, d_depth, params, d_out_rgb):
+        """rgk_denoise_device: the guided a-trous filter of a whole frame, DEVICE pointers (ints) on the scene's GPU."""
+        capi.check(self.lib, self.lib.rgk_denoise_device(self.h, xres, yres, d_accum_rgb, d_accum_count, d_albedo, d_normal, d_depth,
+                                                         C.byref(params), d_out_rgb))
+
+    def post_timing(self, which):
+        """HIP-event times (ms) of the launches of the last feature pass (0) / denoise call (1); set_tuning(time_post=1) first."""
+        ms, n = (C.c_double * 32)(), C.c_uint32(32)
+        capi.check(self.lib, self.lib.rgk_scene_get_post_timing(self.h, which, ms, C.byref(n)))
+        return list(ms[:min(n.value, 32)])
+
     def render_round_device(self, camera, params, tiles, d_accum_ptr, d_count_ptr):
         cnt = capi.Counters()
         capi.check(self.lib, self.lib.rgk_render_round_device(self.h, C.byref(camera), C.byref(params), tiles, len(tiles),
@@ -160,6 +193,13 @@ def read_exr(path):
         for k, c in enumerate(chans):
             img[yy - y0, :, "RGBA".index(c)] = line[k]
     return img
+
+
+def write_exr(path, rgb):
+    """rgk_output_write_exr of a (y, x, 3) float32 image."""
+    lib = capi.load_product()
+    rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+    capi.check(lib, lib.rgk_output_write_exr(str(path).encode(), rgb.shape[1], rgb.shape[0], rgb.ctypes.data))
 
 
 class EXRTexture:
@@ -218,6 +258,7 @@ class RenderDriver:
         self.round_ob = None
         self.clock = time.time
         self.checkpoint_tag = 0  # digest of scene + camera + parameters (rgk_accum_set_tag); 0: checkpoints are not compared
+        self.aov = None  # the frame's feature planes once render_aov() has made them
 
     def render_round(self, reduce=True):
         """One RenderRound: every rank renders its tiles into its private accumulator, then ONE sum-reduce of the RGB
@@ -256,6 +297,45 @@ class RenderDriver:
         self.rounds_done += 1
         self.counters.append(cnt)
         return cnt
+
+    def render_aov(self):
+        """First-hit feature planes of the whole frame, one ray per pixel through the pixel centre: a dict of torch tensors
+        on the device -- "albedo", "normal" (y, x, 3) float32, "depth" (y, x) float32, "tri" (y, x) int32 (-1: miss).
+        Rendered once per driver (one frame, one camera) and kept.  With several ranks the root alone renders them, the
+        whole frame (it is one ray per pixel); the other ranks get None."""
+        import torch
+        if self.rank != 0:
+            return None
+        if self.aov is None:
+            y, x = self.cfg.yres, self.cfg.xres
+            a = {"albedo": torch.empty((y, x, 3), dtype=torch.float32, device=self.device),
+                 "normal": torch.empty((y, x, 3), dtype=torch.float32, device=self.device),
+                 "depth": torch.empty((y, x), dtype=torch.float32, device=self.device),
+                 "tri": torch.empty((y, x), dtype=torch.int32, device=self.device)}
+            torch.cuda.current_stream(self.device).synchronize()
+            self.scene.render_aov_device(self.camera, self.params, self.tasks, a["albedo"].data_ptr(), a["normal"].data_ptr(),
+                                         a["depth"].data_ptr(), a["tri"].data_ptr())
+            self.aov = a
+        return self.aov
+
+    def default_denoise_params(self):
+        """The shipped defaults; sigma_color = DENOISE_SIGMA_K x the mean over pixels of the largest channel of the image."""
+        level = float(self.total_ob.get_pixels().max(dim=-1).values.double().mean())
+        return capi.DenoiseParams(sigma_color=DENOISE_SIGMA_K * level if level > 0 else 1.0)
+
+    def denoise(self, params=None):
+        """The current accumulator's image (data / count, not normalised) through the guided a-trous filter
+        (rgk_denoise_device): a (y, x, 3) float32 torch tensor on the device.  The accumulator is not changed.  Root rank only."""
+        import torch
+        if self.rank != 0:
+            return None
+        a = self.render_aov()
+        params = params or self.default_denoise_params()
+        out = torch.empty_like(self.total_ob.data)
+        torch.cuda.current_stream(self.device).synchronize()
+        self.scene.denoise_device(self.cfg.xres, self.cfg.yres, self.total_ob.data.data_ptr(), self.total_ob.count.data_ptr(),
+                                  a["albedo"].data_ptr(), a["normal"].data_ptr(), a["depth"].data_ptr(), params, out.data_ptr())
+        return out
 
     def save_checkpoint(self, path):
         """Raw-accumulator checkpoint (rgk_accum_save): accumulator + rounds done + the running task counter."""
@@ -300,17 +380,26 @@ class RenderDriver:
             go = bool(flag.item())
         return go
 
-    def render_frame(self, rounds=None, minutes=None, output_file=None, checkpoint=None):
+    def render_frame(self, rounds=None, minutes=None, output_file=None, checkpoint=None, aov_files=None, denoised_file=None):
         """RenderFrame: Rounds mode (render_driver.cpp:229-235) or Timed mode (:237-247); with `output_file` the
-        normalised image is rewritten after every round, as the reference does (rank 0 only)."""
+        normalised image is rewritten after every round, as the reference does (rank 0 only).
+        aov_files: {"albedo" / "normal" / "depth": path} -- the feature planes, written once (depth replicated to R, G, B).
+        denoised_file: rewritten after every round that rewrites output_file, normalised with the scale output_file got."""
         rounds = self.cfg.render_rounds if rounds is None else rounds
         minutes = self.cfg.render_minutes if minutes is None else minutes
         t0 = self.clock()
+        if aov_files and self.rank == 0:
+            a = self.render_aov()
+            for name, path in aov_files.items():
+                plane = a[name] if a[name].dim() == 3 else a[name].unsqueeze(-1).expand(-1, -1, 3)
+                write_exr(path, plane.cpu().numpy())
 
         def one():
             self.render_round()
             if output_file and self.rank == 0:
-                self.total_ob.write(output_file, getattr(self.cfg, "output_scale", -1.0))
+                val = self.total_ob.write(output_file, getattr(self.cfg, "output_scale", -1.0))
+                if denoised_file:
+                    write_exr(denoised_file, (self.denoise() * val).cpu().numpy())
             if checkpoint and self.rank == 0:
                 self.save_checkpoint(checkpoint)
         if minutes is None:
