@@ -213,6 +213,9 @@ int down(T* dst, const DevBuf<T>& b, size_t count) {
     return 0;
 }
 
+// The eight traversal-stats words: closest nodes / triangles, shadow nodes / triangles, and the walker's occupancy counters.
+int read_stats(const rgk_scene* s, unsigned long long (&h)[8]) { return down(h, s->stats, 8); }
+
 RgkTuning read_tuning() {
     auto off = [](const char* name) { const char* e = std::getenv(name); return e && e[0] == '0'; };
     RgkTuning t;
@@ -685,21 +688,23 @@ void add_pass_counters(const uint32_t* hc, const PassParams& pp, bool light_entr
     for (uint32_t k = 0; k < pp.reverse; k++) { c.path_rays += k == 0 ? n0 : hl[RGK_CNT_QUEUE + k]; c.shadow_rays += hl[RGK_CNT_SHADOW + k]; }
 }
 
-// The round's pixel list in Tracer::Render order and its per-pixel seeds (a1, a2), built on the device from the tile list, and
-// the camera rays' entry nodes per pixel group.  P: the round's pixels (0: nothing queued).  `toff` receives the tiles' offsets
-// into the list, which a queued copy reads: the caller keeps it until it has synchronised the stream.
-int prepare_round_lists(rgk_scene* s, const rgk_camera* camera, const rgk_params* prm, const rgk_tile* tiles, uint32_t n_tiles,
-                        std::vector<uint32_t>& toff, size_t& P) {
+// The tiles checked against the frame, and their offsets into the pixel list they make (toff[n_tiles]: its length).  Host only.
+// `what`: the caller's unit of work, for the error text.
+int tile_offsets(const rgk_params* prm, const rgk_tile* tiles, uint32_t n_tiles, const char* what, std::vector<uint32_t>& toff) {
     toff.assign(n_tiles + 1, 0u);
     for (uint32_t i = 0; i < n_tiles; i++) {
         const rgk_tile& t = tiles[i];
         if (t.x1 > prm->xres || t.y1 > prm->yres || t.x0 > t.x1 || t.y0 > t.y1) return fail(RGK_ERR_INVALID, "tile %u outside the frame", i);
         const uint64_t n = (uint64_t)toff[i] + (uint64_t)(t.x1 - t.x0) * (t.y1 - t.y0);
-        if (n >= (1ull << 31)) return fail(RGK_ERR_UNSUPPORTED, "more than 2^31 pixels in one round");
+        if (n >= (1ull << 31)) return fail(RGK_ERR_UNSUPPORTED, "more than 2^31 pixels in one %s", what);
         toff[i + 1] = (uint32_t)n;
     }
-    P = toff[n_tiles];
-    if (P == 0) return 0;
+    return 0;
+}
+// ... and that list (toff[n_tiles] > 0 pixels) in Tracer::Render order with its per-pixel seeds (a1, a2), built on the device from
+// the tile list.  A queued copy reads `toff`: the caller keeps it until it has synchronised the stream.
+int queue_pixel_list(rgk_scene* s, const rgk_tile* tiles, uint32_t n_tiles, const std::vector<uint32_t>& toff) {
+    const size_t P = toff[n_tiles];
     hipStream_t st = s->stream;
     int rc;
     if ((rc = s->pix_xy.alloc(P)) || (rc = s->pix_seed.alloc(P)) || (rc = s->tile_buf.alloc((size_t)n_tiles * 5 + n_tiles + 1))) return rc;
@@ -707,6 +712,18 @@ int prepare_round_lists(rgk_scene* s, const rgk_camera* camera, const rgk_params
     HIPCHK(hipMemcpyAsync(s->tile_buf.p, tiles, (size_t)n_tiles * sizeof(rgk_tile), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(s->tile_buf.p + (size_t)n_tiles * 5, toff.data(), (n_tiles + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     rgk_launch_build_pixel_list(st, reinterpret_cast<const rgk_tile*>(s->tile_buf.p), s->tile_buf.p + (size_t)n_tiles * 5, n_tiles, s->pix_xy.p, s->pix_seed.p);
+    return 0;
+}
+
+// The round's pixel list and the camera rays' entry nodes per pixel group.  P: the round's pixels (0: nothing queued).  `toff`:
+// see queue_pixel_list.
+int prepare_round_lists(rgk_scene* s, const rgk_camera* camera, const rgk_params* prm, const rgk_tile* tiles, uint32_t n_tiles,
+                        std::vector<uint32_t>& toff, size_t& P) {
+    int rc;
+    if ((rc = tile_offsets(prm, tiles, n_tiles, "round", toff))) return rc;
+    P = toff[n_tiles];
+    if (P == 0) return 0;
+    if ((rc = queue_pixel_list(s, tiles, n_tiles, toff))) return rc;
     if (!s->tune.entry_points) { // (off: every camera ray starts at the root)
         s->entry.release(); s->entry_cap.release();
         return 0;
@@ -722,7 +739,7 @@ int prepare_round_lists(rgk_scene* s, const rgk_camera* camera, const rgk_params
     if ((rc = s->entry.alloc(n_entry)) || (rc = s->entry_cap.alloc(n_entry / RGK_ENTRY_K + 1)) || (rc = s->trange.alloc((n_entry / RGK_ENTRY_K + 1) * 2))) return rc;
     DevCamera cam0;
     make_camera(camera, cam0);
-    rgk_launch_entry_points(st, s->dev, cam0, prm->xres, prm->yres, s->pix_xy.p, (uint32_t)P, 0u, (uint32_t)(n_entry / RGK_ENTRY_K), nullptr, s->entry.p, s->entry_cap.p);
+    rgk_launch_entry_points(s->stream, s->dev, cam0, prm->xres, prm->yres, s->pix_xy.p, (uint32_t)P, 0u, (uint32_t)(n_entry / RGK_ENTRY_K), nullptr, s->entry.p, s->entry_cap.p);
     s->entry_key = key; s->entry_n = n_entry;
     s->entry_capped = 0; s->lentry_done = 0; // a new frame: capped / light-side lists are rebuilt as its first passes finish
     return 0;
@@ -730,16 +747,13 @@ int prepare_round_lists(rgk_scene* s, const rgk_camera* camera, const rgk_params
 
 // The pass plan: pixel ranges of npix_pass pixels x equal-sized sample passes of ns_pass samples, and the workspace for them.
 // Paths per pass: what the card has room for now (an existing workspace counts as room); halved on an allocation failure.
-int plan_passes(rgk_scene* s, const rgk_params* prm, size_t P, uint32_t R, size_t& npix_pass, uint32_t& ns_pass) {
+int plan_passes(rgk_scene* s, const rgk_params* prm, size_t P, uint32_t R, RgkPassPlan& plan) {
     size_t B = batch_paths(s->tune, R);
     if (!s->tune.batch_paths && s->batch_reverse >= R) B = std::max(B, s->batch); // (an explicit batch size is taken literally)
     int rc;
     for (;;) {
-        npix_pass = std::min(P, B);
-        const uint32_t ns_max = (uint32_t)std::max<size_t>(1, std::min<size_t>(prm->multisample, B / npix_pass));
-        const uint32_t n_sample_passes = (prm->multisample + ns_max - 1) / ns_max;
-        ns_pass = (prm->multisample + n_sample_passes - 1) / n_sample_passes; // equal-sized passes
-        rc = ensure_workspace(s, npix_pass * ns_pass, R);
+        plan = rgk_plan_passes(P, prm->multisample, B);
+        rc = ensure_workspace(s, plan.npix_pass * plan.ns_pass, R);
         if (rc != RGK_ERR_OOM || B <= ((size_t)1 << 20)) break;
         (void)hipGetLastError();
         B /= 2;
@@ -754,13 +768,13 @@ int plan_passes(rgk_scene* s, const rgk_params* prm, size_t P, uint32_t R, size_
 int queue_first_hit_lists(rgk_scene* s, KernelLog& kl, const DevCamera& cam, PassParams& pp, uint32_t P, bool cap_entries, bool light_entry) {
     hipStream_t st = s->stream;
     const size_t end = (size_t)pp.j0 + pp.npix;
+    const RgkGroupRange groups = rgk_group_range(pp.j0, pp.npix);
     const bool need_cap = cap_entries && end > s->entry_capped;
     const bool need_light = light_entry && end > s->lentry_done;
     int rc;
     if ((need_cap || need_light) && (rc = kl.run(RGK_K_OTHER, [&] { rgk_launch_group_trange(st, pp, s->hit.p, s->trange.p); }))) return rc;
     if (need_cap) {
-        const uint32_t g_first = pp.j0 >> RGK_ENTRY_SHIFT, g_last = (uint32_t)((end + RGK_ENTRY_PIX - 1) >> RGK_ENTRY_SHIFT);
-        if ((rc = kl.run(RGK_K_OTHER, [&] { rgk_launch_entry_points(st, s->dev, cam, pp.xres, pp.yres, s->pix_xy.p, P, g_first, g_last - g_first, s->trange.p, s->entry.p, s->entry_cap.p); })))
+        if ((rc = kl.run(RGK_K_OTHER, [&] { rgk_launch_entry_points(st, s->dev, cam, pp.xres, pp.yres, s->pix_xy.p, P, groups.first, groups.count(), s->trange.p, s->entry.p, s->entry_cap.p); })))
             return rc;
         s->entry_capped = end;
     }
@@ -770,7 +784,7 @@ int queue_first_hit_lists(rgk_scene* s, KernelLog& kl, const DevCamera& cam, Pas
     if ((rc = kl.run(RGK_K_OTHER, [&] { rgk_launch_light_entry_points(st, s->dev, cam, pp, P, s->trange.p, s->lentry.p, s->lbox.p); }))) return rc;
     s->lentry_done = end;
     if (s->tune.debug_bvh) { // how many pixel groups got light-side entry nodes below the root
-        const size_t g0 = pp.j0 >> RGK_ENTRY_SHIFT, g1 = (end + RGK_ENTRY_PIX - 1) >> RGK_ENTRY_SHIFT;
+        const size_t g0 = groups.first, g1 = groups.last;
         std::vector<int> he((g1 - g0) * RGK_ENTRY_K);
         HIPCHK(hipStreamSynchronize(st));
         HIPCHK(hipMemcpy(he.data(), s->lentry.p + g0 * RGK_ENTRY_K, he.size() * sizeof(int), hipMemcpyDeviceToHost));
@@ -791,17 +805,9 @@ int queue_pass(rgk_scene* s, KernelLog& kl, const DevCamera& cam, PassParams& pp
     const bool count_stats = kl.count_stats, cap_entries = s->entry.p != nullptr && s->tune.entry_cap;
     const bool track = pp.depth > 12; // queue lengths read back (queue_len): measured, depth 10 loses 4 % to the read-backs, depth 40 gains 4 %
     const uint32_t R = pp.reverse, n0 = pp.npix * pp.ns;
-    {   // 2^gshift samples of a pixel side by side in the slot order (rgk_kernels.h PassParams); RGK_SAMPLE_GROUP = log2
-        uint32_t g = s->tune.sample_group >= 0 ? (uint32_t)s->tune.sample_group : (uint32_t)RGK_SAMPLE_GROUP_DEFAULT;
-        while (g && (pp.ns & ((1u << g) - 1u))) g--;
-        pp.gshift = g;
-        // the bundle walk (k_trace_camera_beam) for passes whose entry lists are not capped yet -- a frame's first round:
-        // measured on the headline workload, camera launch 20.6 (per ray, uncapped) -> 17.2 ms (bundles), a one-round
-        // frame 135.2 -> 130.8 ms; against CAPPED lists the per-ray walk is the faster one (16.1 vs 17.2: a bundle tests
-        // every triangle it meets against all 8 rays, 2.86 tests per ray instead of 2.57, at half the occupancy)
-        const bool lists_capped = cap_entries && (size_t)pp.j0 + pp.npix <= s->entry_capped;
-        pp.beam = (s->tune.beam == 2 || (s->tune.beam == 1 && !lists_capped)) ? 1u : 0u;
-    }
+    // the slot order, and the bundle walk for passes whose entry lists are not capped yet -- a frame's first round (rgk_plan.h)
+    pp.gshift = rgk_plan_gshift(s->tune.sample_group, RGK_SAMPLE_GROUP_DEFAULT, pp.ns);
+    pp.beam = rgk_beam_wanted(s->tune.beam, cap_entries && (size_t)pp.j0 + pp.npix <= s->entry_capped) ? 1u : 0u;
     float4* const rayA[2] = {s->rayA[0].p, s->rayA[1].p};
     float4* const rayB[2] = {s->rayB[0].p, s->rayB[1].p};
     float4 *const hit = s->hit.p, *const thr = s->thr.p, *const tot = s->tot.p, *const shA = s->shA.p, *const shB = s->shB.p, *const shC = s->shC.p;
@@ -810,46 +816,44 @@ int queue_pass(rgk_scene* s, KernelLog& kl, const DevCamera& cam, PassParams& pp
     int rc;
     if (R > 0) {
         // light sub-path first (its sampler dimensions are fixed), splats straight into the accumulator
-        rgk_launch_set_bound(n0, n0);
         if ((rc = kl.run(RGK_K_OTHER, [&] { rgk_launch_init_counters(st, cl, 0u); })) || // (k_raygen_light queues the light rays that can touch the scene's box)
             (rc = kl.run(RGK_K_LIGHT_SHADE, [&] { rgk_launch_raygen_light(st, s->dev, cam, pp, rayA[0], rayB[0], thr, cl); })))
             return rc;
         for (uint32_t k = 0; k < R; k++) {
             const int q = k & 1;
-            if ((rc = kl.run(RGK_K_LIGHT_TRACE, [&] { rgk_launch_trace_closest(st, s->dev, tc, count_stats, rayA[q], rayB[q], nullptr, hit, cl + RGK_CNT_QUEUE + k, cl + RGK_CNT_FETCH_T + k, s->stats.p); })) ||
-                (rc = kl.run(RGK_K_LIGHT_SHADE, [&] { rgk_launch_list_hits(st, hit, cl + RGK_CNT_QUEUE + k, s->hitlist.p, cl + RGK_CNT_HITS + k); })) ||
-                (rc = kl.run(RGK_K_LIGHT_SHADE, [&] { rgk_launch_shade_light(st, s->dev, cam, pp, k, rayA[q], rayB[q], hit, thr, rayA[q ^ 1], rayB[q ^ 1], shA, shB, shC, cl); })) ||
+            if ((rc = kl.run(RGK_K_LIGHT_TRACE, [&] { rgk_launch_trace_closest(st, s->dev, tc, count_stats, rayA[q], rayB[q], nullptr, hit, {n0, cl + RGK_CNT_QUEUE + k, cl + RGK_CNT_FETCH_T + k}, s->stats.p); })) ||
+                (rc = kl.run(RGK_K_LIGHT_SHADE, [&] { rgk_launch_list_hits(st, hit, cl + RGK_CNT_QUEUE + k, s->hitlist.p, cl + RGK_CNT_HITS + k, n0); })) ||
+                (rc = kl.run(RGK_K_LIGHT_SHADE, [&] { rgk_launch_shade_light(st, s->dev, cam, pp, k, rayA[q], rayB[q], hit, thr, rayA[q ^ 1], rayB[q ^ 1], shA, shB, shC, cl, n0); })) ||
                 (rc = kl.run(RGK_K_LIGHT_SPLAT, [&] { rgk_launch_trace_shadow(st, s->dev, tc, count_stats, shA, shB, shC, nullptr, nullptr, RGK_SHADOW_SPLAT, d_accum_rgb,
-                                                                              cl + RGK_CNT_SHADOW + k, cl + RGK_CNT_FETCH_S + k, s->stats.p); })))
+                                                                              {n0, cl + RGK_CNT_SHADOW + k, cl + RGK_CNT_FETCH_S + k}, s->stats.p); })))
                 return rc;
         }
     }
     // the camera path: the same pipeline for uni- and bidirectional rounds (R > 0: vertices with connections take the record
     // route -- k_shade<BDPT> -> k_connect -> k_trace_shadow_jobs -- beside the plain NEE rays)
     if ((rc = kl.run(RGK_K_OTHER, [&] { rgk_launch_init_counters(st, cn, n0); }))) return rc;
-    uint32_t ub = n0; // upper bound on bounce b's queue
+    uint32_t ub = n0; // upper bound on bounce b's queues: every launch of the bounce sizes its grid by it
     for (uint32_t b = 0; b < pp.depth && ub > 0; b++) {
         const int q = b & 1;
-        rgk_launch_set_bound(ub, ub);
+        const RgkWalk wq = {ub, cn + RGK_CNT_QUEUE + b, cn + RGK_CNT_FETCH_T + b}, ws = {ub, cn + RGK_CNT_SHADOW + b, cn + RGK_CNT_FETCH_S + b};
         if (b == 0) // no ray queue at bounce 0: the camera ray of slot i is made where it is traced and shaded
-            rc = kl.run(RGK_K_TRACE_CAMERA, [&] { rgk_launch_trace_camera(st, s->dev, cam, pp, tc, count_stats, hit, cn + RGK_CNT_QUEUE, cn + RGK_CNT_FETCH_T, s->stats.p); });
+            rc = kl.run(RGK_K_TRACE_CAMERA, [&] { rgk_launch_trace_camera(st, s->dev, cam, pp, tc, count_stats, hit, wq, s->stats.p); });
         else
-            rc = kl.run(RGK_K_TRACE_CLOSEST, [&] { rgk_launch_trace_closest(st, s->dev, tc, count_stats, rayA[q], rayB[q], nullptr, hit, cn + RGK_CNT_QUEUE + b, cn + RGK_CNT_FETCH_T + b, s->stats.p); });
+            rc = kl.run(RGK_K_TRACE_CLOSEST, [&] { rgk_launch_trace_closest(st, s->dev, tc, count_stats, rayA[q], rayB[q], nullptr, hit, wq, s->stats.p); });
         if (rc || (b == 0 && (rc = queue_first_hit_lists(s, kl, cam, pp, (uint32_t)P, cap_entries, light_entry)))) return rc;
-        if ((rc = kl.run(b == 0 ? RGK_K_SHADE_FIRST : RGK_K_SHADE, [&] { rgk_launch_shade(st, s->dev, cam, pp, b, rayA[q], rayB[q], hit, thr, tot, rayA[q ^ 1], rayB[q ^ 1], shA, shB, shC, cn, R > 0, const_light); })) ||
-            (R > 0 && (rc = kl.run(RGK_K_CONNECT, [&] { rgk_launch_connect(st, s->dev, pp, b, s->jobs.p, s->rads.p, cn); }))))
+        if ((rc = kl.run(b == 0 ? RGK_K_SHADE_FIRST : RGK_K_SHADE, [&] { rgk_launch_shade(st, s->dev, cam, pp, b, rayA[q], rayB[q], hit, thr, tot, rayA[q ^ 1], rayB[q ^ 1], shA, shB, shC, cn, ub, R > 0, const_light); })) ||
+            (R > 0 && (rc = kl.run(RGK_K_CONNECT, [&] { rgk_launch_connect(st, s->dev, pp, b, s->jobs.p, s->rads.p, cn, ub); }))))
             return rc;
         // (the constant-light route: the shading launches above left 32-byte records, shA = {d, far}, shB = {radiance, slot})
-        if (const_light && rgk_const_light_records() && b == 0 && light_entry)
-            rc = kl.run(RGK_K_SHADOW_FIRST, [&] { rgk_launch_trace_shadow_first_cl(st, s->dev, pp, tc, count_stats, shA, shB, tot, cn + RGK_CNT_SHADOW + b, cn + RGK_CNT_FETCH_S + b, s->stats.p); });
-        else if (const_light && rgk_const_light_records())
-            rc = kl.run(RGK_K_SHADOW, [&] { rgk_launch_trace_shadow_cl(st, s->dev, tc, count_stats, shA, shB, tot, cn + RGK_CNT_SHADOW + b, cn + RGK_CNT_FETCH_S + b, s->stats.p); });
-        else if (b == 0 && light_entry)
-            rc = kl.run(RGK_K_SHADOW_FIRST, [&] { rgk_launch_trace_shadow_first(st, s->dev, pp, tc, count_stats, shA, shB, shC, tot, cn + RGK_CNT_SHADOW + b, cn + RGK_CNT_FETCH_S + b, s->stats.p); });
-        else
-            rc = kl.run(RGK_K_SHADOW, [&] { rgk_launch_trace_shadow(st, s->dev, tc, count_stats, shA, shB, shC, tot, nullptr, RGK_SHADOW_ADD, nullptr, cn + RGK_CNT_SHADOW + b, cn + RGK_CNT_FETCH_S + b, s->stats.p); });
+        const bool first = b == 0 && light_entry, rec32 = const_light && rgk_const_light_records();
+        rc = kl.run(first ? RGK_K_SHADOW_FIRST : RGK_K_SHADOW, [&] {
+            if (rec32 && first) rgk_launch_trace_shadow_first_cl(st, s->dev, pp, tc, count_stats, shA, shB, tot, ws, s->stats.p);
+            else if (rec32) rgk_launch_trace_shadow_cl(st, s->dev, tc, count_stats, shA, shB, tot, ws, s->stats.p);
+            else if (first) rgk_launch_trace_shadow_first(st, s->dev, pp, tc, count_stats, shA, shB, shC, tot, ws, s->stats.p);
+            else rgk_launch_trace_shadow(st, s->dev, tc, count_stats, shA, shB, shC, tot, nullptr, RGK_SHADOW_ADD, nullptr, ws, s->stats.p);
+        });
         // (the vertex queue after the plain rays: both add into the slot sums, a slot has a vertex in ONE of the two queues)
-        if (rc || (R > 0 && (rc = kl.run(RGK_K_SHADOW_JOBS, [&] { rgk_launch_trace_shadow_jobs(st, s->dev, pp, tc, count_stats, s->jobs.p, s->rads.p, tot, cn + RGK_CNT_CONN + b, cn + RGK_CNT_FETCH_J + b, s->stats.p); }))))
+        if (rc || (R > 0 && (rc = kl.run(RGK_K_SHADOW_JOBS, [&] { rgk_launch_trace_shadow_jobs(st, s->dev, pp, tc, count_stats, s->jobs.p, s->rads.p, tot, {ub, cn + RGK_CNT_CONN + b, cn + RGK_CNT_FETCH_J + b}, s->stats.p); }))))
             return rc;
         rgk_launch_stage_mark(st, s->h_stage, stage + b + 1);
         if (track && b >= 3 && (b & 1) && b + 1 < pp.depth && (rc = queue_len(s, cn + RGK_CNT_QUEUE + b + 1, ub))) return rc;
@@ -874,14 +878,14 @@ int rgk_render_round_device(rgk_scene* s, const rgk_camera* camera, const rgk_pa
     HIPCHK(hipSetDevice(s->device));
     if (counters) std::memset(counters, 0, sizeof(*counters));
     std::vector<uint32_t> toff; // (read by a queued copy: it lives to the end of this call, which synchronises the stream before returning)
-    size_t P = 0, npix_pass = 0;
-    uint32_t ns_pass = 0;
+    size_t P = 0;
+    RgkPassPlan plan{};
     int rc;
     if ((rc = prepare_round_lists(s, camera, prm, tiles, n_tiles, toff, P))) return rc;
     if (P == 0) return RGK_OK;
     // no light at all: TracePath builds no light sub-path (`reverse > 0 && valid light`), same as reverse == 0
     const uint32_t R = (s->dev.total_point_power + s->dev.total_areal_power > 0.0f) ? prm->reverse : 0u;
-    if ((rc = plan_passes(s, prm, P, R, npix_pass, ns_pass))) return rc;
+    if ((rc = plan_passes(s, prm, P, R, plan))) return rc;
 
     DevCamera cam;
     make_camera(camera, cam);
@@ -892,7 +896,7 @@ int rgk_render_round_device(rgk_scene* s, const rgk_camera* camera, const rgk_pa
     // round trip per mark)
     const uint32_t pass_stages = std::max(1u, prm->depth);
     {
-        const uint32_t n_pix_passes = (uint32_t)((P + npix_pass - 1) / npix_pass), n_s_passes = (prm->multisample + ns_pass - 1) / ns_pass;
+        const uint32_t n_pix_passes = (uint32_t)((P + plan.npix_pass - 1) / plan.npix_pass), n_s_passes = (prm->multisample + plan.ns_pass - 1) / plan.ns_pass;
         *(volatile uint32_t*)s->h_stage = 0; s->prog_stages = n_pix_passes * n_s_passes * pass_stages;
         s->prog_pixels = P; s->prog_paths = (uint64_t)P * prm->multisample; s->prog_busy = 1;
     }
@@ -919,12 +923,12 @@ int rgk_render_round_device(rgk_scene* s, const rgk_camera* camera, const rgk_pa
 
     rgk_counters tot{};
     uint32_t stage = 0; // progress stages of the passes before this one
-    for (size_t j0 = 0; j0 < P; j0 += npix_pass) {
+    for (size_t j0 = 0; j0 < P; j0 += plan.npix_pass) {
         pp.j0 = (uint32_t)j0;
-        pp.npix = (uint32_t)std::min(npix_pass, P - j0);
-        for (uint32_t s0 = 0; s0 < prm->multisample; s0 += ns_pass, stage += pass_stages) {
+        pp.npix = (uint32_t)std::min(plan.npix_pass, P - j0);
+        for (uint32_t s0 = 0; s0 < prm->multisample; s0 += plan.ns_pass, stage += pass_stages) {
             pp.s0 = s0;
-            pp.ns = std::min(ns_pass, prm->multisample - s0);
+            pp.ns = std::min(plan.ns_pass, prm->multisample - s0);
             if ((rc = queue_pass(s, kl, cam, pp, P, light_entry, const_light, d_accum_rgb, d_accum_count, stage))) return rc;
             HIPCHK(hipStreamSynchronize(s->stream));
             add_pass_counters(s->h_counters, pp, light_entry, tot);
@@ -936,7 +940,7 @@ int rgk_render_round_device(rgk_scene* s, const rgk_camera* camera, const rgk_pa
         tot.paths = (uint64_t)P * prm->multisample;
         if (kl.count_stats) {
             unsigned long long h[8];
-            HIPCHK(hipMemcpy(h, s->stats.p, sizeof(h), hipMemcpyDeviceToHost));
+            if ((rc = read_stats(s, h))) return rc;
             tot.node_visits = h[0]; tot.tri_tests = h[1]; tot.shadow_node_visits = h[2]; tot.shadow_tri_tests = h[3];
         }
         if ((rc = kl.fold(tot))) return rc;
@@ -987,17 +991,15 @@ int rgk_trace_closest(rgk_scene* s, uint32_t n, const float* rays, const int32_t
     HIPCHK(hipMemsetAsync(s->stats.p, 0, 8 * sizeof(unsigned long long), st));
     rgk_launch_init_counters(st, s->counters.p, n);
     rgk_launch_pack_rays(st, n, s->scratch_f.p, d_ign, s->rayA[0].p, s->rayB[0].p, s->nearfar.p);
-    rgk_launch_set_bound(n, n);
+    const RgkWalk w = {n, s->counters.p + RGK_CNT_QUEUE, s->counters.p + RGK_CNT_FETCH_T};
     hipEvent_t e0 = nullptr, e1 = nullptr; // kernel time of the traversal alone, for counters->ms_trace
     if (counters) { HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1)); HIPCHK(hipEventRecord(e0, st)); }
-    rgk_launch_trace_closest(st, s->dev, s->tcfg, false, s->rayA[0].p, s->rayB[0].p, s->nearfar.p, s->hit.p,
-                             s->counters.p + RGK_CNT_QUEUE, s->counters.p + RGK_CNT_FETCH_T, s->stats.p);
+    rgk_launch_trace_closest(st, s->dev, s->tcfg, false, s->rayA[0].p, s->rayB[0].p, s->nearfar.p, s->hit.p, w, s->stats.p);
     if (counters) {
         HIPCHK(hipEventRecord(e1, st));
         // the counting variant runs separately so that the timed launch is the kernel a round runs
         rgk_launch_init_counters(st, s->counters.p, n);
-        rgk_launch_trace_closest(st, s->dev, s->tcfg, true, s->rayA[0].p, s->rayB[0].p, s->nearfar.p, s->hit.p,
-                                 s->counters.p + RGK_CNT_QUEUE, s->counters.p + RGK_CNT_FETCH_T, s->stats.p);
+        rgk_launch_trace_closest(st, s->dev, s->tcfg, true, s->rayA[0].p, s->rayB[0].p, s->nearfar.p, s->hit.p, w, s->stats.p);
     }
     rgk_hit* d_hits = (rgk_hit*)s->scratch_u.p; // 5 dwords per hit; reuses the ignore buffer after the trace
     rgk_launch_unpack_hits(st, n, s->hit.p, d_hits);
@@ -1006,7 +1008,7 @@ int rgk_trace_closest(rgk_scene* s, uint32_t n, const float* rays, const int32_t
     HIPCHK(hipGetLastError());
     if (counters) {
         unsigned long long h[8];
-        HIPCHK(hipMemcpy(h, s->stats.p, sizeof(h), hipMemcpyDeviceToHost));
+        if ((rc = read_stats(s, h))) return rc;
         counters->node_visits = h[0]; counters->tri_tests = h[1]; counters->path_rays = n;
         if (s->tune.debug_util) // lane occupancy per phase of the walker: lane-visits / (64 x wave iterations)
             std::fprintf(stderr, "[rgk util] rays %u  node visits %llu in %llu wave iterations (%.3f of lanes)  triangle tests %llu in %llu (%.3f)  outer iterations %llu  refills %llu\n",
@@ -1032,15 +1034,14 @@ int rgk_trace_visibility(rgk_scene* s, uint32_t n, const float* a, const float* 
     HIPCHK(hipMemsetAsync(s->stats.p, 0, 8 * sizeof(unsigned long long), st));
     rgk_launch_init_counters(st, s->counters.p, n);
     rgk_launch_pack_visibility(st, s->dev, n, s->scratch_f.p, s->scratch_f.p + (size_t)3 * n, s->shA.p, s->shB.p, s->shC.p);
-    rgk_launch_set_bound(n, n);
     rgk_launch_trace_shadow(st, s->dev, s->tcfg, counters != nullptr, s->shA.p, s->shB.p, s->shC.p, s->tot.p, (uint8_t*)s->scratch_u.p,
-                            RGK_SHADOW_ADD, nullptr, s->counters.p + RGK_CNT_QUEUE, s->counters.p + RGK_CNT_FETCH_S, s->stats.p);
+                            RGK_SHADOW_ADD, nullptr, {n, s->counters.p + RGK_CNT_QUEUE, s->counters.p + RGK_CNT_FETCH_S}, s->stats.p);
     HIPCHK(hipMemcpyAsync(visible, s->scratch_u.p, n, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     HIPCHK(hipGetLastError());
     if (counters) {
         unsigned long long h[8];
-        HIPCHK(hipMemcpy(h, s->stats.p, sizeof(h), hipMemcpyDeviceToHost));
+        if ((rc = read_stats(s, h))) return rc;
         counters->shadow_node_visits = h[2]; counters->shadow_tri_tests = h[3]; counters->shadow_rays = n;
     }
     return RGK_OK;
@@ -1158,14 +1159,11 @@ struct PostTimer {
     }
 };
 
-int check_aov_args(const rgk_scene* s, const rgk_camera* camera, const rgk_params* prm, const rgk_tile* tiles, uint32_t n_tiles) {
+// (every check before the scene or the device is touched; `toff`: tile_offsets)
+int check_aov_args(const rgk_scene* s, const rgk_camera* camera, const rgk_params* prm, const rgk_tile* tiles, uint32_t n_tiles, std::vector<uint32_t>& toff) {
     if (!s || !camera || !prm || (!tiles && n_tiles)) return fail(RGK_ERR_INVALID, "null argument");
     if (prm->xres == 0 || prm->yres == 0 || prm->xres > 65535 || prm->yres > 65535) return fail(RGK_ERR_INVALID, "resolution out of range");
-    for (uint32_t i = 0; i < n_tiles; i++) {
-        const rgk_tile& t = tiles[i];
-        if (t.x1 > prm->xres || t.y1 > prm->yres || t.x0 > t.x1 || t.y0 > t.y1) return fail(RGK_ERR_INVALID, "tile %u outside the frame", i);
-    }
-    return 0;
+    return tile_offsets(prm, tiles, n_tiles, "feature pass", toff);
 }
 } // namespace
 
@@ -1174,14 +1172,9 @@ extern "C" {
 int rgk_render_aov_device(rgk_scene* s, const rgk_camera* camera, const rgk_params* prm, const rgk_tile* tiles, uint32_t n_tiles, float* d_albedo,
                           float* d_normal, float* d_depth, int32_t* d_tri) {
     int rc;
-    if ((rc = check_aov_args(s, camera, prm, tiles, n_tiles))) return rc;
+    std::vector<uint32_t> toff; // (read by a queued copy: lives until the stream has been waited for)
+    if ((rc = check_aov_args(s, camera, prm, tiles, n_tiles, toff))) return rc;
     if (s->prog_busy.load()) return fail(RGK_ERR_INVALID, "rgk_render_aov_device while a round is in flight on this scene");
-    std::vector<uint32_t> toff(n_tiles + 1, 0u); // (read by a queued copy: lives until the stream has been waited for)
-    for (uint32_t i = 0; i < n_tiles; i++) {
-        const uint64_t total = (uint64_t)toff[i] + (uint64_t)(tiles[i].x1 - tiles[i].x0) * (tiles[i].y1 - tiles[i].y0);
-        if (total >= (1ull << 31)) return fail(RGK_ERR_UNSUPPORTED, "more than 2^31 pixels in one feature pass");
-        toff[i + 1] = (uint32_t)total;
-    }
     const uint32_t n = toff[n_tiles];
     s->post_ms[0].clear();
     if (n == 0) return RGK_OK;
@@ -1189,21 +1182,17 @@ int rgk_render_aov_device(rgk_scene* s, const rgk_camera* camera, const rgk_para
     // The round's own buffers: its pixel list (rebuilt by every round before it is read), two ray planes and the hit plane of
     // the workspace (written by every pass before they are read).  The frame's cached lists -- entry nodes, their caps, the
     // light-side entries -- are neither read nor written here, so the rounds of a frame compute the same with or without this call.
-    if ((rc = ensure_workspace(s, n)) || (rc = s->pix_xy.alloc(n)) || (rc = s->pix_seed.alloc(n)) || (rc = s->tile_buf.alloc((size_t)n_tiles * 5 + n_tiles + 1))) return rc;
+    if ((rc = ensure_workspace(s, n))) return rc;
     hipStream_t st = s->stream;
     PostTimer tm(s);
-    HIPCHK(hipMemcpyAsync(s->tile_buf.p, tiles, (size_t)n_tiles * sizeof(rgk_tile), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(s->tile_buf.p + (size_t)n_tiles * 5, toff.data(), (n_tiles + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     DevCamera cam;
     make_camera(camera, cam);
     cam.lens_size = 0.0f; // every feature ray leaves from the camera's origin
-    if ((rc = tm.mark())) return rc;
-    rgk_launch_build_pixel_list(st, reinterpret_cast<const rgk_tile*>(s->tile_buf.p), s->tile_buf.p + (size_t)n_tiles * 5, n_tiles, s->pix_xy.p, s->pix_seed.p);
+    if ((rc = tm.mark()) || (rc = queue_pixel_list(s, tiles, n_tiles, toff))) return rc;
     rgk_launch_init_counters(st, s->counters.p, n);
     rgk_launch_aov_raygen(st, cam, prm->xres, prm->yres, s->pix_xy.p, n, s->rayA[0].p, s->rayB[0].p);
     if ((rc = tm.mark())) return rc;
-    rgk_launch_set_bound(n, n);
-    rgk_launch_trace_closest(st, s->dev, s->tcfg, false, s->rayA[0].p, s->rayB[0].p, nullptr, s->hit.p, s->counters.p + RGK_CNT_QUEUE, s->counters.p + RGK_CNT_FETCH_T, s->stats.p);
+    rgk_launch_trace_closest(st, s->dev, s->tcfg, false, s->rayA[0].p, s->rayB[0].p, nullptr, s->hit.p, {n, s->counters.p + RGK_CNT_QUEUE, s->counters.p + RGK_CNT_FETCH_T}, s->stats.p);
     if ((rc = tm.mark())) return rc;
     rgk_launch_aov_gather(st, s->dev, prm->bumpmap_scale, prm->xres, s->pix_xy.p, n, s->rayA[0].p, s->rayB[0].p, s->hit.p, d_albedo, d_normal, d_depth, d_tri);
     if ((rc = tm.mark())) return rc;
@@ -1215,7 +1204,8 @@ int rgk_render_aov_device(rgk_scene* s, const rgk_camera* camera, const rgk_para
 int rgk_render_aov(rgk_scene* s, const rgk_camera* camera, const rgk_params* prm, const rgk_tile* tiles, uint32_t n_tiles, float* albedo, float* normal,
                    float* depth, int32_t* tri) {
     int rc;
-    if ((rc = check_aov_args(s, camera, prm, tiles, n_tiles))) return rc;
+    std::vector<uint32_t> toff;
+    if ((rc = check_aov_args(s, camera, prm, tiles, n_tiles, toff))) return rc;
     HIPCHK(hipSetDevice(s->device));
     const size_t P = (size_t)prm->xres * prm->yres;
     DevBuf<float> d_alb, d_nrm, d_z;

@@ -2,21 +2,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "device_types.h"
+#include "rgk_plan.h" // block sizes, pixel groups, RgkTraceCfg; every grid a launch below takes
 
-#ifndef RGK_TRACE_BLOCK
-#define RGK_TRACE_BLOCK 256
-#endif
 #ifndef RGK_SHADE_WAVES
 #define RGK_SHADE_WAVES 4 // waves per SIMD the shade kernel is compiled for (128 VGPRs)
-#endif
-#ifndef RGK_SHADE_BLOCK
-#define RGK_SHADE_BLOCK 512
-#endif
-#ifndef RGK_LIGHT_BLOCK
-#define RGK_LIGHT_BLOCK RGK_SHADE_BLOCK // the light sub-path's kernels (rgk_bdpt.h)
-#endif
-#ifndef RGK_SHADE_BLOCK_LATER
-#define RGK_SHADE_BLOCK_LATER 256 // k_shade at bounce >= 1 (see there)
 #endif
 #define RGK_MAX_DEPTH 62
 #define RGK_LV_FLOAT4 6 // float4 per stored light vertex: {pos,mat}{lightN,u}{Vr,v}{light_from_source,valid}{diffuse colour}{specular colour}
@@ -40,11 +29,6 @@
 #ifndef RGK_ENTRY_K
 #define RGK_ENTRY_K 6 // entry nodes per pixel group (unused ones hold the traversal's stack sentinel)
 #endif
-#ifndef RGK_ENTRY_SHIFT
-#define RGK_ENTRY_SHIFT 3 // log2 of the pixels per group: consecutive pixels of the round's list (8x8 blocks, row-major inside: a row of 8)
-// (Sponza proxy, ms per round: off 146.6; K, pixels = 4, 64: 138.8; 8, 64: 137.5; 4, 16: 139.4; 4, 8: 139.1; 6, 8: 136.3; 8, 8: 136.2)
-#endif
-#define RGK_ENTRY_PIX (1u << RGK_ENTRY_SHIFT)
 // One pass = pixels [j0, j0+npix) of the round's pixel list x samples [s0, s0+ns).
 // Path slot = ((srel >> g) * npix + j) << g | (srel & (2^g - 1)) with srel = s - s0, j = pixel - j0, g = gshift: 2^g consecutive
 // samples of a pixel sit side by side, so a wave of 64 slots is 64 >> g neighbouring pixels x 2^g samples -- rays that differ by
@@ -94,42 +78,37 @@ void rgk_launch_stage_mark(hipStream_t st, uint32_t* host_word, uint32_t v); // 
 void rgk_launch_init_counters(hipStream_t st, uint32_t* counters, uint32_t n0);
 void rgk_launch_build_pixel_list(hipStream_t st, const rgk_tile* tiles, const uint32_t* tile_off, uint32_t n_tiles, uint32_t* pix_xy, uint32_t* pix_seed);
 void rgk_launch_build_halton_table(hipStream_t st, const DevScene& sc, uint32_t S, float* htab);
-// traversal-stack configuration of a scene: entries its tree can need, how many of them live in LDS, overflow area
-struct RgkTraceCfg {
-    int stack, lds;
-    int* ovf;
-};
-int rgk_trace_grid(int lds_entries);
-// upper bounds on the queue lengths the following launches consume (grids shrink accordingly); 0xffffffff = unknown
-void rgk_launch_set_bound(uint32_t items, uint32_t shadow_items); // workgroups of a persistent trace launch (LDS-limited residency x 256 CUs)
+// What a persistent walker consumes: the queue counter it reads its length from, its work-fetch cursor, and the caller's upper
+// bound on that length, which sizes the grid (rgk_plan.h rgk_bounded_grid).  The launches that take a plain `bound` size theirs
+// the same way.
+struct RgkWalk { uint32_t bound; const uint32_t* count_ptr; uint32_t* fetch; };
 void rgk_launch_trace_camera(hipStream_t st, const DevScene& sc, const DevCamera& cam, const PassParams& pp, const RgkTraceCfg& tc, bool count_stats, float4* hit,
-                             const uint32_t* count_ptr, uint32_t* fetch, unsigned long long* stats);
+                             const RgkWalk& w, unsigned long long* stats);
 void rgk_launch_trace_closest(hipStream_t st, const DevScene& sc, const RgkTraceCfg& tc, bool count_stats, const float4* rayA, const float4* rayB,
-                              const float2* nearfar, float4* hit, const uint32_t* count_ptr, uint32_t* fetch, unsigned long long* stats);
+                              const float2* nearfar, float4* hit, const RgkWalk& w, unsigned long long* stats);
 void rgk_launch_trace_shadow(hipStream_t st, const DevScene& sc, const RgkTraceCfg& tc, bool count_stats, const float4* shA, const float4* shB,
-                             const float4* shC, float4* tot, uint8_t* vis_out, int mode, float* splat_rgb, const uint32_t* count_ptr,
-                             uint32_t* fetch, unsigned long long* stats);
+                             const float4* shC, float4* tot, uint8_t* vis_out, int mode, float* splat_rgb, const RgkWalk& w, unsigned long long* stats);
 void rgk_launch_trace_shadow_first(hipStream_t st, const DevScene& sc, const PassParams& pp, const RgkTraceCfg& tc, bool count_stats, const float4* shA, const float4* shB,
-                                   const float4* shC, float4* tot, const uint32_t* count_ptr, uint32_t* fetch, unsigned long long* stats);
+                                   const float4* shC, float4* tot, const RgkWalk& w, unsigned long long* stats);
 void rgk_launch_raygen_light(hipStream_t st, const DevScene& sc, const DevCamera& cam, const PassParams& pp, float4* rayA, float4* rayB,
                              float4* thr, uint32_t* counters);
 void rgk_launch_shade_light(hipStream_t st, const DevScene& sc, const DevCamera& cam, const PassParams& pp, uint32_t k, const float4* rayA,
                             const float4* rayB, const float4* hit, float4* thr, float4* nextA, float4* nextB, float4* shA, float4* shB,
-                            float4* shC, uint32_t* counters);
-void rgk_launch_list_hits(hipStream_t st, const float4* hit, const uint32_t* count_ptr, uint32_t* list, uint32_t* list_count);
-void rgk_launch_connect(hipStream_t st, const DevScene& sc, const PassParams& pp, uint32_t bounce, float4* jobs, float4* rads, uint32_t* counters);
+                            float4* shC, uint32_t* counters, uint32_t bound);
+void rgk_launch_list_hits(hipStream_t st, const float4* hit, const uint32_t* count_ptr, uint32_t* list, uint32_t* list_count, uint32_t bound);
+void rgk_launch_connect(hipStream_t st, const DevScene& sc, const PassParams& pp, uint32_t bounce, float4* jobs, float4* rads, uint32_t* counters, uint32_t bound);
 void rgk_launch_trace_shadow_jobs(hipStream_t st, const DevScene& sc, const PassParams& pp, const RgkTraceCfg& tc, bool count_stats, const float4* jobs, const float4* rads,
-                                  float4* tot, const uint32_t* count_ptr, uint32_t* fetch, unsigned long long* stats);
+                                  float4* tot, const RgkWalk& w, unsigned long long* stats);
 void rgk_launch_shade(hipStream_t st, const DevScene& sc, const DevCamera& cam, const PassParams& pp, uint32_t bounce, const float4* rayA,
                       const float4* rayB, const float4* hit, float4* thr, float4* tot, float4* nextA, float4* nextB, float4* shA,
-                      float4* shB, float4* shC, uint32_t* counters, bool bdpt = false, bool const_light = false);
+                      float4* shB, float4* shC, uint32_t* counters, uint32_t bound, bool bdpt = false, bool const_light = false);
 // the constant-light route (rgk.h rgk_scene_info::const_light; never with bdpt): rgk_launch_shade(const_light = true) queues shadow
 // rays as shA = {d.xyz, far}, shB = {radiance.rgb, slot} when rgk_const_light_records() says so, and these two trace them
 bool rgk_const_light_records();
 void rgk_launch_trace_shadow_cl(hipStream_t st, const DevScene& sc, const RgkTraceCfg& tc, bool count_stats, const float4* shA, const float4* shB,
-                                float4* tot, const uint32_t* count_ptr, uint32_t* fetch, unsigned long long* stats);
+                                float4* tot, const RgkWalk& w, unsigned long long* stats);
 void rgk_launch_trace_shadow_first_cl(hipStream_t st, const DevScene& sc, const PassParams& pp, const RgkTraceCfg& tc, bool count_stats, const float4* shA, const float4* shB,
-                                      float4* tot, const uint32_t* count_ptr, uint32_t* fetch, unsigned long long* stats);
+                                      float4* tot, const RgkWalk& w, unsigned long long* stats);
 void rgk_launch_resolve(hipStream_t st, const PassParams& pp, const float4* tot, float4* pixsum, float* accum_rgb, uint32_t* accum_count);
 void rgk_launch_pack_rays(hipStream_t st, uint32_t n, const float* rays, const int32_t* ignore, float4* rayA, float4* rayB, float2* nearfar);
 void rgk_launch_pack_visibility(hipStream_t st, const DevScene& sc, uint32_t n, const float* a, const float* b, float4* shA, float4* shB,

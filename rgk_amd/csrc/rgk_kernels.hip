@@ -6,7 +6,7 @@
 //   k_trace_shadow[_first]  K5  Scene::Visibility + accumulate   reference src/scene.cpp:670-673, src/path_tracer.cpp:431,455-457 (rgk_trace.h)
 //   k_resolve[_tiled]  K9  clamp / NaN scrub / AddPixel  reference src/path_tracer.cpp:502-507, src/tracer.cpp:18, src/texture.cpp:342-347
 //   k_build_pixel_list, k_build_halton_table             Tracer::Render pixel order + seeds; halton_raw per round
-//   k_entry_points, k_group_trange, k_entry_points_light  where a pixel group's camera rays / first shadow rays start in the tree
+//   k_entry_points, k_group_trange_wave, k_entry_points_light  where a pixel group's camera rays / first shadow rays start in the tree
 //                                                         (no reference counterpart: work shared by the rays of a group)
 //
 // Design: one path per slot, SoA-of-float4 queues so every lane moves 16 B
@@ -17,12 +17,10 @@
 // No MFMA: there is no dense contraction on this path.
 #include <hip/hip_runtime.h>
 #include <cstdlib>
+#include <type_traits>
 #include "rgk_device.h"
 #include "rgk_kernels.h"
 
-#ifndef RGK_TRANGE_ATOMIC
-#define RGK_TRANGE_ATOMIC 0
-#endif
 #include "rgk_trace.h" // K2 / K5: persistent traversal with lane refill
 
 #ifndef RGK_SKIP_DEAD_NEE
@@ -565,37 +563,17 @@ void rgk_launch_texture_sample(hipStream_t st, const DevScene& sc, uint32_t n, c
 }
 
 // ------------------------------------------------------------------ launch wrappers (host)
-// Upper bound on the length of the queues the next launches will consume (the host reads a queue counter back every
-// few bounces of a deep path loop): a 40-bounce round ends in dozens of launches over a few hundred rays, and a
-// full persistent grid of 3000 waves then costs more in work-fetch atomics and LDS fills than the rays themselves.
-static thread_local uint32_t g_bound = 0xffffffffu, g_bound_shadow = 0xffffffffu;
-void rgk_launch_set_bound(uint32_t items, uint32_t shadow_items) { g_bound = items; g_bound_shadow = shadow_items; }
-static inline int bounded_grid(int full, uint32_t items, uint32_t per_block) {
-    const uint64_t need = ((uint64_t)items + per_block - 1) / per_block;
-    return (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)full, need));
-}
-
-int rgk_trace_grid(int lds_entries) {
-    // LDS-limited residency: entries*256*4 B per block out of 160 KiB, 256 CUs
-    int per_cu = (160 * 1024) / (lds_entries * RGK_TRACE_BLOCK * 4);
-    if (per_cu > 8) per_cu = 8;
-    if (per_cu < 1) per_cu = 1;
-    return 256 * per_cu;
-}
-// (stack need, LDS entries) variants.  Default 256/16: 16 entries per lane in LDS, the rest -- reached only by the deep
-// part of a walk -- per lane in global memory.  That keeps 8 workgroups per CU resident whatever the tree depth
-// (occupancy was LDS-bound: 5 per CU with 32 entries, 3 with 48), and more waves are what the L1-latency-bound half
-// of the kernel wanted: Sponza trace launch 40.3 -> 33.8 ms, shadow 25 -> 20 ms per round (32 / 24 / 16 / 12 / 8
-// entries: 40.3 / 37.0 / 35.1 / 35.5 / 35.2 ms at 7 waves per SIMD; 16 entries at 8 waves: 34.2).
-// RGK_STACK_LDS=32 selects 256/32, RGK_STACK_OVF=0 the all-LDS 32/32 (shallow trees only).
-#define RGK_TRACE_DISPATCH(K, BOUND, ...)                                                            \
-    {                                                                                                \
-        const int grid = bounded_grid(rgk_trace_grid(tc.lds), BOUND, RGK_TRACE_BLOCK);               \
-        if (tc.stack <= 32 && tc.lds == 32) { if (count_stats) K<true, 32, 32><<<grid, RGK_TRACE_BLOCK, 0, st>>>(__VA_ARGS__); else K<false, 32, 32><<<grid, RGK_TRACE_BLOCK, 0, st>>>(__VA_ARGS__); } \
-        else if (tc.lds == 32) { if (count_stats) K<true, 256, 32><<<grid, RGK_TRACE_BLOCK, 0, st>>>(__VA_ARGS__); else K<false, 256, 32><<<grid, RGK_TRACE_BLOCK, 0, st>>>(__VA_ARGS__); } \
-        else { if (count_stats) K<true, 256, 16><<<grid, RGK_TRACE_BLOCK, 0, st>>>(__VA_ARGS__); else K<false, 256, 16><<<grid, RGK_TRACE_BLOCK, 0, st>>>(__VA_ARGS__); } \
+// Grids, walker variants and the bounds that shrink them: rgk_plan.h.  A walker launch takes its variant from the scene's stack
+// configuration `tc` and its grid from the bound the caller passes.
+#define RGK_TRACE_LAUNCH(K, S, L, ...) { if (count_stats) K<true, S, L><<<grid, RGK_TRACE_BLOCK, 0, st>>>(__VA_ARGS__); else K<false, S, L><<<grid, RGK_TRACE_BLOCK, 0, st>>>(__VA_ARGS__); }
+#define RGK_TRACE_DISPATCH(K, BOUND, ...)                                                       \
+    {                                                                                           \
+        const int grid = rgk_bounded_grid(rgk_trace_grid(tc.lds), BOUND, RGK_TRACE_BLOCK);      \
+        const RgkWalker v = rgk_walker_variant(tc);                                             \
+        if (v.stack == 32) RGK_TRACE_LAUNCH(K, 32, 32, __VA_ARGS__)                             \
+        else if (v.lds == 32) RGK_TRACE_LAUNCH(K, 256, 32, __VA_ARGS__)                         \
+        else RGK_TRACE_LAUNCH(K, 256, 16, __VA_ARGS__)                                          \
     }
-
 
 // ------------------------------------------------------------------ entry points of the camera rays
 // All camera rays through a group of RGK_ENTRY_PIX consecutive pixels of the round's list (a row of an 8x8 block, or whatever a
@@ -703,30 +681,17 @@ __global__ __launch_bounds__(64) void k_entry_points(const DevScene sc, const De
 // ------------------------------------------------------------------ entry points of the first vertex's shadow rays
 // A scene lit by ONE point or sphere light sends every shadow ray FROM that light (Ray(light.pos, p.pos, 20 eps), src/ray.hpp:15-22)
 // to a first hit of the group's camera rays, and those first hits lie in the slice of the group's view pyramid between the
-// nearest and the farthest of them.  k_group_trange collects that distance range per pixel group from the hit records of a
+// nearest and the farthest of them.  k_group_trange_wave collects that distance range per pixel group from the hit records of a
 // pass; k_entry_points_light bounds the slice by a box, spans the pyramid from the light over that box (capped behind it) and
 // descends the tree exactly like k_entry_points.  A sphere light's start points lie within `size` of its centre: the pyramid's
 // apex moves back so that it holds the light's box as well.
-__global__ __launch_bounds__(256) void k_group_trange(const PassParams pp, const float4* __restrict__ hit, const uint32_t n_slots, uint32_t* __restrict__ trange) {
-    for (uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x; slot < ((n_slots + 63u) & ~63u); slot += gridDim.x * blockDim.x) {
-        const bool valid = slot < n_slots;
-        uint32_t srel = 0, j = 0;
-        if (valid) slot_decode(pp, slot, j, srel);
-        const uint32_t g = valid ? (pp.j0 + j) >> RGK_ENTRY_SHIFT : 0xffffffffu;
-        float tmin = __builtin_inff(), tmax = 0.f;
-        if (valid) { const float4 h = hit[slot]; if (__float_as_int(h.w) >= 0) tmin = tmax = h.x; }
-        const uint32_t g0 = __builtin_amdgcn_readfirstlane(g);
-        if (__builtin_amdgcn_ballot_w64(g != g0) == 0ull) { // the whole wave is one group (the usual case: 8 pixels x 8 samples)
-            for (int o = 32; o > 0; o >>= 1) { tmin = fminf(tmin, __shfl_xor(tmin, o)); tmax = fmaxf(tmax, __shfl_xor(tmax, o)); }
-            if ((threadIdx.x & 63) == 0 && g0 != 0xffffffffu && tmax > 0.f) { atomicMin(&trange[2 * g0], __float_as_uint(tmin)); atomicMax(&trange[2 * g0 + 1], __float_as_uint(tmax)); }
-        } else if (valid && tmax > 0.f) { atomicMin(&trange[2 * g], __float_as_uint(tmin)); atomicMax(&trange[2 * g + 1], __float_as_uint(tmax)); }
-    }
-}
-// The same ranges with ONE WAVE PER GROUP and no atomics: lane = (pixel of the group, sample of a block of 8), the wave walks the
-// pass's sample blocks (with 8 samples side by side in the slot order, 64 consecutive slots = 1 KB per step) and writes the
-// group's two words once.  The atomic form above sends 2 atomics per 64 slots at words that sit 16 groups to a 128-byte line,
-// and consecutive waves ARE consecutive groups: 1.6 ms per 530 M slots at 256 spp, but 21 ms per 212 M at 512 spp (configs[3]:
-// four such passes in a frame's first round).  Distances compare as their bit patterns, as the atomics did.
+// ONE WAVE PER GROUP and no atomics: lane = (pixel of the group, sample of a block of 8), the wave walks the pass's sample blocks
+// (with 8 samples side by side in the slot order, 64 consecutive slots = 1 KB per step) and writes the group's two words once.
+// (Until the end of round 3 a grid-stride kernel reduced each wave of slots and sent 2 atomics per 64 slots, at words that sit 16
+// groups to a 128-byte line while consecutive waves ARE consecutive groups: 1.6 ms per 530 M slots at 256 spp, but 21 ms per
+// 212 M at 512 spp (configs[3]: four such passes in a frame's first round).  That form and its switch are gone; the measurement
+// stands.)  Distances compare as their bit patterns.
+static_assert(RGK_ENTRY_SHIFT == 3, "k_group_trange_wave lays a group out as 8 pixels x 8 samples per wave");
 __global__ __launch_bounds__(64) void k_group_trange_wave(const PassParams pp, const float4* __restrict__ hit, const uint32_t g_first, const uint32_t groups,
                                                            uint32_t* __restrict__ trange) {
     const uint32_t gi = blockIdx.x;
@@ -745,9 +710,6 @@ __global__ __launch_bounds__(64) void k_group_trange_wave(const PassParams pp, c
     }
     for (int o = 32; o > 0; o >>= 1) { tmin = min(tmin, (uint32_t)__shfl_xor((int)tmin, o)); tmax = max(tmax, (uint32_t)__shfl_xor((int)tmax, o)); }
     if (lane == 0) { trange[2 * (size_t)g] = tmin; trange[2 * (size_t)g + 1] = tmax; }
-}
-__global__ void k_init_trange(uint32_t* trange, uint32_t groups) {
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < groups; i += gridDim.x * blockDim.x) { trange[2 * i] = 0x7f800000u; trange[2 * i + 1] = 0u; }
 }
 __global__ __launch_bounds__(64) void k_entry_points_light(const DevScene sc, const DevCamera cam, const uint32_t xres, const uint32_t yres,
                                                             const uint32_t* __restrict__ pix_xy, const uint32_t n_pixels, const uint32_t g_first, const uint32_t g_count,
@@ -832,20 +794,12 @@ void rgk_launch_entry_points(hipStream_t st, const DevScene& sc, const DevCamera
 }
 // nearest / farthest first hit per pixel group of a finished bounce-0 trace of this pass
 void rgk_launch_group_trange(hipStream_t st, const PassParams& pp, const float4* hit, uint32_t* trange) {
-    const uint32_t g_first = pp.j0 >> RGK_ENTRY_SHIFT, g_last = (pp.j0 + pp.npix + RGK_ENTRY_PIX - 1u) >> RGK_ENTRY_SHIFT, groups = g_last - g_first;
-#if RGK_TRANGE_ATOMIC
-    k_init_trange<<<(groups + 255u) / 256u, 256, 0, st>>>(trange + 2 * (size_t)g_first, groups);
-    const uint32_t n = pp.npix * pp.ns; // every slot of this pass (done once per frame and pixel range, so 16 bytes per path do not matter)
-    uint32_t blocks = (n + 255u) / 256u;
-    if (blocks > 256u * 64u) blocks = 256u * 64u;
-    k_group_trange<<<blocks, 256, 0, st>>>(pp, hit, n, trange);
-#else
-    k_group_trange_wave<<<groups, 64, 0, st>>>(pp, hit, g_first, groups, trange);
-#endif
+    const RgkGroupRange g = rgk_group_range(pp.j0, pp.npix);
+    k_group_trange_wave<<<g.count(), 64, 0, st>>>(pp, hit, g.first, g.count(), trange);
 }
 void rgk_launch_light_entry_points(hipStream_t st, const DevScene& sc, const DevCamera& cam, const PassParams& pp, uint32_t n_pixels_round, const uint32_t* trange, int* entries, float4* lbox) {
-    const uint32_t g_first = pp.j0 >> RGK_ENTRY_SHIFT, g_last = (pp.j0 + pp.npix + RGK_ENTRY_PIX - 1u) >> RGK_ENTRY_SHIFT, groups = g_last - g_first;
-    k_entry_points_light<<<(groups + 63u) / 64u, 64, 0, st>>>(sc, cam, pp.xres, pp.yres, pp.pix_xy, n_pixels_round, g_first, groups, trange, entries, lbox);
+    const RgkGroupRange g = rgk_group_range(pp.j0, pp.npix);
+    k_entry_points_light<<<(g.count() + 63u) / 64u, 64, 0, st>>>(sc, cam, pp.xres, pp.yres, pp.pix_xy, n_pixels_round, g.first, g.count(), trange, entries, lbox);
 }
 
 __global__ void k_stage_mark(uint32_t* host_word, uint32_t v) { *(volatile uint32_t*)host_word = v; __threadfence_system(); }
@@ -861,81 +815,69 @@ void rgk_launch_build_halton_table(hipStream_t st, const DevScene& sc, uint32_t 
 
 // bounce 0 of a unidirectional pass: camera rays generated in the traversal kernel (no queue)
 void rgk_launch_trace_camera(hipStream_t st, const DevScene& sc, const DevCamera& cam, const PassParams& pp, const RgkTraceCfg& tc, bool count_stats, float4* hit,
-                             const uint32_t* count_ptr, uint32_t* fetch, unsigned long long* stats) {
-    if (pp.beam && pp.gshift == 3 && cam.lens_size == 0.0f && tc.lds < tc.stack) {
+                             const RgkWalk& w, unsigned long long* stats) {
+    if (rgk_beam_taken(pp.beam != 0, pp.gshift, cam.lens_size != 0.0f, tc)) {
         // 8 stack entries per lane in LDS (the rest in the overflow area): with the bundle's 32 floats per lane that makes 40 KB per
         // workgroup, four workgroups per CU
-        const int grid = bounded_grid(rgk_trace_grid(tc.lds), (g_bound >> 3) + 1u, RGK_TRACE_BLOCK);
-        if (count_stats) k_trace_camera_beam<true, 256, 8><<<grid, RGK_TRACE_BLOCK, 0, st>>>(sc, cam, pp, hit, count_ptr, fetch, stats, tc.ovf);
-        else k_trace_camera_beam<false, 256, 8><<<grid, RGK_TRACE_BLOCK, 0, st>>>(sc, cam, pp, hit, count_ptr, fetch, stats, tc.ovf);
+        const int grid = rgk_bounded_grid(rgk_trace_grid(tc.lds), rgk_beam_bound(w.bound), RGK_TRACE_BLOCK);
+        RGK_TRACE_LAUNCH(k_trace_camera_beam, 256, 8, sc, cam, pp, hit, w.count_ptr, w.fetch, stats, tc.ovf)
         return;
     }
-    RGK_TRACE_DISPATCH(k_trace_camera, g_bound, sc, cam, pp, hit, count_ptr, fetch, stats, tc.ovf)
+    RGK_TRACE_DISPATCH(k_trace_camera, w.bound, sc, cam, pp, hit, w.count_ptr, w.fetch, stats, tc.ovf)
 }
 
 void rgk_launch_trace_closest(hipStream_t st, const DevScene& sc, const RgkTraceCfg& tc, bool count_stats, const float4* rayA, const float4* rayB,
-                              const float2* nearfar, float4* hit, const uint32_t* count_ptr, uint32_t* fetch, unsigned long long* stats) {
-    RGK_TRACE_DISPATCH(k_trace_closest, g_bound, sc, rayA, rayB, nearfar, hit, count_ptr, fetch, stats, tc.ovf)
+                              const float2* nearfar, float4* hit, const RgkWalk& w, unsigned long long* stats) {
+    RGK_TRACE_DISPATCH(k_trace_closest, w.bound, sc, rayA, rayB, nearfar, hit, w.count_ptr, w.fetch, stats, tc.ovf)
 }
 
 void rgk_launch_trace_shadow(hipStream_t st, const DevScene& sc, const RgkTraceCfg& tc, bool count_stats, const float4* shA, const float4* shB,
-                             const float4* shC, float4* tot, uint8_t* vis_out, int mode, float* splat_rgb, const uint32_t* count_ptr,
-                             uint32_t* fetch, unsigned long long* stats) {
-    RGK_TRACE_DISPATCH(k_trace_shadow, g_bound_shadow, sc, shA, shB, shC, tot, vis_out, mode, splat_rgb, count_ptr, fetch, stats, tc.ovf)
+                             const float4* shC, float4* tot, uint8_t* vis_out, int mode, float* splat_rgb, const RgkWalk& w, unsigned long long* stats) {
+    RGK_TRACE_DISPATCH(k_trace_shadow, w.bound, sc, shA, shB, shC, tot, vis_out, mode, splat_rgb, w.count_ptr, w.fetch, stats, tc.ovf)
 }
 
 void rgk_launch_trace_shadow_first(hipStream_t st, const DevScene& sc, const PassParams& pp, const RgkTraceCfg& tc, bool count_stats, const float4* shA, const float4* shB,
-                                   const float4* shC, float4* tot, const uint32_t* count_ptr, uint32_t* fetch, unsigned long long* stats) {
-    RGK_TRACE_DISPATCH(k_trace_shadow_first, g_bound_shadow, sc, pp, shA, shB, shC, tot, count_ptr, fetch, stats, tc.ovf)
+                                   const float4* shC, float4* tot, const RgkWalk& w, unsigned long long* stats) {
+    RGK_TRACE_DISPATCH(k_trace_shadow_first, w.bound, sc, pp, shA, shB, shC, tot, w.count_ptr, w.fetch, stats, tc.ovf)
 }
 
 // The same two for the 32-byte records of the constant-light route: shA = {d.xyz, far}, shB = {radiance.rgb, slot}; every ray
 // starts at sc.cl_pos with near = 20 eps.
 bool rgk_const_light_records() { return RGK_CL_REC32 != 0; }
 void rgk_launch_trace_shadow_cl(hipStream_t st, const DevScene& sc, const RgkTraceCfg& tc, bool count_stats, const float4* shA, const float4* shB,
-                                float4* tot, const uint32_t* count_ptr, uint32_t* fetch, unsigned long long* stats) {
-    RGK_TRACE_DISPATCH(k_trace_shadow_cl, g_bound_shadow, sc, shA, shB, tot, count_ptr, fetch, stats, tc.ovf)
+                                float4* tot, const RgkWalk& w, unsigned long long* stats) {
+    RGK_TRACE_DISPATCH(k_trace_shadow_cl, w.bound, sc, shA, shB, tot, w.count_ptr, w.fetch, stats, tc.ovf)
 }
 void rgk_launch_trace_shadow_first_cl(hipStream_t st, const DevScene& sc, const PassParams& pp, const RgkTraceCfg& tc, bool count_stats, const float4* shA, const float4* shB,
-                                      float4* tot, const uint32_t* count_ptr, uint32_t* fetch, unsigned long long* stats) {
-    RGK_TRACE_DISPATCH(k_trace_shadow_first_cl, g_bound_shadow, sc, pp, shA, shB, tot, count_ptr, fetch, stats, tc.ovf)
+                                      float4* tot, const RgkWalk& w, unsigned long long* stats) {
+    RGK_TRACE_DISPATCH(k_trace_shadow_first_cl, w.bound, sc, pp, shA, shB, tot, w.count_ptr, w.fetch, stats, tc.ovf)
 }
 
 void rgk_launch_shade(hipStream_t st, const DevScene& sc, const DevCamera& cam, const PassParams& pp, uint32_t bounce, const float4* rayA,
                       const float4* rayB, const float4* hit, float4* thr, float4* tot, float4* nextA, float4* nextB, float4* shA,
-                      float4* shB, float4* shC, uint32_t* counters, bool bdpt, bool const_light) {
-    const int blk = bounce == 0 ? RGK_SHADE_BLOCK : RGK_SHADE_BLOCK_LATER;
-    const int g1 = bounded_grid(256 * 4 * 512 / blk, g_bound, blk), g2 = bounded_grid(256 * 2 * 512 / blk, g_bound, blk);
+                      float4* shB, float4* shC, uint32_t* counters, uint32_t bound, bool bdpt, bool const_light) {
+    const RgkGridPair g = rgk_shade_grids(bounce, bound);
     // the second launch shades the vertices the first one listed (materials on the generic BxDF route); it returns at once when there are none
-    if (bdpt && bounce == 0) {
-        k_shade<false, true, true><<<g1, blk, RGK_LDS_SHADE_BYTES, st>>>(sc, cam, pp, bounce, rayA, rayB, hit, thr, tot, nextA, nextB, shA, shB, shC, counters);
-        k_shade<true, true, true><<<g2, blk, RGK_LDS_SHADE_BYTES, st>>>(sc, cam, pp, bounce, rayA, rayB, hit, thr, tot, nextA, nextB, shA, shB, shC, counters);
-    } else if (bdpt) {
-        k_shade<false, false, true><<<g1, blk, RGK_LDS_SHADE_BYTES, st>>>(sc, cam, pp, bounce, rayA, rayB, hit, thr, tot, nextA, nextB, shA, shB, shC, counters);
-        k_shade<true, false, true><<<g2, blk, RGK_LDS_SHADE_BYTES, st>>>(sc, cam, pp, bounce, rayA, rayB, hit, thr, tot, nextA, nextB, shA, shB, shC, counters);
-    } else if (const_light && bounce == 0) {
-        k_shade<false, true, false, true><<<g1, blk, RGK_LDS_SHADE_BYTES, st>>>(sc, cam, pp, bounce, rayA, rayB, hit, thr, tot, nextA, nextB, shA, shB, shC, counters);
-        k_shade<true, true, false, true><<<g2, blk, RGK_LDS_SHADE_BYTES, st>>>(sc, cam, pp, bounce, rayA, rayB, hit, thr, tot, nextA, nextB, shA, shB, shC, counters);
-    } else if (const_light) {
-        k_shade<false, false, false, true><<<g1, blk, RGK_LDS_SHADE_BYTES, st>>>(sc, cam, pp, bounce, rayA, rayB, hit, thr, tot, nextA, nextB, shA, shB, shC, counters);
-        k_shade<true, false, false, true><<<g2, blk, RGK_LDS_SHADE_BYTES, st>>>(sc, cam, pp, bounce, rayA, rayB, hit, thr, tot, nextA, nextB, shA, shB, shC, counters);
-    } else if (bounce == 0) {
-        k_shade<false, true><<<g1, blk, RGK_LDS_SHADE_BYTES, st>>>(sc, cam, pp, bounce, rayA, rayB, hit, thr, tot, nextA, nextB, shA, shB, shC, counters);
-        k_shade<true, true><<<g2, blk, RGK_LDS_SHADE_BYTES, st>>>(sc, cam, pp, bounce, rayA, rayB, hit, thr, tot, nextA, nextB, shA, shB, shC, counters);
-    } else {
-        k_shade<false, false><<<g1, blk, RGK_LDS_SHADE_BYTES, st>>>(sc, cam, pp, bounce, rayA, rayB, hit, thr, tot, nextA, nextB, shA, shB, shC, counters);
-        k_shade<true, false><<<g2, blk, RGK_LDS_SHADE_BYTES, st>>>(sc, cam, pp, bounce, rayA, rayB, hit, thr, tot, nextA, nextB, shA, shB, shC, counters);
+    auto pair = [&](auto first, auto bd, auto cl) {
+        constexpr bool FIRST = decltype(first)::value, BDPT = decltype(bd)::value, CL = decltype(cl)::value;
+        k_shade<false, FIRST, BDPT, CL><<<g.fast, g.block, RGK_LDS_SHADE_BYTES, st>>>(sc, cam, pp, bounce, rayA, rayB, hit, thr, tot, nextA, nextB, shA, shB, shC, counters);
+        k_shade<true, FIRST, BDPT, CL><<<g.generic, g.block, RGK_LDS_SHADE_BYTES, st>>>(sc, cam, pp, bounce, rayA, rayB, hit, thr, tot, nextA, nextB, shA, shB, shC, counters);
+    };
+    constexpr std::true_type T{}; constexpr std::false_type F{};
+    switch ((bounce == 0 ? 4 : 0) | (bdpt ? 2 : (const_light ? 1 : 0))) { // (FIRST, BDPT, CL): a bidirectional round never takes the constant-light route
+    case 4 | 2: pair(T, T, F); break;
+    case 2: pair(F, T, F); break;
+    case 4 | 1: pair(T, F, T); break;
+    case 1: pair(F, F, T); break;
+    case 4: pair(T, F, F); break;
+    default: pair(F, F, F); break;
     }
 }
 
 void rgk_launch_resolve(hipStream_t st, const PassParams& pp, const float4* tot, float4* pixsum, float* accum_rgb, uint32_t* accum_count) {
-    int grid = (int)((pp.npix + 255) / 256);
-    if (grid > 256 * 16) grid = 256 * 16;
-    if (pp.gshift == 0) { k_resolve<<<grid, 256, 0, st>>>(pp, tot, pixsum, accum_rgb, accum_count); return; }
-    const uint32_t G = 1u << pp.gshift;
-    const uint32_t PT = G <= 8 ? 64u : 512u / G; // pixels per tile: ~9 KB of LDS per wave (more waves per CU matter more here than full lanes in the short summing phase)
-    int tiles = (int)((pp.npix + PT - 1) / PT);
-    k_resolve_tiled<<<tiles > 256 * 64 ? 256 * 64 : tiles, 64, PT * (G + 1) * sizeof(float4), st>>>(pp, tot, pixsum, accum_rgb, accum_count, PT);
+    const RgkResolvePlan r = rgk_resolve_plan(pp.npix, pp.gshift);
+    if (pp.gshift == 0) k_resolve<<<r.grid, 256, 0, st>>>(pp, tot, pixsum, accum_rgb, accum_count);
+    else k_resolve_tiled<<<r.grid, 64, r.lds, st>>>(pp, tot, pixsum, accum_rgb, accum_count, r.PT);
 }
 
 void rgk_launch_pack_rays(hipStream_t st, uint32_t n, const float* rays, const int32_t* ignore, float4* rayA, float4* rayB, float2* nearfar) {
@@ -950,29 +892,24 @@ void rgk_launch_sampler_eval(hipStream_t st, const DevScene& sc, uint32_t n, con
     k_sampler_eval<<<(n + 255) / 256, 256, 0, st>>>(sc, n, seed, index, dim, is2d, out);
 }
 
-static inline int slot_grid(const PassParams& pp) {
-    uint32_t n = pp.npix * pp.ns;
-    int grid = (int)((n + 255) / 256);
-    return grid > 256 * 16 ? 256 * 16 : grid;
-}
 void rgk_launch_raygen_light(hipStream_t st, const DevScene& sc, const DevCamera& cam, const PassParams& pp, float4* rayA, float4* rayB,
                              float4* thr, uint32_t* counters) {
-    const uint32_t n = pp.npix * pp.ns;
-    k_raygen_light<<<bounded_grid(256 * 4 * 512 / RGK_LIGHT_BLOCK, n, RGK_LIGHT_BLOCK), RGK_LIGHT_BLOCK, 0, st>>>(sc, cam, pp, rayA, rayB, thr, counters);
+    k_raygen_light<<<rgk_light_grids(pp.npix * pp.ns).fast, RGK_LIGHT_BLOCK, 0, st>>>(sc, cam, pp, rayA, rayB, thr, counters);
 }
 void rgk_launch_shade_light(hipStream_t st, const DevScene& sc, const DevCamera& cam, const PassParams& pp, uint32_t k, const float4* rayA,
                             const float4* rayB, const float4* hit, float4* thr, float4* nextA, float4* nextB, float4* shA, float4* shB,
-                            float4* shC, uint32_t* counters) {
-    k_shade_light<false><<<bounded_grid(256 * 4 * 512 / RGK_LIGHT_BLOCK, g_bound, RGK_LIGHT_BLOCK), RGK_LIGHT_BLOCK, RGK_LDS_SHADE_BYTES, st>>>(sc, cam, pp, k, rayA, rayB, hit, thr, nextA, nextB, shA, shB, shC, counters);
-    k_shade_light<true><<<bounded_grid(256 * 2 * 512 / RGK_LIGHT_BLOCK, g_bound, RGK_LIGHT_BLOCK), RGK_LIGHT_BLOCK, RGK_LDS_SHADE_BYTES, st>>>(sc, cam, pp, k, rayA, rayB, hit, thr, nextA, nextB, shA, shB, shC, counters);
+                            float4* shC, uint32_t* counters, uint32_t bound) {
+    const RgkGridPair g = rgk_light_grids(bound);
+    k_shade_light<false><<<g.fast, g.block, RGK_LDS_SHADE_BYTES, st>>>(sc, cam, pp, k, rayA, rayB, hit, thr, nextA, nextB, shA, shB, shC, counters);
+    k_shade_light<true><<<g.generic, g.block, RGK_LDS_SHADE_BYTES, st>>>(sc, cam, pp, k, rayA, rayB, hit, thr, nextA, nextB, shA, shB, shC, counters);
 }
-void rgk_launch_connect(hipStream_t st, const DevScene& sc, const PassParams& pp, uint32_t bounce, float4* jobs, float4* rads, uint32_t* counters) {
-    k_connect<<<bounded_grid(256 * 8, g_bound, 256), 256, RGK_LDS_SHADE_BYTES, st>>>(sc, pp, bounce, jobs, rads, counters);
+void rgk_launch_connect(hipStream_t st, const DevScene& sc, const PassParams& pp, uint32_t bounce, float4* jobs, float4* rads, uint32_t* counters, uint32_t bound) {
+    k_connect<<<rgk_connect_grid(bound), RGK_CONNECT_BLOCK, RGK_LDS_SHADE_BYTES, st>>>(sc, pp, bounce, jobs, rads, counters);
 }
-void rgk_launch_list_hits(hipStream_t st, const float4* hit, const uint32_t* count_ptr, uint32_t* list, uint32_t* list_count) {
-    k_list_hits<<<bounded_grid(256 * 4 * 512 / RGK_LIGHT_BLOCK, g_bound, RGK_LIGHT_BLOCK), RGK_LIGHT_BLOCK, 0, st>>>(hit, count_ptr, list, list_count);
+void rgk_launch_list_hits(hipStream_t st, const float4* hit, const uint32_t* count_ptr, uint32_t* list, uint32_t* list_count, uint32_t bound) {
+    k_list_hits<<<rgk_light_grids(bound).fast, RGK_LIGHT_BLOCK, 0, st>>>(hit, count_ptr, list, list_count);
 }
 void rgk_launch_trace_shadow_jobs(hipStream_t st, const DevScene& sc, const PassParams& pp, const RgkTraceCfg& tc, bool count_stats, const float4* jobs, const float4* rads,
-                                  float4* tot, const uint32_t* count_ptr, uint32_t* fetch, unsigned long long* stats) {
-    RGK_TRACE_DISPATCH(k_trace_shadow_jobs, g_bound_shadow, sc, pp, jobs, rads, tot, count_ptr, fetch, stats, tc.ovf)
+                                  float4* tot, const RgkWalk& w, unsigned long long* stats) {
+    RGK_TRACE_DISPATCH(k_trace_shadow_jobs, w.bound, sc, pp, jobs, rads, tot, w.count_ptr, w.fetch, stats, tc.ovf)
 }

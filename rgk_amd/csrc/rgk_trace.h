@@ -31,9 +31,6 @@
 #ifndef RGK_TRACE_WAVES
 #define RGK_TRACE_WAVES 8 // waves per SIMD the 16-LDS-entry traversal kernels are compiled for (64 VGPRs); the 32-entry ones are LDS-bound at 5
 #endif
-#ifndef RGK_JOB_FINISH_ATOMIC
-#define RGK_JOB_FINISH_ATOMIC 0 // the vertex total into the slot sum as three float atomics instead of a read-modify-write
-#endif
 #ifndef RGK_JOB_REFILL_BELOW
 #define RGK_JOB_REFILL_BELOW 24 // the vertex queue's walker: lanes between two rays of their vertex wait for the refill too
 #endif
@@ -235,12 +232,9 @@ __device__ __forceinline__ void trace_persistent(const DevScene& sc, const float
 // (The LDS part is read by an explicit ds_read_b32.  Written as a plain conditional the compiler folds the two sources into ONE
 // flat_load of a selected pointer -- also with the sides forced to values, also through a volatile pointer: then a system-coherent
 // flat load -- and every pop, nearly all of which come from LDS, takes the flat path: a vector-memory AND an LDS operation, waited
-// for as both.  The low half of a generic pointer into LDS is its LDS address.)
-#if defined(RGK_POP_FLAT)
-#define RGK_POP() ((LDSN >= STACK || sp < LDSN) ? stack[sp * stride] : ovf[(size_t)(sp - LDSN) * ostride])
-#else
+// for as both.  The low half of a generic pointer into LDS is its LDS address.  The plain form, kept behind a switch while the
+// two were measured, is gone.)
 #define RGK_POP() ((LDSN >= STACK || sp < LDSN) ? lds_pop(stack + sp * stride) : ovf[(size_t)(sp - LDSN) * ostride])
-#endif
     for (;;) {
         // ------------------------------------------------ refill idle lanes
         // (JOB: a lane whose ray is done but whose vertex has more waits like an idle lane -- `act` counts the lanes with a ray in
@@ -372,16 +366,12 @@ __device__ __forceinline__ void trace_persistent(const DevScene& sc, const float
                     total = clamp3(total, pp->clamp);
                     const float4 c = q0[(size_t)pp->batch + idx];
                     const f3 add = total * mk3(c.x, c.y, c.z);
-#if RGK_JOB_FINISH_ATOMIC
-                    // (one vertex per slot and bounce, so each component sees ONE addition per launch -- the same bits as the
-                    // read-modify-write -- but nothing to wait for at a point where the whole wave waits)
-                    float* tp = reinterpret_cast<float*>(tot + jslot);
-                    unsafeAtomicAdd(tp, add.x); unsafeAtomicAdd(tp + 1, add.y); unsafeAtomicAdd(tp + 2, add.z);
-#else
+                    // (the total as three float atomics instead -- one vertex per slot and bounce, so each component sees ONE
+                    // addition per launch, the same bits, and nothing to wait for at a point where the whole wave waits -- was
+                    // tried behind a switch and lost: DESIGN.md)
                     float4 t = tot[jslot]; // one vertex per slot and bounce: no race
                     t.x = t.x + add.x; t.y = t.y + add.y; t.z = t.z + add.z;
                     tot[jslot] = t;
-#endif
                     active = false; seg_pending = false;
                     break;
                 }
@@ -861,9 +851,6 @@ __global__ __launch_bounds__(RGK_TRACE_BLOCK, (LDSN <= 16 ? RGK_TRACE_WAVES : 5)
 
 // K5 for bidirectional rounds: one queue entry per camera-path vertex (JOB above).  jobs = {vertex}{contribution, mask}{emission},
 // rads = one radiance per ray (k_connect wrote both, and counted the rays).
-#ifndef RGK_JOB_FINISH_ATOMIC
-#define RGK_JOB_FINISH_ATOMIC 0
-#endif
 #ifndef RGK_JOB_WAVES
 #define RGK_JOB_WAVES 6 // the vertex state costs ~12 VGPRs over a plain shadow ray: 8 waves per SIMD would spill 44 bytes
 #endif

@@ -276,7 +276,7 @@ def test_entry_nodes_do_not_change_the_image(rd):
             imgs.append((acc, k.path_rays, k.shadow_rays))
         for acc, pr, sr in imgs[1:]:
             assert np.array_equal(acc, imgs[0][0]) and pr == imgs[0][1] and sr == imgs[0][2], (name, kw)
-        # other slot orders (a wave then mixes pixel groups: the per-lane path of k_group_trange) and passes split over pixels and samples
+        # other slot orders (a wave of slots then mixes pixel groups: k_group_trange_wave finds a group's slots through slot_of) and passes split over pixels and samples
         for grp, batch in (("0", None), ("6", None), ("3", 30000)):
             g2 = rd.Scene(wl.builder.to_desc()).set_tuning(sample_group=int(grp), batch_paths=batch or 0)     # (a fresh scene: nothing cached from the runs above)
             acc, cnt, k = g2.render_round(wl.camera, wl.params(), tiles)
