@@ -258,6 +258,12 @@ struct Scene {
     Intersection FindIntersectKd(const Ray& r, TravStats* st = nullptr) const { return Find(r, -1, st); }
     Intersection FindIntersectKdOtherThan(const Ray& r, int ignore, TravStats* st = nullptr) const { return Find(r, ignore, st); }
     Intersection Find(const Ray& r, int ignore, TravStats* st) const;
+    bool ClipToBox(const Ray& r, float& t0, float& t1) const;
+    Intersection FindExhaustive(const Ray& r, int ignore) const;
+    bool VisibilityExhaustive(vec3 a, vec3 b) const {
+        Ray r(a, b, epsilon * 20.0f);
+        return FindExhaustive(r, -1).triangle < 0;
+    }
     bool Visibility(vec3 a, vec3 b, TravStats* st = nullptr) const {
         Ray r(a, b, epsilon * 20.0f); // scene.cpp:670-673
         return FindIntersectKd(r, st).triangle < 0;
@@ -331,12 +337,10 @@ bool Scene::TestIntersection(const Triangle& tri, const Ray& r, float& t, float&
 }
 
 // scene_intersect.cpp:4-116 (ignore<0) and :211-327 (ignore>=0): identical but for the skip.
-Intersection Scene::Find(const Ray& r, int ignore, TravStats* st) const {
-    Intersection res;
-    res.triangle = -1;
-    res.t = std::numeric_limits<float>::infinity();
+// The ray's [near, far] clipped to the epsilon-padded scene box (scene_intersect.cpp:223-232); false when nothing is left.
+bool Scene::ClipToBox(const Ray& r, float& t0, float& t1) const {
     const std::pair<float, float>* bb[3] = {&xBB, &yBB, &zBB};
-    float t0 = r.near, t1 = r.far;
+    t0 = r.near; t1 = r.far;
     for (int i = 0; i < 3; ++i) {
         float invRayDir = 1.f / r.direction[i];
         float tNear = (bb[i]->first - r.origin[i]) * invRayDir;
@@ -344,8 +348,43 @@ Intersection Scene::Find(const Ray& r, int ignore, TravStats* st) const {
         if (tNear > tFar) std::swap(tNear, tFar);
         t0 = tNear > t0 ? tNear : t0;
         t1 = tFar < t1 ? tFar : t1;
-        if (t0 > t1) return res;
+        if (t0 > t1) return false;
     }
+    return true;
+}
+
+// The traversal contract without a tree (rgk_amd/csrc/rgk_trace.h): every triangle but `ignore` is tested, a hit is accepted
+// when t0 - eps <= t <= t1 + eps for the clipped [t0, t1], the smallest t wins and an exact tie goes to the higher triangle
+// id.  What Find returns on the same ray is a hit of this set (its per-leaf windows lie inside this one), never a nearer one.
+Intersection Scene::FindExhaustive(const Ray& r, int ignore) const {
+    Intersection res;
+    res.triangle = -1;
+    res.t = std::numeric_limits<float>::infinity();
+    float t0, t1;
+    if (!ClipToBox(r, t0, t1)) return res;
+    const float lo = t0 - epsilon, hi = t1 + epsilon;
+    const int n = (int)triangles.size();
+    for (int i = 0; i < n; i++) {
+        if (i == ignore) continue;
+        float t, a, b;
+        if (!TestIntersection(triangles[i], r, t, a, b)) continue;
+        if (t < lo || t > hi) continue;
+        if (t < res.t || (t == res.t && res.triangle >= 0 && i > res.triangle)) {
+            res.triangle = i;
+            res.t = t;
+            float c = 1.0f - a - b;
+            res.a = c; res.b = a; res.c = b;
+        }
+    }
+    return res;
+}
+
+Intersection Scene::Find(const Ray& r, int ignore, TravStats* st) const {
+    Intersection res;
+    res.triangle = -1;
+    res.t = std::numeric_limits<float>::infinity();
+    float t0, t1;
+    if (!ClipToBox(r, t0, t1)) return res;
     struct NodeToDo { const CompressedKdNode* node; float tmin, tmax; };
     vec3 invDir(1.f / r.direction.x, 1.f / r.direction.y, 1.f / r.direction.z);
     NodeToDo todo[200];
@@ -1373,6 +1412,16 @@ struct TileResult {
 
 } // namespace
 
+// [0, n) split into contiguous pieces over worker threads (the calling thread takes one); fn(begin, end)
+template <typename F> static void parallel_ranges(uint32_t n, F fn) {
+    unsigned nt = std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
+    nt = std::max(1u, std::min(nt, n / 256u));
+    std::vector<std::thread> th;
+    for (unsigned k = 1; k < nt; k++) th.emplace_back(fn, (uint32_t)((uint64_t)n * k / nt), (uint32_t)((uint64_t)n * (k + 1) / nt));
+    fn(0u, (uint32_t)((uint64_t)n / nt));
+    for (auto& t : th) t.join();
+}
+
 // ======================================================================= C interface
 extern "C" {
 
@@ -1562,6 +1611,31 @@ int orc_trace_visibility(void* h, uint32_t n, const float* a, const float* b, ui
     for (uint32_t i = 0; i < n; i++)
         vis[i] = s->Visibility(vec3(a[3 * i], a[3 * i + 1], a[3 * i + 2]), vec3(b[3 * i], b[3 * i + 1], b[3 * i + 2]), &st);
     if (c) { std::memset(c, 0, sizeof(*c)); c->shadow_node_visits = st.nodes; c->shadow_tri_tests = st.tris; c->shadow_rays = n; }
+    return 0;
+}
+
+// orc_trace_closest / orc_trace_visibility by exhaustive search (Scene::FindExhaustive): same layouts, no tree, no counters
+int orc_trace_closest_exhaustive(void* h, uint32_t n, const float* rays, const int32_t* ignore, rgk_hit* hits) {
+    const Scene* s = (const Scene*)h;
+    parallel_ranges(n, [=](uint32_t b, uint32_t e) {
+        for (uint32_t i = b; i < e; i++) {
+            Ray r;
+            r.origin = vec3(rays[8 * i], rays[8 * i + 1], rays[8 * i + 2]);
+            r.direction = vec3(rays[8 * i + 3], rays[8 * i + 4], rays[8 * i + 5]);
+            r.near = rays[8 * i + 6]; r.far = rays[8 * i + 7];
+            Intersection x = s->FindExhaustive(r, ignore ? ignore[i] : -1);
+            hits[i].tri = x.triangle; hits[i].t = x.t; hits[i].a = x.a; hits[i].b = x.b; hits[i].c = x.c;
+        }
+    });
+    return 0;
+}
+
+int orc_trace_visibility_exhaustive(void* h, uint32_t n, const float* a, const float* b, uint8_t* vis) {
+    const Scene* s = (const Scene*)h;
+    parallel_ranges(n, [=](uint32_t lo, uint32_t hi) {
+        for (uint32_t i = lo; i < hi; i++)
+            vis[i] = s->VisibilityExhaustive(vec3(a[3 * i], a[3 * i + 1], a[3 * i + 2]), vec3(b[3 * i], b[3 * i + 1], b[3 * i + 2]));
+    });
     return 0;
 }
 

@@ -41,6 +41,8 @@ def lib():
                                         _p(capi.Counters)]
         L.orc_trace_visibility.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                            _p(capi.Counters)]
+        L.orc_trace_closest_exhaustive.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.orc_trace_visibility_exhaustive.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.orc_halton_raw.restype = C.c_float
         L.orc_halton_raw.argtypes = [C.c_uint32, C.c_uint32]
         L.orc_sampler_eval.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
@@ -112,6 +114,22 @@ class OracleScene:
         cnt = capi.Counters()
         self.L.orc_trace_visibility(self.h, len(a), a.ctypes.data, b.ctypes.data, vis.ctypes.data, C.byref(cnt))
         return vis, cnt
+
+    def trace_closest_exhaustive(self, rays, ignore=None):
+        """trace_closest's layouts, answered by testing every triangle under the walkers' stated rule (Scene::FindExhaustive)."""
+        rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
+        n = len(rays)
+        ig = None if ignore is None else np.ascontiguousarray(ignore, dtype=np.int32)
+        hits = np.zeros(n, dtype=[("t", "f4"), ("tri", "i4"), ("a", "f4"), ("b", "f4"), ("c", "f4")])
+        self.L.orc_trace_closest_exhaustive(self.h, n, rays.ctypes.data, None if ig is None else ig.ctypes.data, hits.ctypes.data)
+        return hits
+
+    def visibility_exhaustive(self, a, b):
+        a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 3)
+        b = np.ascontiguousarray(b, dtype=np.float32).reshape(-1, 3)
+        vis = np.zeros(len(a), dtype=np.uint8)
+        self.L.orc_trace_visibility_exhaustive(self.h, len(a), a.ctypes.data, b.ctypes.data, vis.ctypes.data)
+        return vis
 
 
 def sampler_eval(seed, index, dim, is2d):

@@ -1,0 +1,266 @@
+"""GPU suite (-m gpu): the HIP walkers against the exhaustive-search reference, with no excuse list.
+
+The walkers' contract (rgk_amd/csrc/rgk_trace.h) names no tree: the nearest accepted hit with t in [t0 - eps, t1 + eps], [t0, t1]
+the ray's [near, far] clipped to the epsilon-padded scene box, exact ties to the higher triangle id, any-hit in the same window.
+OracleScene.trace_closest_exhaustive / visibility_exhaustive test every triangle under exactly that rule with the kernels' own
+triangle test, so for every builder, tree, stack variant and ray count the bar is
+
+    tri equal for every ray; t, a, b, c equal bit for bit (a miss is t = +inf, a = b = c = 0 on both sides);
+    visibility bytes equal for every pair -- no tie band, no `unexplained` allowance.
+
+Scenes (tests/trace_ref.py) are the small and degenerate ones the other traversal tests never build: 1 ... 257 triangles, a flat
+scene, one centroid for every triangle, coincident runs, a closed mesh hit at its vertices and edges, a deep tree from 1 200
+triangles, the same soup at 1e-3 and at 1e3 far from the origin.  Every test records rays, hits and differing (0).
+"""
+import ctypes as C
+import functools
+import os
+
+import numpy as np
+import pytest
+
+from rgk_amd import capi
+from rgk_amd.config import make_camera, make_params
+
+from conftest import record_parity
+import trace_ref as T
+
+pytestmark = pytest.mark.gpu
+
+N_RAYS = 20000
+SMALLER = {"deep": (10000, 10000)}    # (rays, pairs): 1 200 triangles -- three exhaustive traces + the pairs stay under 5e7 triangle tests
+BUILDERS = {   # name -> (build flags, environment of rgk_scene_create)
+    "host-sah": (capi.BUILD_HOST_SAH, {}),
+    "device": (capi.BUILD_DEVICE, {}),                                                              # clustering (the default)
+    "device-karras": (capi.BUILD_DEVICE, {"RGK_LBVH_PLOC": "0", "RGK_LBVH_ROTATE": "0"}),
+    "device-karras-rotate4": (capi.BUILD_DEVICE, {"RGK_LBVH_PLOC": "0", "RGK_LBVH_ROTATE": "4"}),
+    # the walkers' <STACK, LDSN> variants (rgk_plan.h rgk_walker_variant): 256/16 is what the four above run
+    "host-sah-stack256-lds16": (capi.BUILD_HOST_SAH, {"RGK_STACK_OVF": "1", "RGK_STACK_LDS": "16"}),
+    "host-sah-stack256-lds32": (capi.BUILD_HOST_SAH, {"RGK_STACK_OVF": "1", "RGK_STACK_LDS": "32"}),
+    # all-LDS 32/32: taken only where max_stack + 1 + RGK_ENTRY_K <= 32 (rgk_host.cpp configure_stack), else 256/16 runs without a
+    # word.  Which one ran cannot be read through the C ABI; max_depth can, and max_stack <= 3 (max_depth + 1): see the test.
+    "host-sah-stack32-lds32": (capi.BUILD_HOST_SAH, {"RGK_STACK_OVF": "0"}),
+}
+CASES = [(s, b) for s in T.SCENES for b in ("host-sah", "device", "device-karras", "device-karras-rotate4")]
+CASES += [("deep", "host-sah-stack256-lds16"), ("deep", "host-sah-stack256-lds32"), ("count65", "host-sah-stack32-lds32"),
+          ("duplicates", "host-sah-stack32-lds32"), ("closed", "host-sah-stack32-lds32"), ("closed", "host-sah-stack256-lds32")]
+MAXLEAF_DEV = 2   # rgk_commit.h BuildOptions::max_leaf_dev: at or below it a device request is answered by the host builder
+
+
+@pytest.fixture(scope="module")
+def rd(product_lib):
+    from rgk_amd import render_driver
+    assert product_lib.rgk_device_count() >= 1, "no HIP device: the product path has no fallback"
+    return render_driver
+
+
+def gpu_scene(rd, sb, builder):
+    """rd.Scene of `sb` by `builder`; the build switches are read once, in rgk_scene_create, and restored here."""
+    flags, env = BUILDERS[builder]
+    old = {k: os.environ.get(k) for k in env}
+    keep = getattr(sb, "build_flags", None)
+    os.environ.update(env)
+    sb.build_flags = flags
+    try:
+        return rd.Scene(sb.to_desc())
+    finally:
+        for k, v in old.items():
+            if v is None:
+                del os.environ[k]
+            else:
+                os.environ[k] = v
+        if keep is None:
+            del sb.build_flags
+        else:
+            sb.build_flags = keep
+
+
+@functools.lru_cache(maxsize=None)
+def _reference(name):
+    """Per scene, once: the builder, the oracle scene, the rays and pairs, and the exhaustive answers every builder must equal."""
+    from oracle import rgk_oracle as O
+    sb = T.SCENES[name]()
+    osc = O.OracleScene(sb.to_desc())
+    n_rays, n_pairs = SMALLER.get(name, (N_RAYS, N_RAYS))
+    kw = {}
+    if name == "flat":                                  # (the box is a slab: origins inside it would only see the triangles edge-on)
+        kw.update(in_plane_y=0.0, inside=((0.0, 0.0, 0.0), 6.0))
+    if name == "closed":
+        kw.update(inside=((0.0, 0.0, 0.0), 0.6), within=0.9)   # rays start inside the mesh (inradius 0.97): every one must come out through a triangle
+    rays = T.ray_mix(osc, n_rays, seed=100 + len(name), targets=T.targets_of(sb), **kw)
+    ex = osc.trace_closest_exhaustive(rays)
+    ig = ex["tri"].astype(np.int32)
+    ex2 = osc.trace_closest_exhaustive(rays, ig)
+    a, b = T.visibility_pairs(osc, n_pairs, seed=200 + len(name))
+    vis = osc.visibility_exhaustive(a, b)
+    return dict(sb=sb, osc=osc, rays=rays, ex=ex, ignore=ig, ex2=ex2, a=a, b=b, vis=vis)
+
+
+def assert_same_frame(g, osc):
+    """The window of the rule is made of epsilon and the padded box: the two sides must hold the same floats."""
+    gi, oi = g.info(), osc.info()
+    assert gi.epsilon == oi.epsilon and list(gi.bbox_min) == list(oi.bbox_min) and list(gi.bbox_max) == list(oi.bbox_max)
+
+
+def assert_equal_hits(name, rays, got, want):
+    bad = T.differing(got, want)
+    record_parity(name, rays=len(rays), hits=int((want["tri"] >= 0).sum()), differing=int(bad.sum()))
+    assert not bad.any(), f"{name}: {int(bad.sum())} of {len(rays)} rays differ: " + T.describe(rays, got, want, bad)
+
+
+@pytest.mark.parametrize("scene,builder", CASES, ids=[f"{s}-{b}" for s, b in CASES])
+def test_closest_hit_and_visibility_equal_the_exhaustive_search(rd, scene, builder):
+    """rgk_trace_closest (k_trace_closest), without and with `ignore` = the first hit, and rgk_trace_visibility against the
+    exhaustive reference.  rgk_trace_visibility launches k_trace_shadow only (any-hit, 48-byte records): the constant-light
+    kernels (k_trace_shadow_cl, k_trace_shadow_first_cl), k_trace_shadow_first and k_trace_shadow_jobs are reached through
+    rgk_render_round alone and stay with the switches-never-change-a-result tests, whose base this pins."""
+    ref = _reference(scene)
+    g = gpu_scene(rd, ref["sb"], builder)
+    assert_same_frame(g, ref["osc"])
+    n_tri = len(ref["sb"].F)
+    if builder.startswith("device") and n_tri <= MAXLEAF_DEV:
+        assert g.info().n_nodes >= 1       # the host builder answered: the scene builds and (below) answers
+    if scene == "deep" and builder.startswith("host-sah"):
+        assert g.info().max_depth >= 11, g.info().max_depth      # 3 pushes per level: more than 32 stack entries possible
+    if builder == "host-sah-stack32-lds32":   # 3 pushes per level and RGK_ENTRY_K = 6 entry nodes: max_depth <= 7 means at most 31 entries, the 32/32 walker
+        assert g.info().max_depth <= 7, g.info().max_depth
+    tag = f"gpu_exhaustive[{scene}-{builder}]"
+    rays = ref["rays"]
+    assert (ref["ex"]["tri"] >= 0).mean() > 0.25
+    hg, _ = g.trace_closest(rays)
+    assert_equal_hits(tag + ":closest", rays, hg, ref["ex"])
+    hg2, _ = g.trace_closest(rays, ref["ignore"])
+    assert_equal_hits(tag + ":ignore-first", rays, hg2, ref["ex2"])
+    vg, _ = g.visibility(ref["a"], ref["b"])
+    differ = int((vg != ref["vis"]).sum())
+    record_parity(tag + ":visibility", pairs=len(vg), visible=float(ref["vis"].mean()), differing=differ)
+    assert differ == 0, (differ, np.nonzero(vg != ref["vis"])[0][:10])
+    g.close()
+
+
+@functools.lru_cache(maxsize=None)
+def _dense_order(scene):
+    """An order of the scene's rays in which three of every four hit: position i with i % 4 == 1 holds a miss, every other one a
+    hit, those that also hit with the first hit ignored first.  So the prefixes of 1, 63, 64 and 65 rays end in a hit."""
+    ref = _reference(scene)
+    rng = np.random.default_rng(17)
+    hit, second = ref["ex"]["tri"] >= 0, ref["ex2"]["tri"] >= 0
+    hits = np.concatenate([rng.permutation(np.nonzero(hit & second)[0]), rng.permutation(np.nonzero(hit & ~second)[0])])
+    misses = rng.permutation(np.nonzero(~hit)[0])
+    n = min(len(hits) * 4 // 3, len(misses) * 4, len(hit))
+    order = np.empty(n, np.int64)
+    is_miss = np.arange(n) % 4 == 1
+    order[is_miss] = misses[:is_miss.sum()]
+    order[~is_miss] = hits[:(~is_miss).sum()]
+    return order
+
+
+@pytest.mark.parametrize("scene", ["count65", "duplicates"])
+@pytest.mark.parametrize("n", [0, 1, 63, 64, 65, 4097])
+def test_ray_counts_at_the_edges_of_a_wave_and_of_the_refill(rd, scene, n):
+    """The first n rays of an order dense in hits (three of four; on `duplicates` the first ~2 000 of them hit again with the
+    first hit ignored): one lane, a wave less one, a full wave, a wave and one, and more than one static slice of the persistent
+    walker's queue -- the last ray of each is a hit, so a lane that is dropped, swapped or mis-indexed at the end of a partial
+    wave shows.  n = 0: rgk_trace_closest and rgk_trace_visibility return before any launch."""
+    ref = _reference(scene)
+    sel = _dense_order(scene)[:n]
+    assert len(sel) == n
+    rays, ig, ex, ex2 = ref["rays"][sel], ref["ignore"][sel], ref["ex"][sel], ref["ex2"][sel]
+    if n:
+        assert ex["tri"][-1] >= 0 and ex["tri"][0] >= 0 and (ex["tri"] >= 0).sum() >= (3 * n) // 4
+        assert len(np.unique(ex["tri"][ex["tri"] >= 0])) >= min(n // 4, 8) or n == 1      # not one triangle over and over
+        if scene == "duplicates":
+            assert (ex2["tri"] >= 0).sum() >= n // 4 and (n > 65 or ex2["tri"][-1] >= 0)      # (about 2 300 rays hit twice: 4 097 outruns them)
+    g = gpu_scene(rd, ref["sb"], "host-sah")
+    hg, _ = g.trace_closest(rays)
+    assert_equal_hits(f"gpu_exhaustive[ray-count {scene} {n}]:closest", rays, hg, ex)
+    hg, _ = g.trace_closest(rays, ig)
+    assert_equal_hits(f"gpu_exhaustive[ray-count {scene} {n}]:ignore-first", rays, hg, ex2)
+    # pairs: every other one blocked as far as the scene has blocked pairs, the last one of the prefix among them
+    blocked, free = np.nonzero(ref["vis"] == 0)[0], np.nonzero(ref["vis"] == 1)[0]
+    m = min(n, 2 * len(blocked) - 1)
+    pick = np.empty(m, np.int64)
+    pick[(m - 1) % 2::2] = blocked[:len(pick[(m - 1) % 2::2])]
+    pick[m % 2::2] = free[:len(pick[m % 2::2])]
+    if m:
+        assert ref["vis"][pick[-1]] == 0
+    vg, _ = g.visibility(ref["a"][pick], ref["b"][pick])
+    differ = int((vg != ref["vis"][pick]).sum())
+    record_parity(f"gpu_exhaustive[ray-count {scene} {n}]:visibility", pairs=m, blocked=int((ref["vis"][pick] == 0).sum()), differing=differ)
+    assert differ == 0
+    g.close()
+
+
+@pytest.mark.parametrize("builder", ["host-sah", "device"])
+@pytest.mark.parametrize("scene", ["closed", "count257"])
+def test_refitted_tree_equals_the_exhaustive_search_on_the_moved_mesh(rd, oracle, scene, builder):
+    """rgk_scene_refit (k_refit_recs, k_qbvh_refit: new reference boxes, node boxes and 8-bit codes on the old topology): the
+    vertices twisted about the vertical axis and swollen by a few per cent of the scene size, then moved back.  After each
+    step the refitted scene must answer like the exhaustive search over the vertices it now holds -- aimed at their vertices
+    and edge midpoints, where a node box one step too tight drops the hit."""
+    sb = T.SCENES[scene]()
+    sb.finalize()
+    V0 = sb.V.copy()
+    ctr, ext = V0.mean(axis=0), np.ptp(V0, axis=0).max()
+    ang = 0.35 * (V0[:, 1] - ctr[1]) / ext
+    c, s_ = np.cos(ang), np.sin(ang)
+    V1 = V0.copy()
+    V1[:, 0] = ctr[0] + c * (V0[:, 0] - ctr[0]) - s_ * (V0[:, 2] - ctr[2])
+    V1[:, 2] = ctr[2] + s_ * (V0[:, 0] - ctr[0]) + c * (V0[:, 2] - ctr[2])
+    V1 = (V1 + 0.03 * ext * np.sin(3.0 * V0[:, [1, 2, 0]] / ext)).astype(np.float32)
+    g = gpu_scene(rd, sb, builder)
+    for step, V in (("moved", V1), ("back", V0)):
+        g.refit(V)
+        sb.vertices = [V]
+        osc = oracle.OracleScene(sb.to_desc())
+        assert_same_frame(g, osc)
+        kw = dict(inside=(tuple(ctr), 0.5)) if scene == "closed" else {}
+        rays = T.ray_mix(osc, N_RAYS, seed=7, targets=T.targets_of(sb), **kw)
+        ex = osc.trace_closest_exhaustive(rays)
+        assert (ex["tri"] >= 0).mean() > 0.25
+        hg, _ = g.trace_closest(rays)
+        assert_equal_hits(f"gpu_exhaustive[refit {scene}-{builder} {step}]", rays, hg, ex)
+        a, b = T.visibility_pairs(osc, N_RAYS, seed=8)
+        assert np.array_equal(g.visibility(a, b)[0], osc.visibility_exhaustive(a, b))
+    g.close()
+
+
+# ----------------------------------------------------------------------- the feature pass: camera rays made on the device
+def _camera_case(name, W, H):
+    from rgk_amd.workloads import Workload
+    if name == "cornell":
+        sb = Workload("cornell-256", scale=1.0, spp=1).builder
+        c = sb.extra["camera"]
+        return sb, make_camera(c["pos"], c["lookat"], c["up"], fov=c["fov"], xres=W, yres=H)
+    if name == "closed":     # from inside the mesh: every pixel sees a triangle, many pixel centres fall on shared edges
+        return T.SCENES["closed"](), make_camera((0.1, 0.2, 0.3), (1.0, 0.3, -0.2), (0, 1, 0), fov=70, xres=W, yres=H)
+    return T.SCENES["count65"](), make_camera((0.0, 0.0, 7.0), (0, 0, 0), (0, 1, 0), fov=75, xres=W, yres=H)   # (from among the triangles: 11 % of the pixels see one)
+
+
+@pytest.mark.parametrize("name", ["closed", "count65", "cornell"])
+@pytest.mark.parametrize("size", [(67, 45), (100, 70)])
+def test_feature_pass_equals_the_exhaustive_search_on_every_pixel(rd, oracle, name, size):
+    """rgk_render_aov with only tri and depth asked for, against the exhaustive reference on orc_camera_ray's pixel-centre rays,
+    for EVERY pixel of the frame.  The pass makes its rays on the device (k_aov_raygen: camera_ray, the function k_trace_camera
+    uses) and walks them with k_trace_closest; k_trace_camera, the beam walker and the entry-point lists are reached through
+    rgk_render_round alone.  At Cornell 100 x 70 this includes the 14 pixels on the back wall's diagonal that
+    test_features_equal_the_oracle_composition leaves out: the tie rule decides them."""
+    W, H = size
+    sb, cam = _camera_case(name, W, H)
+    osc = oracle.OracleScene(sb.to_desc())
+    rays = T.camera_rays(oracle, cam, W, H)
+    ex = osc.trace_closest_exhaustive(rays)
+    for builder in ("host-sah", "device"):
+        g = gpu_scene(rd, sb, builder)
+        assert_same_frame(g, osc)
+        prm = make_params(W, H, 1, 1)
+        tiles = rd.generate_task_list(W, H)
+        depth = np.full((H, W), 7.5, np.float32)
+        tri = np.full((H, W), 7, np.int32)
+        capi.check(g.lib, g.lib.rgk_render_aov(g.h, C.byref(cam), C.byref(prm), tiles, len(tiles), None, None, depth.ctypes.data, tri.ctypes.data))
+        want_z = np.where(ex["tri"] >= 0, ex["t"], np.float32(0)).astype(np.float32).reshape(H, W)
+        bad = (tri != ex["tri"].reshape(H, W)) | (T.bits(depth) != T.bits(want_z))
+        record_parity(f"gpu_exhaustive[aov {name} {W}x{H} {builder}]", rays=W * H, hits=int((ex["tri"] >= 0).sum()), differing=int(bad.sum()))
+        assert not bad.any(), (name, size, builder, int(bad.sum()), np.argwhere(bad)[:5].tolist())
+        g.close()
+    assert (ex["tri"] >= 0).mean() > (0.9 if name != "count65" else 0.08)

@@ -23,6 +23,7 @@ from rgk_amd.config import make_camera, make_params
 from rgk_amd.scene import SceneBuilder
 
 from conftest import ROOT, make_rays, record_parity
+import trace_ref as T
 
 pytestmark = pytest.mark.gpu
 
@@ -81,18 +82,17 @@ def test_sampler_matches_reference_golden_vectors(rd):
 
 
 # ----------------------------------------------------------------------- K2 / K5 traversal
-def random_rays(rng, lo, hi, n):
-    o = (lo + (hi - lo) * rng.uniform(0.02, 0.98, (n, 3))).astype(np.float32)
-    d = rng.normal(size=(n, 3)).astype(np.float32)
-    d /= np.linalg.norm(d, axis=1, keepdims=True)
-    return o, d
+random_rays = T.random_rays
 
 
 def check_closest(g, o, rays, eps, ignore=None, max_unexplained=2e-5, name=None):
     """Hits must agree in the triangle, and then bit for bit in t and the barycentrics.  Where the triangle differs both
     accelerators must have found hits whose distances tie within 2 epsilon (H3: the oracle's kd-tree and the BVH take
     exact / epsilon-band ties in different orders); anything else is `unexplained` and bounded by max_unexplained.  With
-    `name` the measured numbers go on record, and the first unexplained cases are dumped with both hits."""
+    `name` the measured numbers go on record, and the first unexplained cases are dumped with both hits.
+    Then the stated rule decides what the kd-tree walk cannot: every ray on which the two name different triangles (the first
+    5 000 of them) is traced again by exhaustive search (trace_ref.py), and the GPU's tri, t, a, b, c must be that answer --
+    each "tie" and each "unexplained" ray is the walker's by the rule of rgk_trace.h, or a failure (`exhaustive_disagree`)."""
     hg, _ = g.trace_closest(rays, ignore)
     ho, _ = o.trace_closest(rays, ignore)
     same = hg["tri"] == ho["tri"]
@@ -103,12 +103,28 @@ def check_closest(g, o, rays, eps, ignore=None, max_unexplained=2e-5, name=None)
     with np.errstate(invalid="ignore"):
         tie = both_hit & (np.abs(hg["t"] - ho["t"]) <= 2 * eps)
     unexplained = bad.sum() - tie.sum()
+    idx = np.nonzero(bad)[0][:5000]
+    rays8 = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
+    ex = o.trace_closest_exhaustive(rays8[idx], None if ignore is None else np.asarray(ignore)[idx])
+    disagree = T.differing(hg[idx], ex)
     if name:
-        record_parity(name, rays=len(rays), same_triangle=float(same.mean()), eps_band_ties=int(tie.sum()), unexplained=int(unexplained))
+        record_parity(name, rays=len(rays), same_triangle=float(same.mean()), eps_band_ties=int(tie.sum()), unexplained=int(unexplained),
+                      rechecked=len(idx), exhaustive_disagree=int(disagree.sum()))
         for i in np.where(bad & ~tie)[:1][0][:20]:
             print(f"[{name}] unexplained ray {i}: o={rays[i, :3]} d={rays[i, 3:6]} gpu tri {hg['tri'][i]} t {hg['t'][i]!r} | oracle tri {ho['tri'][i]} t {ho['t'][i]!r} | eps {eps}")
     assert unexplained <= max(1, max_unexplained * len(rays)), (int(bad.sum()), int(tie.sum()))
+    assert not disagree.any(), f"{int(disagree.sum())} of {len(idx)} re-checked rays: " + T.describe(rays8[idx], hg[idx], ex, disagree)
     return float(same.mean())
+
+
+def check_visibility_disagreements(g_vis, o_vis, o, a, b, name):
+    """The pairs on which the GPU and the kd-tree oracle disagree (the first 5 000), decided by exhaustive search in the same
+    window: the GPU's byte must be that answer."""
+    idx = np.nonzero(g_vis != o_vis)[0][:5000]
+    ex = o.visibility_exhaustive(np.asarray(a)[idx], np.asarray(b)[idx])
+    disagree = int((g_vis[idx] != ex).sum())
+    record_parity(name, pairs=len(g_vis), kd_disagree=int((g_vis != o_vis).sum()), rechecked=len(idx), exhaustive_disagree=disagree)
+    assert disagree == 0, (name, disagree, idx[g_vis[idx] != ex][:10])
 
 
 def test_closest_hit_cornell_bit_exact(rd, oracle, cornell):
@@ -385,6 +401,7 @@ def test_deep_tree_stack_overflow_variant(rd, oracle):
     vg, _ = g.visibility(oo[:50000], oo[50000:100000])
     vo, _ = o.visibility(oo[:50000], oo[50000:100000])
     assert (vg != vo).mean() < 2e-3
+    check_visibility_disagreements(vg, vo, o, oo[:50000], oo[50000:100000], "test_deep_tree_stack_overflow_variant:visibility")
 
 
 def test_envmap_sky_float_texture(rd, oracle):
@@ -1041,7 +1058,9 @@ def test_device_built_bvh_gives_the_same_hits(rd, oracle):
         a = (lo + (hi - lo) * np.random.default_rng(42).uniform(0.02, 0.98, (100000, 3))).astype(np.float32)
         b = (lo + (hi - lo) * np.random.default_rng(43).uniform(0.02, 0.98, (100000, 3))).astype(np.float32)
         assert (gh.visibility(a, b)[0] == gd.visibility(a, b)[0]).mean() > 0.9999
-        assert (o.visibility(a, b)[0] != gd.visibility(a, b)[0]).mean() < 2e-3
+        vo, vd = o.visibility(a, b)[0], gd.visibility(a, b)[0]
+        assert (vo != vd).mean() < 2e-3
+        check_visibility_disagreements(vd, vo, o, a, b, "test_device_built_bvh_gives_the_same_hits:" + name + ":visibility")
         prm = wl.params()
         tiles = rd.generate_task_list(wl.xres, wl.yres)
         ah = gh.render_round(wl.camera, prm, tiles)[0]
