@@ -446,9 +446,57 @@ int rgk_denoise_device(rgk_scene *scene, uint32_t xres, uint32_t yres, const flo
                        float *d_out_rgb);
 
 /* HIP-event times of the launches of the LAST feature pass (which = 0: pixel list + ray generation, walker, gather) or denoise
- * call (which = 1: preparation, one per iteration, finish) on this scene, in ms; recorded only while the tuning key "time_post"
- * is 1.  *n: in, room in ms; out, entries the call had (those that fit are written). */
+ * call (which = 1: preparation, one per iteration, finish), variance-guided denoise call (which = 2: preparation, prefilter, one
+ * per iteration, finish [, variance copy]) or noise estimate (which = 3: the tile sums) on this scene, in ms; recorded only while
+ * the tuning key "time_post" is 1. *n: in, room in ms; out, entries the call had (those that fit are written). */
 int rgk_scene_get_post_timing(const rgk_scene *scene, uint32_t which, double *ms, uint32_t *n);
+
+/* ---- noise estimate from two half-buffers and the variance-guided filter (DESIGN.md "Half-buffer noise estimate") ----
+ *
+ * The caller keeps, beside the frame's accumulator {S, n}, a second one {S_B, n_B} that received the odd rounds only (n_B <= n).
+ * Per pixel, in float32, only + - * / max, no contraction, in the order written:
+ *   n_A = n - n_B,  a = (S - S_B) / n_A,  b = S_B / n_B,  c = S / n  (0 where n == 0)
+ *   estimable: n_A > 0 and n_B > 0;  f = ((float)n_A * (float)n_B) / ((float)n * (float)n)
+ *   v = ((h.r^2 + h.g^2) + h.b^2) * f,  h = a - b;  0 where the pixel is not estimable
+ * v is the variance of c (|a - b|^2 / 4 for equal halves).
+ *
+ * Workspace: both entries use the scene's post-processing planes -- the two colour planes and the guide plane rgk_denoise_device
+ * uses, and a tile array of their own -- and nothing else: no buffer, list or counter a round reads or writes.  A call between two
+ * rounds of a frame changes nothing those rounds compute; a call overwrites what an earlier post-processing call left in the planes
+ * (every entry is blocking and has delivered its outputs by then).  Not while a round is in flight on this scene.  Arguments are
+ * checked before the scene or the device is touched. */
+
+/* Statistics of one tile of tile_size x tile_size pixels (ragged at the right and bottom edges) over its ESTIMABLE pixels:
+ * sum_var = sum of v, sum_sq = sum of ((c.r^2 + c.g^2) + c.b^2), accumulated in double from the float32 per-pixel terms (no scene
+ * features, nothing demodulated).  A frame's relative noise is sqrt(sum of sum_var / sum of sum_sq), tiles added in row-major order:
+ * an estimate of |c - converged image| / |c|. */
+typedef struct rgk_noise_tile { double sum_var, sum_sq; uint64_t n_estimable; } rgk_noise_tile;
+/* per-tile statistics of a frame; tiles: host array of ceil(xres/ts)*ceil(yres/ts), row-major; d_variance (P floats, raw v) may be NULL.
+ * The other pointers are DEVICE pointers on the scene's GPU; tile_size >= 1; whole frame; blocking. */
+int rgk_noise_estimate_device(rgk_scene *scene, uint32_t xres, uint32_t yres, uint32_t tile_size,
+                              const float *d_accum_rgb, const uint32_t *d_accum_count, const float *d_half_rgb,
+                              const uint32_t *d_half_count, rgk_noise_tile *tiles, float *d_variance);
+
+/* The a-trous filter of rgk_denoise_device with the colour weight taken from the pixels' own variances instead of one sigma_color.
+ * Guide plane, wn, wz, h[], tap order, the live-pixel rule (zero normal: passes through, never a tap), taps outside the frame and
+ * "iterations == 0: out = c" are rgk_denoise_device's.  What differs:
+ *   div = albedo > 0 ? max(albedo, albedo_floor) : 1 per channel when `demodulate`; a, b and c are each divided by div, v is computed
+ *   from the demodulated a and b, and the result is multiplied back by the same div
+ *   prefilter, 5 x 5, step 1:  var_p = sum((wn * wz) * v_q) / sum(wn * wz) over the live taps (a pixel that is not live keeps v_p)
+ *   iteration i, step 2^i, k2 = sigma_k * sigma_k:
+ *     wc = 1 / (1 + d2 / (k2 * (var_p + var_q) + 1e-20f)),  d2 = |c_p - c_q|^2
+ *     w  = (((h[dy] * h[dx]) * wn) * wz) * wc
+ *     c'_p = sum(w * c_q) / sum(w),   var'_p = sum((w * w) * var_q) / (sum(w) * sum(w))
+ * out_variance: the variance plane after the last iteration -- of the filtered image, in the space the filter ran in (divided by
+ * div^2 in effect when `demodulate`); with iterations == 0 it is the raw v.  sigma_k > 0, albedo_floor >= 0, sigma_depth >= 0, all
+ * finite; iterations, normal_power_log2 <= 16. */
+typedef struct rgk_denoise_var_params { uint32_t iterations; float sigma_k, sigma_depth; uint32_t normal_power_log2, demodulate; float albedo_floor; } rgk_denoise_var_params;
+/* d_albedo may be NULL when demodulate == 0; out_rgb: 3P floats, out_variance: P floats or NULL, neither one of the inputs.  All DEVICE
+ * pointers on the scene's GPU; whole frame; blocking. */
+int rgk_denoise_variance_device(rgk_scene *scene, uint32_t xres, uint32_t yres, const float *d_accum_rgb, const uint32_t *d_accum_count,
+                                const float *d_half_rgb, const uint32_t *d_half_count, const float *d_albedo, const float *d_normal,
+                                const float *d_depth, const rgk_denoise_var_params *params, float *d_out_rgb,
+                                float *d_out_variance /* P, the filtered image's variance, may be NULL */);
 
 /* The pinned transcendental functions of the path (include/rgk_libm.h) evaluated on the device, for the test that the GPU
  * and the CPU produce the same bits: fn 0 sin, 1 cos, 2 acos, 3 asin, 4 atan2(a[i], b[i]) (b may be NULL otherwise). */

@@ -18,6 +18,12 @@
                     `normal` (world space, as lit) and `depth` (the ray's t in R, G and B; 0 where nothing is hit)
   --denoise         also writes the output name with the suffix `denoised` after every round: the round's image through the
                     feature-guided a-trous filter, normalised with the scale the plain output got.  The plain output is unchanged
+  --noise           keeps a second accumulator of the odd rounds (the half-buffer noise estimate): prints the frame's relative noise
+                    after every round from the second on, writes the output name with the suffix `noise` -- sqrt of the
+                    variance-guided filter's output variance in R, G and B, scaled like the plain output -- after every round that
+                    rewrites the output, and makes --denoise use the variance-guided filter from round 2 on.  With --checkpoint
+                    the half-buffer is saved beside the checkpoint as `F.half`; resuming a checkpoint that has none is refused
+  --until-noise X   implies --noise; stops the frame once the relative noise is <= X (rounds / -t still bound it)
 FILE is a .json or .rtc scene config.  One process drives one GPU; several GPUs: python -m torch.distributed.run ... bench.py.
 """
 import argparse
@@ -77,6 +83,8 @@ def main(argv=None):
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--aov", action="store_true")
     ap.add_argument("--denoise", action="store_true")
+    ap.add_argument("--noise", action="store_true")
+    ap.add_argument("--until-noise", type=float, default=None, metavar="X")
     ap.add_argument("--frames", type=int, default=None, help="with -r: stop after this many frames (default: all 501)")
     args = ap.parse_args(argv)
     verbosity = max(0, 2 + args.v - args.q)
@@ -93,6 +101,13 @@ def main(argv=None):
         cfg.render_minutes, cfg.render_rounds = args.timed, 1
     if args.scale is not None:
         cfg.output_scale = args.scale
+    track_noise = args.noise or args.until_noise is not None
+    if args.until_noise is not None and not args.until_noise > 0:
+        print("ERROR: Invalid argument for --until-noise.")
+        return 1
+    if track_noise and not args.rotate and args.checkpoint and os.path.exists(args.checkpoint) and not os.path.exists(args.checkpoint + ".half"):
+        print(f"ERROR: cannot resume from `{args.checkpoint}`: {rd.missing_half_message(args.checkpoint)}")  # (before the scene is built and a GPU is asked for)
+        return 1
     output_file = os.path.join(args.dir, cfg.output_file) if args.dir else cfg.output_file
     if args.preview:
         output_file = insert_file_suffix(output_file, "preview")
@@ -126,7 +141,7 @@ def main(argv=None):
             open(out, "ab").close()  # claim the frame before rendering it (processes sharing the directory skip it)
             say(1, f"Rendering frame #{frame_no} of ~{int(time_length * fps)} ({format_percent(t / time_length * 100.0)})")
         camera = cfg.get_camera(t / time_length if args.rotate else 0.0)
-        drv = rd.RenderDriver(scene, cfg, camera, device=device)
+        drv = rd.RenderDriver(scene, cfg, camera, device=device, track_noise=track_noise)
         if args.debug:
             x, y = args.debug
             if not (0 <= x < cfg.xres and 0 <= y < cfg.yres):
@@ -159,7 +174,9 @@ def main(argv=None):
         with FrameMonitor(scene, timed, cfg.render_rounds, cfg.render_minutes or 0, cfg.xres * cfg.yres, verbosity=verbosity) as mon:
             drv.render_frame(rounds=max(0, cfg.render_rounds - drv.rounds_done) if not timed else None, output_file=out, checkpoint=ckpt,
                              aov_files={k: insert_file_suffix(out, k) for k in ("albedo", "normal", "depth")} if args.aov else None,
-                             denoised_file=insert_file_suffix(out, "denoised") if args.denoise else None)
+                             denoised_file=insert_file_suffix(out, "denoised") if args.denoise else None,
+                             **(dict(until_noise=args.until_noise, noise_file=insert_file_suffix(out, "noise"),
+                                     on_noise=lambda r, rel: say(1, f"Round {r}: relative noise {rel:.4g}")) if track_noise else {}))
             mon.rays_done = sum(c.path_rays for c in drv.counters)
     return 0
 

@@ -134,6 +134,20 @@ class DenoiseParams(C.Structure):
         super().__init__(iterations, sigma_color, sigma_depth, normal_power_log2, demodulate)
 
 
+class NoiseTile(C.Structure):
+    """rgk_noise_tile: sums over a tile's estimable pixels."""
+    _fields_ = [("sum_var", C.c_double), ("sum_sq", C.c_double), ("n_estimable", C.c_uint64)]
+
+
+class DenoiseVarParams(C.Structure):
+    """rgk_denoise_var_params; the defaults are the shipped ones (sigma_k and albedo_floor: the minimum of tools/noise_sweep.py)."""
+    _fields_ = [("iterations", C.c_uint32), ("sigma_k", C.c_float), ("sigma_depth", C.c_float),
+                ("normal_power_log2", C.c_uint32), ("demodulate", C.c_uint32), ("albedo_floor", C.c_float)]
+
+    def __init__(self, iterations=5, sigma_k=3.0, sigma_depth=0.02, normal_power_log2=6, demodulate=1, albedo_floor=0.25):
+        super().__init__(iterations, sigma_k, sigma_depth, normal_power_log2, demodulate, albedo_floor)
+
+
 # every symbol include/rgk.h declares (tests check the .so exports all of them)
 EXPORTS = ["rgk_last_error", "rgk_device_count", "rgk_scene_create", "rgk_scene_destroy",
            "rgk_scene_get_info", "rgk_scene_get_progress", "rgk_scene_set_tuning", "rgk_scene_refit", "rgk_generate_task_list", "rgk_camera_init", "rgk_render_round",
@@ -143,7 +157,8 @@ EXPORTS = ["rgk_last_error", "rgk_device_count", "rgk_scene_create", "rgk_scene_
            "rgk_accum_create", "rgk_accum_destroy", "rgk_accum_clear", "rgk_accum_rgb", "rgk_accum_count",
            "rgk_accum_download", "rgk_accum_upload", "rgk_accum_add", "rgk_accum_set_tag", "rgk_accum_save", "rgk_accum_load",
            "rgk_shard_tiles", "rgk_comm_get_unique_id", "rgk_comm_create", "rgk_comm_destroy", "rgk_accum_reduce",
-           "rgk_render_aov_device", "rgk_render_aov", "rgk_denoise_device", "rgk_scene_get_post_timing"]
+           "rgk_render_aov_device", "rgk_render_aov", "rgk_denoise_device", "rgk_scene_get_post_timing",
+           "rgk_noise_estimate_device", "rgk_denoise_variance_device"]
 
 _p = C.POINTER
 
@@ -201,6 +216,10 @@ def _bind(lib):
     lib.rgk_render_aov.argtypes = lib.rgk_render_aov_device.argtypes
     lib.rgk_denoise_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        _p(DenoiseParams), C.c_void_p]
+    lib.rgk_noise_estimate_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              _p(NoiseTile), C.c_void_p]
+    lib.rgk_denoise_variance_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, _p(DenoiseVarParams), C.c_void_p, C.c_void_p]
     lib.rgk_scene_get_post_timing.argtypes = [C.c_void_p, C.c_uint32, _p(C.c_double), _p(C.c_uint32)]
     lib.rgk_float_to_half.argtypes = [C.c_float]
     lib.rgk_float_to_half.restype = C.c_uint16

@@ -93,7 +93,9 @@ struct RgkTuning {
     bool time_post = false;   // feature pass / denoiser: HIP events around their launches (rgk_scene_get_post_timing)
 };
 
+constexpr uint32_t RGK_SCENE_MAGIC = 0x53474b52u; // "RKGS": what a live scene handle starts with (rgk_scene_get_post_timing)
 struct rgk_scene {
+    uint32_t magic = RGK_SCENE_MAGIC;
     int device = 0;
     RgkTuning tune;
     hipStream_t stream = nullptr;
@@ -151,7 +153,8 @@ struct rgk_scene {
     DevBuf<float> scratch_f;
     DevBuf<uint32_t> scratch_u;
     DevBuf<float4> dn_col[2], dn_guide; // the denoiser's two colour planes and its guide plane {n.xyz, z}
-    std::vector<double> post_ms[2];     // launch times of the last feature pass [0] / denoise call [1] (tuning "time_post")
+    DevBuf<rgk_noise_tile> nz_tiles;    // the noise estimate's per-tile sums
+    std::vector<double> post_ms[4];     // launch times of the last feature pass [0] / denoise call [1] / variance-guided denoise call [2] / noise estimate [3] (tuning "time_post")
     std::vector<hipEvent_t> events;
     uint32_t* h_counters = nullptr; // pinned
     // progress, read by rgk_scene_get_progress from any thread
@@ -162,6 +165,7 @@ struct rgk_scene {
     // by then: the body waits for the stream first (an entry point waits for the work it queued before it returns, but one
     // that fails halfway may leave some behind).
     ~rgk_scene() {
+        magic = 0;
         (void)hipSetDevice(device);
         if (stream) (void)hipStreamSynchronize(stream);
         for (auto e : events) (void)hipEventDestroy(e);
@@ -1249,15 +1253,93 @@ int rgk_denoise_device(rgk_scene* s, uint32_t xres, uint32_t yres, const float* 
         rgk_launch_dn_atrous(st, xres, yres, 1u << i, sigma2[i], dp->sigma_depth, dp->normal_power_log2, s->dn_guide.p, s->dn_col[i & 1].p, s->dn_col[(i & 1) ^ 1].p);
         if ((rc = tm.mark())) return rc;
     }
-    rgk_launch_dn_finish(st, P, s->dn_col[it & 1].p, d_albedo, demod, d_out_rgb);
+    rgk_launch_dn_finish(st, P, s->dn_col[it & 1].p, d_albedo, demod, 0.0f, d_out_rgb);
     if ((rc = tm.mark())) return rc;
     HIPCHK(hipStreamSynchronize(st));
     HIPCHK(hipGetLastError());
     return tm.fold(s->post_ms[1]);
 }
 
+int rgk_noise_estimate_device(rgk_scene* s, uint32_t xres, uint32_t yres, uint32_t tile_size, const float* d_accum_rgb, const uint32_t* d_accum_count,
+                              const float* d_half_rgb, const uint32_t* d_half_count, rgk_noise_tile* tiles, float* d_variance) {
+    // (every check before the scene or the device is touched)
+    if (!s || !d_accum_rgb || !d_accum_count || !d_half_rgb || !d_half_count || !tiles) return fail(RGK_ERR_INVALID, "null argument");
+    if (xres == 0 || yres == 0 || xres > 65535 || yres > 65535) return fail(RGK_ERR_INVALID, "resolution out of range");
+    if (tile_size == 0) return fail(RGK_ERR_INVALID, "tile_size must be >= 1");
+    if (d_variance && (d_variance == d_accum_rgb || d_variance == d_half_rgb || (const void*)d_variance == d_accum_count || (const void*)d_variance == d_half_count))
+        return fail(RGK_ERR_INVALID, "variance must not be one of the inputs");
+    if (d_half_rgb == d_accum_rgb || d_half_count == d_accum_count) return fail(RGK_ERR_INVALID, "the half-buffer must not be the accumulator");
+    if (s->prog_busy.load()) return fail(RGK_ERR_INVALID, "rgk_noise_estimate_device while a round is in flight on this scene");
+    HIPCHK(hipSetDevice(s->device));
+    const RgkGrid2 g = rgk_nz_tile_grid(xres, yres, tile_size);
+    int rc;
+    if ((rc = s->nz_tiles.alloc(g.count()))) return rc;
+    hipStream_t st = s->stream;
+    PostTimer tm(s);
+    s->post_ms[3].clear();
+    if ((rc = tm.mark())) return rc;
+    rgk_launch_nz_tile_sums(st, xres, yres, tile_size, d_accum_rgb, d_accum_count, d_half_rgb, d_half_count, s->nz_tiles.p, d_variance);
+    if ((rc = tm.mark())) return rc;
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    if ((rc = down(tiles, s->nz_tiles, g.count()))) return rc;
+    return tm.fold(s->post_ms[3]);
+}
+
+int rgk_denoise_variance_device(rgk_scene* s, uint32_t xres, uint32_t yres, const float* d_accum_rgb, const uint32_t* d_accum_count, const float* d_half_rgb,
+                                const uint32_t* d_half_count, const float* d_albedo, const float* d_normal, const float* d_depth,
+                                const rgk_denoise_var_params* dp, float* d_out_rgb, float* d_out_variance) {
+    // (every check before the scene or the device is touched)
+    if (!s || !d_accum_rgb || !d_accum_count || !d_half_rgb || !d_half_count || !d_normal || !d_depth || !dp || !d_out_rgb) return fail(RGK_ERR_INVALID, "null argument");
+    if (dp->demodulate && !d_albedo) return fail(RGK_ERR_INVALID, "demodulate without an albedo plane");
+    if (xres == 0 || yres == 0 || xres > 65535 || yres > 65535) return fail(RGK_ERR_INVALID, "resolution out of range");
+    if (dp->iterations > 16 || dp->normal_power_log2 > 16) return fail(RGK_ERR_INVALID, "iterations and normal_power_log2 must be <= 16");
+    if (!(dp->sigma_k > 0.0f) || !(dp->sigma_depth >= 0.0f) || !(dp->albedo_floor >= 0.0f) || std::isinf(dp->sigma_k) || std::isinf(dp->sigma_depth) || std::isinf(dp->albedo_floor))
+        return fail(RGK_ERR_INVALID, "sigma_k must be > 0, sigma_depth and albedo_floor >= 0, all finite");
+    const float k2 = dp->sigma_k * dp->sigma_k;
+    if (!(k2 > 0.0f) || std::isinf(k2)) return fail(RGK_ERR_INVALID, "sigma_k^2 leaves the float range");
+    if (d_half_rgb == d_accum_rgb || d_half_count == d_accum_count) return fail(RGK_ERR_INVALID, "the half-buffer must not be the accumulator");
+    const void* ins[] = {d_accum_rgb, d_accum_count, d_half_rgb, d_half_count, d_albedo, d_normal, d_depth};
+    for (const void* in : ins)
+        if (in && (in == (const void*)d_out_rgb || in == (const void*)d_out_variance)) return fail(RGK_ERR_INVALID, "out_rgb and out_variance must not be one of the inputs");
+    if ((const void*)d_out_rgb == (const void*)d_out_variance) return fail(RGK_ERR_INVALID, "out_rgb and out_variance must differ");
+    if (s->prog_busy.load()) return fail(RGK_ERR_INVALID, "rgk_denoise_variance_device while a round is in flight on this scene");
+    HIPCHK(hipSetDevice(s->device));
+    const size_t P = (size_t)xres * yres;
+    const uint32_t it = dp->iterations, demod = (it && dp->demodulate) ? 1u : 0u; // no iteration: out = c, variance = v, nothing to demodulate for
+    int rc;
+    if ((rc = s->dn_col[0].alloc(P)) || (it && ((rc = s->dn_col[1].alloc(P)) || (rc = s->dn_guide.alloc(P))))) return rc;
+    hipStream_t st = s->stream;
+    PostTimer tm(s);
+    s->post_ms[2].clear();
+    if ((rc = tm.mark())) return rc;
+    rgk_launch_nz_prepare(st, P, d_accum_rgb, d_accum_count, d_half_rgb, d_half_count, d_albedo, d_normal, d_depth, demod, dp->albedo_floor, s->dn_col[0].p,
+                          it ? s->dn_guide.p : nullptr);
+    if ((rc = tm.mark())) return rc;
+    uint32_t cur = 0; // the plane that holds the current image
+    if (it) {
+        rgk_launch_nz_prefilter(st, xres, yres, dp->sigma_depth, dp->normal_power_log2, s->dn_guide.p, s->dn_col[0].p, s->dn_col[1].p);
+        cur = 1;
+        if ((rc = tm.mark())) return rc;
+    }
+    for (uint32_t i = 0; i < it; i++, cur ^= 1u) {
+        rgk_launch_nz_atrous(st, xres, yres, 1u << i, k2, dp->sigma_depth, dp->normal_power_log2, s->dn_guide.p, s->dn_col[cur].p, s->dn_col[cur ^ 1u].p);
+        if ((rc = tm.mark())) return rc;
+    }
+    rgk_launch_dn_finish(st, P, s->dn_col[cur].p, d_albedo, demod, dp->albedo_floor, d_out_rgb);
+    if ((rc = tm.mark())) return rc;
+    if (d_out_variance) {
+        rgk_launch_nz_finish(st, P, s->dn_col[cur].p, d_out_variance);
+        if ((rc = tm.mark())) return rc;
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    return tm.fold(s->post_ms[2]);
+}
+
 int rgk_scene_get_post_timing(const rgk_scene* s, uint32_t which, double* ms, uint32_t* n) {
-    if (!s || !n || which > 1 || (!ms && *n)) return fail(RGK_ERR_INVALID, "bad argument");
+    if (!s || !n || which > 3 || (!ms && *n)) return fail(RGK_ERR_INVALID, "bad argument");
+    if (s->magic != RGK_SCENE_MAGIC) return fail(RGK_ERR_INVALID, "not a live scene handle");
     const std::vector<double>& v = s->post_ms[which];
     for (uint32_t i = 0; i < *n && i < v.size(); i++) ms[i] = v[i];
     *n = (uint32_t)v.size();

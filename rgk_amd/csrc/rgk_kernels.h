@@ -131,4 +131,13 @@ void rgk_launch_dn_prepare(hipStream_t st, size_t P, const float* accum_rgb, con
                            uint32_t demodulate, float4* col, float4* guide);
 void rgk_launch_dn_atrous(hipStream_t st, uint32_t xres, uint32_t yres, uint32_t step, float sigma2, float sigma_depth, uint32_t npow, const float4* guide,
                           const float4* src, float4* dst);
-void rgk_launch_dn_finish(hipStream_t st, size_t P, const float4* col, const float* albedo, uint32_t demodulate, float* out_rgb);
+void rgk_launch_dn_finish(hipStream_t st, size_t P, const float4* col, const float* albedo, uint32_t demodulate, float albedo_floor, float* out_rgb);
+// ... the noise estimate from two half-buffers and the variance-guided filter (grids: rgk_plan.h rgk_nz_*)
+void rgk_launch_nz_tile_sums(hipStream_t st, uint32_t xres, uint32_t yres, uint32_t tile_size, const float* accum_rgb, const uint32_t* accum_count,
+                             const float* half_rgb, const uint32_t* half_count, rgk_noise_tile* tiles, float* variance);
+void rgk_launch_nz_prepare(hipStream_t st, size_t P, const float* accum_rgb, const uint32_t* accum_count, const float* half_rgb, const uint32_t* half_count,
+                           const float* albedo, const float* normal, const float* depth, uint32_t demodulate, float albedo_floor, float4* col, float4* guide);
+void rgk_launch_nz_prefilter(hipStream_t st, uint32_t xres, uint32_t yres, float sigma_depth, uint32_t npow, const float4* guide, const float4* src, float4* dst);
+void rgk_launch_nz_atrous(hipStream_t st, uint32_t xres, uint32_t yres, uint32_t step, float k2, float sigma_depth, uint32_t npow, const float4* guide,
+                          const float4* src, float4* dst);
+void rgk_launch_nz_finish(hipStream_t st, size_t P, const float4* col, float* out_variance);

@@ -97,6 +97,7 @@ void rgk_launch_aov_gather(hipStream_t st, const DevScene& sc, float bumpmap_sca
 
 // ------------------------------------------------------------------ denoiser
 __device__ __forceinline__ float demod_div(float a) { return a > 0.0f ? a : 1.0f; }
+__device__ __forceinline__ float demod_div(float a, float floor_) { return a > 0.0f ? fmaxf(a, floor_) : 1.0f; }
 
 __global__ __launch_bounds__(256) void k_dn_prepare(size_t P, const float* __restrict__ accum_rgb, const uint32_t* __restrict__ accum_count,
                                                      const float* __restrict__ albedo, const float* __restrict__ normal, const float* __restrict__ depth,
@@ -204,12 +205,14 @@ __global__ __launch_bounds__(RGK_DN_BX * RGK_DN_BY) void k_dn_atrous_lds(int xre
     dst[p] = dn_result(sum, cp);
 }
 
-__global__ __launch_bounds__(256) void k_dn_finish(size_t P, const float4* __restrict__ col, const float* __restrict__ albedo, uint32_t demodulate, float* __restrict__ out_rgb) {
+// (albedo_floor: 0 for the fixed-sigma filter -- max(a, 0) == a for a > 0 -- and the variance-guided filter's floor on its divisor)
+__global__ __launch_bounds__(256) void k_dn_finish(size_t P, const float4* __restrict__ col, const float* __restrict__ albedo, uint32_t demodulate, float albedo_floor,
+                                                    float* __restrict__ out_rgb) {
     const size_t p = (size_t)blockIdx.x * 256u + threadIdx.x;
     if (p >= P) return;
     const float4 c = col[p];
     f3 o = mk3(c.x, c.y, c.z);
-    if (demodulate) { o.x = o.x * demod_div(albedo[3 * p]); o.y = o.y * demod_div(albedo[3 * p + 1]); o.z = o.z * demod_div(albedo[3 * p + 2]); }
+    if (demodulate) { o.x = o.x * demod_div(albedo[3 * p], albedo_floor); o.y = o.y * demod_div(albedo[3 * p + 1], albedo_floor); o.z = o.z * demod_div(albedo[3 * p + 2], albedo_floor); }
     out_rgb[3 * p] = o.x; out_rgb[3 * p + 1] = o.y; out_rgb[3 * p + 2] = o.z;
 }
 
@@ -226,6 +229,258 @@ void rgk_launch_dn_atrous(hipStream_t st, uint32_t xres, uint32_t yres, uint32_t
     if (step == 2) { k_dn_atrous_lds<2><<<grid, block, 0, st>>>((int)xres, (int)yres, sigma2, sigma_depth, npow, guide, src, dst); return; }
     k_dn_atrous<<<grid, block, 0, st>>>((int)xres, (int)yres, (int)step, sigma2, sigma_depth, npow, guide, src, dst);
 }
-void rgk_launch_dn_finish(hipStream_t st, size_t P, const float4* col, const float* albedo, uint32_t demodulate, float* out_rgb) {
-    k_dn_finish<<<(unsigned)((P + 255) / 256), 256, 0, st>>>(P, col, albedo, demodulate, out_rgb);
+void rgk_launch_dn_finish(hipStream_t st, size_t P, const float4* col, const float* albedo, uint32_t demodulate, float albedo_floor, float* out_rgb) {
+    k_dn_finish<<<(unsigned)((P + 255) / 256), 256, 0, st>>>(P, col, albedo, demodulate, albedo_floor, out_rgb);
+}
+
+// ------------------------------------------------------------------ noise estimate and the variance-guided filter
+//   k_nz_tile_sums  accumulator + the odd rounds' half-buffer -> per tile {sum of v, sum of |c|^2, estimable pixels} (doubles), raw v plane
+//   k_nz_prepare    the same two buffers -> colour plane {c.rgb, v} (demodulated with a floored divisor on request), guide plane
+//   k_nz_prefilter  5 x 5, step 1: v -> the guide-weighted mean of its neighbourhood
+//   k_nz_atrous     one iteration: the a-trous taps with wc from the two pixels' variances, variance carried in the plane's 4th float
+//   k_nz_finish     the plane's 4th float -> a plane of P floats (the image itself leaves through k_dn_finish)
+// Formulas: rgk.h rgk_noise_estimate_device / rgk_denoise_variance_device; the numpy restatement is tests/noise_ref.py.
+struct NzPixel {
+    f3 c, a, b; // mean of all rounds, of the even rounds, of the odd rounds
+    float f;    // n_A * n_B / n^2
+    bool est;   // both halves hold samples
+};
+__device__ __forceinline__ NzPixel nz_pixel(size_t p, const float* __restrict__ accum_rgb, const uint32_t* __restrict__ accum_count,
+                                            const float* __restrict__ half_rgb, const uint32_t* __restrict__ half_count) {
+    NzPixel r;
+    r.c = r.a = r.b = mk3(0.f, 0.f, 0.f);
+    r.f = 0.f;
+    const uint32_t n = accum_count[p], nB = half_count[p];
+    r.est = nB > 0u && nB < n;
+    if (n) {
+        const f3 S = mk3(accum_rgb[3 * p], accum_rgb[3 * p + 1], accum_rgb[3 * p + 2]);
+        r.c = S / (float)n;
+        if (r.est) {
+            const f3 SB = mk3(half_rgb[3 * p], half_rgb[3 * p + 1], half_rgb[3 * p + 2]);
+            const uint32_t nA = n - nB;
+            r.a = (S - SB) / (float)nA;
+            r.b = SB / (float)nB;
+            r.f = ((float)nA * (float)nB) / ((float)n * (float)n);
+        }
+    }
+    return r;
+}
+__device__ __forceinline__ float nz_variance(f3 a, f3 b, float f) {
+    const f3 h = a - b;
+    return ((h.x * h.x + h.y * h.y) + h.z * h.z) * f;
+}
+
+// One workgroup per tile.  Lane t takes the tile's pixels t, t + 256, ... (row-major inside the tile) into double partial sums; the
+// 256 partials are then folded in LDS in a fixed order (s[t] += s[t + 128], + 64, ... + 1): no atomics, the same bits every run.
+__global__ __launch_bounds__(RGK_NZ_BLOCK) void k_nz_tile_sums(uint32_t xres, uint32_t yres, uint32_t tile_size, const float* __restrict__ accum_rgb,
+                                                                const uint32_t* __restrict__ accum_count, const float* __restrict__ half_rgb,
+                                                                const uint32_t* __restrict__ half_count, rgk_noise_tile* __restrict__ tiles,
+                                                                float* __restrict__ variance) {
+    __shared__ double s_v[RGK_NZ_BLOCK], s_q[RGK_NZ_BLOCK];
+    __shared__ unsigned long long s_n[RGK_NZ_BLOCK];
+    const uint64_t x0 = (uint64_t)blockIdx.x * tile_size, y0 = (uint64_t)blockIdx.y * tile_size; // (< xres, yres: the grid is ceil(res / tile_size))
+    const uint64_t tw = min((uint64_t)tile_size, (uint64_t)xres - x0), th = min((uint64_t)tile_size, (uint64_t)yres - y0);
+    double sv = 0.0, sq = 0.0;
+    unsigned long long ne = 0;
+    for (uint64_t k = threadIdx.x; k < tw * th; k += RGK_NZ_BLOCK) {
+        const uint64_t ty = k / tw, tx = k - ty * tw;
+        const size_t p = (size_t)(y0 + ty) * xres + (size_t)(x0 + tx);
+        const NzPixel px = nz_pixel(p, accum_rgb, accum_count, half_rgb, half_count);
+        const float v = px.est ? nz_variance(px.a, px.b, px.f) : 0.0f;
+        if (variance) variance[p] = v;
+        if (px.est) {
+            sv += (double)v;
+            sq += (double)((px.c.x * px.c.x + px.c.y * px.c.y) + px.c.z * px.c.z);
+            ne++;
+        }
+    }
+    s_v[threadIdx.x] = sv; s_q[threadIdx.x] = sq; s_n[threadIdx.x] = ne;
+    __syncthreads();
+    for (uint32_t stride = RGK_NZ_BLOCK / 2; stride > 0; stride >>= 1) {
+        if (threadIdx.x < stride) {
+            s_v[threadIdx.x] += s_v[threadIdx.x + stride];
+            s_q[threadIdx.x] += s_q[threadIdx.x + stride];
+            s_n[threadIdx.x] += s_n[threadIdx.x + stride];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        rgk_noise_tile t;
+        t.sum_var = s_v[0]; t.sum_sq = s_q[0]; t.n_estimable = s_n[0];
+        tiles[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = t;
+    }
+}
+
+__global__ __launch_bounds__(RGK_NZ_BLOCK) void k_nz_prepare(size_t P, const float* __restrict__ accum_rgb, const uint32_t* __restrict__ accum_count,
+                                                              const float* __restrict__ half_rgb, const uint32_t* __restrict__ half_count,
+                                                              const float* __restrict__ albedo, const float* __restrict__ normal, const float* __restrict__ depth,
+                                                              uint32_t demodulate, float albedo_floor, float4* __restrict__ col, float4* __restrict__ guide) {
+    const size_t p = (size_t)blockIdx.x * RGK_NZ_BLOCK + threadIdx.x;
+    if (p >= P) return;
+    NzPixel px = nz_pixel(p, accum_rgb, accum_count, half_rgb, half_count);
+    if (demodulate) {
+        const float dx = demod_div(albedo[3 * p], albedo_floor), dy = demod_div(albedo[3 * p + 1], albedo_floor), dz = demod_div(albedo[3 * p + 2], albedo_floor);
+        px.c = mk3(px.c.x / dx, px.c.y / dy, px.c.z / dz);
+        px.a = mk3(px.a.x / dx, px.a.y / dy, px.a.z / dz);
+        px.b = mk3(px.b.x / dx, px.b.y / dy, px.b.z / dz);
+    }
+    col[p] = make_float4(px.c.x, px.c.y, px.c.z, px.est ? nz_variance(px.a, px.b, px.f) : 0.0f);
+    if (guide) guide[p] = make_float4(normal[3 * p], normal[3 * p + 1], normal[3 * p + 2], depth[p]);
+}
+
+// The workgroup's tile and its halo of HALO pixels, both planes, into LDS; a pixel outside the frame gets a zero normal (k_dn_atrous_lds).
+template <int HALO>
+__device__ __forceinline__ void nz_stage(int xres, int yres, const float4* __restrict__ guide, const float4* __restrict__ src, float4* s_g, float4* s_c) {
+    constexpr int TW = RGK_NZ_BX + 2 * HALO, TH = RGK_NZ_BY + 2 * HALO;
+    const int bx0 = (int)(blockIdx.x * RGK_NZ_BX) - HALO, by0 = (int)(blockIdx.y * RGK_NZ_BY) - HALO;
+    for (int k = (int)(threadIdx.y * RGK_NZ_BX + threadIdx.x); k < TH * TW; k += RGK_NZ_BX * RGK_NZ_BY) {
+        const int ty = k / TW, tx = k - ty * TW, gx = bx0 + tx, gy = by0 + ty;
+        float4 g = make_float4(0.f, 0.f, 0.f, 0.f), c = g;
+        if (gx >= 0 && gx < xres && gy >= 0 && gy < yres) {
+            const size_t q = (size_t)gy * (size_t)xres + (size_t)gx;
+            g = guide[q]; c = src[q];
+        }
+        s_g[k] = g; s_c[k] = c;
+    }
+    __syncthreads();
+}
+// wn * wz of a tap (dn_tap's two guide weights)
+__device__ __forceinline__ float nz_guide_weight(const float4 gp, const float4 gq, float sigma_depth, uint32_t npow) {
+    float wn = fmaxf(0.0f, (gp.x * gq.x + gp.y * gq.y) + gp.z * gq.z);
+    for (uint32_t k = 0; k < npow; k++) wn = wn * wn;
+    const float r = fabsf(gp.w - gq.w) / (sigma_depth * (gp.w + gq.w) + 1e-20f);
+    const float wz = 1.0f / (1.0f + r * r);
+    return wn * wz;
+}
+
+__global__ __launch_bounds__(RGK_NZ_BX * RGK_NZ_BY) void k_nz_prefilter(int xres, int yres, float sigma_depth, uint32_t npow, const float4* __restrict__ guide,
+                                                                        const float4* __restrict__ src, float4* __restrict__ dst) {
+    constexpr int HALO = 2, TW = RGK_NZ_BX + 2 * HALO, TH = RGK_NZ_BY + 2 * HALO;
+    __shared__ float4 s_g[TH * TW], s_c[TH * TW];
+    nz_stage<HALO>(xres, yres, guide, src, s_g, s_c);
+    const int x = (int)(blockIdx.x * RGK_NZ_BX + threadIdx.x), y = (int)(blockIdx.y * RGK_NZ_BY + threadIdx.y);
+    if (x >= xres || y >= yres) return;
+    const size_t p = (size_t)y * (size_t)xres + (size_t)x;
+    const int t0 = ((int)threadIdx.y + HALO) * TW + (int)threadIdx.x + HALO;
+    const float4 cp = s_c[t0], gp = s_g[t0];
+    if (dn_no_normal(gp)) { dst[p] = cp; return; }
+    float sv = 0.f, sw = 0.f;
+#pragma unroll
+    for (int dy = -2; dy <= 2; dy++) {
+#pragma unroll
+        for (int dx = -2; dx <= 2; dx++) {
+            const int t = t0 + dy * TW + dx;
+            const float4 gq = s_g[t];
+            if (dn_no_normal(gq)) continue;
+            const float w = nz_guide_weight(gp, gq, sigma_depth, npow);
+            sv = sv + w * s_c[t].w;
+            sw = sw + w;
+        }
+    }
+    dst[p] = make_float4(cp.x, cp.y, cp.z, sw > 0.0f ? sv / sw : cp.w);
+}
+
+struct NzSums {
+    float r, g, b, w, v;
+};
+__device__ __forceinline__ void nz_tap(const float4 gp, const float4 cp, const float4 gq, const float4 cq, float hh, float k2, float sigma_depth, uint32_t npow, NzSums& s) {
+    float wn = fmaxf(0.0f, (gp.x * gq.x + gp.y * gq.y) + gp.z * gq.z);
+    for (uint32_t k = 0; k < npow; k++) wn = wn * wn;
+    const float r = fabsf(gp.w - gq.w) / (sigma_depth * (gp.w + gq.w) + 1e-20f);
+    const float wz = 1.0f / (1.0f + r * r);
+    const float dr = cp.x - cq.x, dg = cp.y - cq.y, db = cp.z - cq.z;
+    const float d2 = (dr * dr + dg * dg) + db * db;
+    const float wc = 1.0f / (1.0f + d2 / (k2 * (cp.w + cq.w) + 1e-20f));
+    const float w = ((hh * wn) * wz) * wc;
+    s.r = s.r + w * cq.x; s.g = s.g + w * cq.y; s.b = s.b + w * cq.z;
+    s.w = s.w + w;
+    s.v = s.v + (w * w) * cq.w;
+}
+__device__ __forceinline__ float4 nz_result(const NzSums& s, const float4 cp) {
+    return s.w > 0.0f ? make_float4(s.r / s.w, s.g / s.w, s.b / s.w, s.v / (s.w * s.w)) : cp;
+}
+
+__global__ __launch_bounds__(RGK_NZ_BX * RGK_NZ_BY) void k_nz_atrous(int xres, int yres, int step, float k2, float sigma_depth, uint32_t npow,
+                                                                     const float4* __restrict__ guide, const float4* __restrict__ src, float4* __restrict__ dst) {
+    const int x = (int)(blockIdx.x * RGK_NZ_BX + threadIdx.x), y = (int)(blockIdx.y * RGK_NZ_BY + threadIdx.y);
+    if (x >= xres || y >= yres) return;
+    const size_t p = (size_t)y * (size_t)xres + (size_t)x;
+    const float4 cp = src[p], gp = guide[p];
+    if (dn_no_normal(gp)) { dst[p] = cp; return; }
+    const float hk[5] = {1.0f / 16.0f, 1.0f / 4.0f, 3.0f / 8.0f, 1.0f / 4.0f, 1.0f / 16.0f};
+    NzSums sum = {0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int dy = -2; dy <= 2; dy++) {
+        const int qy = y + step * dy;
+        if (qy < 0 || qy >= yres) continue;
+#pragma unroll
+        for (int dx = -2; dx <= 2; dx++) {
+            const int qx = x + step * dx;
+            if (qx < 0 || qx >= xres) continue;
+            const size_t q = (size_t)qy * (size_t)xres + (size_t)qx;
+            const float4 gq = guide[q];
+            if (dn_no_normal(gq)) continue;
+            nz_tap(gp, cp, gq, src[q], hk[dy + 2] * hk[dx + 2], k2, sigma_depth, npow, sum);
+        }
+    }
+    dst[p] = nz_result(sum, cp);
+}
+
+template <int STEP>
+__global__ __launch_bounds__(RGK_NZ_BX * RGK_NZ_BY) void k_nz_atrous_lds(int xres, int yres, float k2, float sigma_depth, uint32_t npow,
+                                                                         const float4* __restrict__ guide, const float4* __restrict__ src, float4* __restrict__ dst) {
+    constexpr int HALO = 2 * STEP, TW = RGK_NZ_BX + 2 * HALO, TH = RGK_NZ_BY + 2 * HALO;
+    __shared__ float4 s_g[TH * TW], s_c[TH * TW];
+    nz_stage<HALO>(xres, yres, guide, src, s_g, s_c);
+    const int x = (int)(blockIdx.x * RGK_NZ_BX + threadIdx.x), y = (int)(blockIdx.y * RGK_NZ_BY + threadIdx.y);
+    if (x >= xres || y >= yres) return;
+    const size_t p = (size_t)y * (size_t)xres + (size_t)x;
+    const int t0 = ((int)threadIdx.y + HALO) * TW + (int)threadIdx.x + HALO;
+    const float4 cp = s_c[t0], gp = s_g[t0];
+    if (dn_no_normal(gp)) { dst[p] = cp; return; }
+    const float hk[5] = {1.0f / 16.0f, 1.0f / 4.0f, 3.0f / 8.0f, 1.0f / 4.0f, 1.0f / 16.0f};
+    NzSums sum = {0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int dy = -2; dy <= 2; dy++) {
+#pragma unroll
+        for (int dx = -2; dx <= 2; dx++) {
+            const int t = t0 + STEP * dy * TW + STEP * dx;
+            const float4 gq = s_g[t];
+            if (dn_no_normal(gq)) continue;
+            nz_tap(gp, cp, gq, s_c[t], hk[dy + 2] * hk[dx + 2], k2, sigma_depth, npow, sum);
+        }
+    }
+    dst[p] = nz_result(sum, cp);
+}
+
+__global__ __launch_bounds__(RGK_NZ_BLOCK) void k_nz_finish(size_t P, const float4* __restrict__ col, float* __restrict__ out_variance) {
+    const size_t p = (size_t)blockIdx.x * RGK_NZ_BLOCK + threadIdx.x;
+    if (p >= P) return;
+    out_variance[p] = col[p].w;
+}
+
+void rgk_launch_nz_tile_sums(hipStream_t st, uint32_t xres, uint32_t yres, uint32_t tile_size, const float* accum_rgb, const uint32_t* accum_count,
+                             const float* half_rgb, const uint32_t* half_count, rgk_noise_tile* tiles, float* variance) {
+    const RgkGrid2 g = rgk_nz_tile_grid(xres, yres, tile_size);
+    k_nz_tile_sums<<<dim3(g.x, g.y), RGK_NZ_BLOCK, 0, st>>>(xres, yres, tile_size, accum_rgb, accum_count, half_rgb, half_count, tiles, variance);
+}
+void rgk_launch_nz_prepare(hipStream_t st, size_t P, const float* accum_rgb, const uint32_t* accum_count, const float* half_rgb, const uint32_t* half_count,
+                           const float* albedo, const float* normal, const float* depth, uint32_t demodulate, float albedo_floor, float4* col, float4* guide) {
+    k_nz_prepare<<<rgk_nz_pixel_grid(P), RGK_NZ_BLOCK, 0, st>>>(P, accum_rgb, accum_count, half_rgb, half_count, albedo, normal, depth, demodulate, albedo_floor, col, guide);
+}
+void rgk_launch_nz_prefilter(hipStream_t st, uint32_t xres, uint32_t yres, float sigma_depth, uint32_t npow, const float4* guide, const float4* src, float4* dst) {
+    const RgkGrid2 g = rgk_nz_filter_grid(xres, yres);
+    k_nz_prefilter<<<dim3(g.x, g.y), dim3(RGK_NZ_BX, RGK_NZ_BY), 0, st>>>((int)xres, (int)yres, sigma_depth, npow, guide, src, dst);
+}
+void rgk_launch_nz_atrous(hipStream_t st, uint32_t xres, uint32_t yres, uint32_t step, float k2, float sigma_depth, uint32_t npow, const float4* guide,
+                          const float4* src, float4* dst) {
+    const RgkGrid2 g = rgk_nz_filter_grid(xres, yres);
+    const dim3 grid(g.x, g.y), block(RGK_NZ_BX, RGK_NZ_BY);
+    // the LDS form for steps 1 and 2, gathers above, as rgk_launch_dn_atrous
+    if (step == 1) { k_nz_atrous_lds<1><<<grid, block, 0, st>>>((int)xres, (int)yres, k2, sigma_depth, npow, guide, src, dst); return; }
+    if (step == 2) { k_nz_atrous_lds<2><<<grid, block, 0, st>>>((int)xres, (int)yres, k2, sigma_depth, npow, guide, src, dst); return; }
+    k_nz_atrous<<<grid, block, 0, st>>>((int)xres, (int)yres, (int)step, k2, sigma_depth, npow, guide, src, dst);
+}
+void rgk_launch_nz_finish(hipStream_t st, size_t P, const float4* col, float* out_variance) {
+    k_nz_finish<<<rgk_nz_pixel_grid(P), RGK_NZ_BLOCK, 0, st>>>(P, col, out_variance);
 }

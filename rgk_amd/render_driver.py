@@ -143,8 +143,25 @@ class Scene:
         capi.check(self.lib, self.lib.rgk_denoise_device(self.h, xres, yres, d_accum_rgb, d_accum_count, d_albedo, d_normal, d_depth,
                                                          C.byref(params), d_out_rgb))
 
+    def noise_estimate_device(self, xres, yres, tile_size, d_accum_rgb, d_accum_count, d_half_rgb, d_half_count, d_variance=None):
+        """rgk_noise_estimate_device: DEVICE pointers (ints) on the scene's GPU -> a (tiles_y, tiles_x) structured array with the
+        fields sum_var, sum_sq (float64) and n_estimable (uint64)."""
+        ty, tx = -(-yres // tile_size), -(-xres // tile_size)
+        tiles = (capi.NoiseTile * (ty * tx))()
+        capi.check(self.lib, self.lib.rgk_noise_estimate_device(self.h, xres, yres, tile_size, d_accum_rgb, d_accum_count, d_half_rgb, d_half_count,
+                                                                tiles, d_variance))
+        dt = np.dtype([("sum_var", "f8"), ("sum_sq", "f8"), ("n_estimable", "u8")])
+        return np.frombuffer(tiles, dtype=dt).reshape(ty, tx).copy()
+
+    def denoise_variance_device(self, xres, yres, d_accum_rgb, d_accum_count, d_half_rgb, d_half_count, d_albedo, d_normal, d_depth, params,
+                                d_out_rgb, d_out_variance=None):
+        """rgk_denoise_variance_device: the variance-guided a-trous filter of a whole frame, DEVICE pointers (ints)."""
+        capi.check(self.lib, self.lib.rgk_denoise_variance_device(self.h, xres, yres, d_accum_rgb, d_accum_count, d_half_rgb, d_half_count, d_albedo,
+                                                                  d_normal, d_depth, C.byref(params), d_out_rgb, d_out_variance))
+
     def post_timing(self, which):
-        """HIP-event times (ms) of the launches of the last feature pass (0) / denoise call (1); set_tuning(time_post=1) first."""
+        """HIP-event times (ms) of the launches of the last feature pass (0) / denoise call (1) / variance-guided denoise call (2) /
+        noise estimate (3); set_tuning(time_post=1) first."""
         ms, n = (C.c_double * 32)(), C.c_uint32(32)
         capi.check(self.lib, self.lib.rgk_scene_get_post_timing(self.h, which, ms, C.byref(n)))
         return list(ms[:min(n.value, 32)])
@@ -238,11 +255,16 @@ class EXRTexture:
         return val.value
 
 
+def missing_half_message(path):
+    return (f"`{path}` has no half-buffer `{path}.half` beside it: it was written without noise tracking, and the noise estimate "
+            "cannot be continued from it (render without --noise, or start the frame again)")
+
+
 class RenderDriver:
     """RenderDriver::RenderFrame / RenderRound for one process per GPU."""
 
     def __init__(self, scene, cfg, camera, rank=0, world_size=1, device=None, sampler=capi.SAMPLER_HALTON, flags=0,
-                 host_reduce=False):
+                 host_reduce=False, track_noise=False):
         import torch
         self.scene, self.cfg, self.camera = scene, cfg, camera
         self.rank, self.world_size = rank, world_size
@@ -259,6 +281,13 @@ class RenderDriver:
         self.clock = time.time
         self.checkpoint_tag = 0  # digest of scene + camera + parameters (rgk_accum_set_tag); 0: checkpoints are not compared
         self.aov = None  # the frame's feature planes once render_aov() has made them
+        # track_noise: rank 0 keeps a second accumulator, the sum of the ODD rounds (the second, fourth, ...), for the half-buffer
+        # noise estimate.  A single-rank driver then renders every round into the cleared per-round accumulator (the one a
+        # multi-rank driver has anyway) and adds it to total_ob itself: when a round is one pass -- one addition per pixel --
+        # total_ob has the bits it has without tracking (0 + s == s); a round of several passes adds its passes to 0 first
+        # instead of to the running total, which may differ in the last place.  Off: every code path is the untracked one.
+        self.track_noise = bool(track_noise)
+        self.half_ob = EXRTexture(cfg.xres, cfg.yres, self.device) if self.track_noise and rank == 0 else None
 
     def render_round(self, reduce=True):
         """One RenderRound: every rank renders its tiles into its private accumulator, then ONE sum-reduce of the RGB
@@ -268,7 +297,20 @@ class RenderDriver:
         import torch
         tiles = generate_task_list(self.cfg.xres, self.cfg.yres, SEEDSTART, self.seedcount)
         self.seedcount += len(tiles)  # `c = seedcount++` per task, render_driver.cpp:160
-        if self.world_size == 1:
+        odd = self.rounds_done % 2 == 1
+        if self.world_size == 1 and self.track_noise:
+            if self.round_ob is None:
+                self.round_ob = EXRTexture(self.cfg.xres, self.cfg.yres, self.device)
+            else:
+                self.round_ob.data.zero_()
+                self.round_ob.count.zero_()
+            ob = self.round_ob
+            torch.cuda.current_stream(self.device).synchronize()
+            cnt = self.scene.render_round_device(self.camera, self.params, tiles, ob.data.data_ptr(), ob.count.data_ptr())
+            for dst in (self.total_ob, self.half_ob) if odd else (self.total_ob,):
+                dst.data += ob.data
+                dst.count += ob.count
+        elif self.world_size == 1:
             torch.cuda.current_stream(self.device).synchronize()
             cnt = self.scene.render_round_device(self.camera, self.params, tiles, self.total_ob.data.data_ptr(), self.total_ob.count.data_ptr())
         else:
@@ -287,13 +329,18 @@ class RenderDriver:
                     hd = ob.data.cpu()
                     dist.reduce(hd, dst=0, op=dist.ReduceOp.SUM)
                     if self.rank == 0:
-                        self.total_ob.data += hd.to(self.total_ob.data.device)
+                        red = hd.to(self.total_ob.data.device)
+                        self.total_ob.data += red
                 else:
                     dist.reduce(ob.data, dst=0, op=dist.ReduceOp.SUM)
                     if self.rank == 0:
-                        self.total_ob.data += ob.data
+                        red = ob.data
+                        self.total_ob.data += red
                 if self.rank == 0:
                     self.total_ob.count += int(self.params.multisample)
+                    if self.track_noise and odd:
+                        self.half_ob.data += red
+                        self.half_ob.count += int(self.params.multisample)
         self.rounds_done += 1
         self.counters.append(cnt)
         return cnt
@@ -323,12 +370,56 @@ class RenderDriver:
         level = float(self.total_ob.get_pixels().max(dim=-1).values.double().mean())
         return capi.DenoiseParams(sigma_color=DENOISE_SIGMA_K * level if level > 0 else 1.0)
 
-    def denoise(self, params=None):
-        """The current accumulator's image (data / count, not normalised) through the guided a-trous filter
-        (rgk_denoise_device): a (y, x, 3) float32 torch tensor on the device.  The accumulator is not changed.  Root rank only."""
+    def noise(self, tile_size=TILE_SIZE):
+        """The half-buffer noise estimate of the current accumulator (rgk_noise_estimate_device): {"rel": the frame's relative
+        noise sqrt(sum of v / sum of |c|^2), an estimate of rel-L2 against the converged image; "tiles": (tiles_y, tiles_x)
+        structured array sum_var / sum_sq / n_estimable; "variance": (y, x) float32 tensor, the raw per-pixel v}.
+        None before two rounds, without track_noise, and on ranks other than the root."""
+        import torch
+        if self.rank != 0 or not self.track_noise or self.rounds_done < 2:
+            return None
+        var = torch.empty((self.cfg.yres, self.cfg.xres), dtype=torch.float32, device=self.device)
+        torch.cuda.current_stream(self.device).synchronize()
+        tiles = self.scene.noise_estimate_device(self.cfg.xres, self.cfg.yres, tile_size, self.total_ob.data.data_ptr(), self.total_ob.count.data_ptr(),
+                                                 self.half_ob.data.data_ptr(), self.half_ob.count.data_ptr(), var.data_ptr())
+        sv = sq = 0.0
+        for t in tiles.reshape(-1):  # row-major, in double
+            sv += float(t["sum_var"])
+            sq += float(t["sum_sq"])
+        return {"rel": (sv / sq) ** 0.5 if sq > 0 else 0.0, "tiles": tiles, "variance": var}
+
+    def denoise_variance(self, params=None):
+        """The variance-guided filter (rgk_denoise_variance_device) of the current accumulator and its half-buffer:
+        (image (y, x, 3), variance of the filtered image (y, x)), float32 tensors on the device.  Needs track_noise and two rounds."""
         import torch
         if self.rank != 0:
             return None
+        if not self.track_noise or self.rounds_done < 2:
+            raise ValueError("the variance-guided filter needs track_noise=True and two rounds")
+        a = self.render_aov()
+        params = params or capi.DenoiseVarParams()
+        out = torch.empty_like(self.total_ob.data)
+        var = torch.empty((self.cfg.yres, self.cfg.xres), dtype=torch.float32, device=self.device)
+        torch.cuda.current_stream(self.device).synchronize()
+        self.scene.denoise_variance_device(self.cfg.xres, self.cfg.yres, self.total_ob.data.data_ptr(), self.total_ob.count.data_ptr(),
+                                           self.half_ob.data.data_ptr(), self.half_ob.count.data_ptr(), a["albedo"].data_ptr(), a["normal"].data_ptr(),
+                                           a["depth"].data_ptr(), params, out.data_ptr(), var.data_ptr())
+        return out, var
+
+    def denoise(self, params=None, variance=False):
+        """The current accumulator's image (data / count, not normalised) through the guided a-trous filter
+        (rgk_denoise_device): a (y, x, 3) float32 torch tensor on the device.  The accumulator is not changed.  Root rank only.
+        variance=True (needs track_noise): the variance-guided filter instead, `params` then a capi.DenoiseVarParams; while fewer
+        than two rounds are done there is no estimate yet and the fixed filter with its defaults runs."""
+        import torch
+        if self.rank != 0:
+            return None
+        if variance:
+            if not self.track_noise:
+                raise ValueError("denoise(variance=True) needs track_noise=True")
+            if self.rounds_done >= 2:
+                return self.denoise_variance(params)[0]
+            params = None
         a = self.render_aov()
         params = params or self.default_denoise_params()
         out = torch.empty_like(self.total_ob.data)
@@ -338,13 +429,19 @@ class RenderDriver:
         return out
 
     def save_checkpoint(self, path):
-        """Raw-accumulator checkpoint (rgk_accum_save): accumulator + rounds done + the running task counter."""
+        """Raw-accumulator checkpoint (rgk_accum_save): accumulator + rounds done + the running task counter.  With track_noise the
+        half-buffer goes beside it as `<path>.half`, same format, same tag."""
+        self._save_ob(self.total_ob, path)
+        if self.track_noise:
+            self._save_ob(self.half_ob, str(path) + ".half")
+
+    def _save_ob(self, ob, path):
         lib = capi.load_product()
         acc = C.c_void_p()
         capi.check(lib, lib.rgk_accum_create(self.cfg.xres, self.cfg.yres, self.scene.device, C.byref(acc)))
         try:
-            a = np.ascontiguousarray(self.total_ob.data.cpu().numpy(), dtype=np.float32)
-            c = np.ascontiguousarray(self.total_ob.count.cpu().numpy()).view(np.uint32)
+            a = np.ascontiguousarray(ob.data.cpu().numpy(), dtype=np.float32)
+            c = np.ascontiguousarray(ob.count.cpu().numpy()).view(np.uint32)
             capi.check(lib, lib.rgk_accum_upload(acc, a.ctypes.data, c.ctypes.data))
             capi.check(lib, lib.rgk_accum_set_tag(acc, self.checkpoint_tag))
             capi.check(lib, lib.rgk_accum_save(acc, str(path).encode(), self.rounds_done, self.seedcount))
@@ -352,7 +449,19 @@ class RenderDriver:
             lib.rgk_accum_destroy(acc)
 
     def load_checkpoint(self, path):
-        """Resume: the next render_round continues the seed sequence where the saved run stopped."""
+        """Resume: the next render_round continues the seed sequence where the saved run stopped.  With track_noise the
+        half-buffer `<path>.half` must be there: without it S != S_A + S_B and the estimate would be silently wrong."""
+        import os
+        half = str(path) + ".half"
+        if self.track_noise and not os.path.exists(half):
+            raise RuntimeError(missing_half_message(path))
+        rounds_done, seedcount = self._load_ob(self.total_ob, path)
+        if self.track_noise:
+            if self._load_ob(self.half_ob, half) != (rounds_done, seedcount):
+                raise RuntimeError(f"`{half}` was not written together with `{path}`")
+        self.rounds_done, self.seedcount = rounds_done, seedcount
+
+    def _load_ob(self, ob, path):
         import torch
         lib = capi.load_product()
         acc = C.c_void_p()
@@ -366,9 +475,21 @@ class RenderDriver:
             capi.check(lib, lib.rgk_accum_download(acc, a.ctypes.data, c.ctypes.data))
         finally:
             lib.rgk_accum_destroy(acc)
-        self.total_ob.data.copy_(torch.from_numpy(a))
-        self.total_ob.count.copy_(torch.from_numpy(c.view(np.int32)))
-        self.rounds_done, self.seedcount = rd_.value, sc_.value
+        ob.data.copy_(torch.from_numpy(a))
+        ob.count.copy_(torch.from_numpy(c.view(np.int32)))
+        return rd_.value, sc_.value
+
+    def _noise_reached(self, until_noise, nz):
+        """After a round: has the frame's relative noise (nz: rank 0's noise()) come down to `until_noise`?  Rank 0's decision,
+        broadcast as in _continue_timed."""
+        stop = nz is not None and nz["rel"] <= until_noise
+        if self.world_size > 1:
+            import torch
+            import torch.distributed as dist
+            flag = torch.tensor([1 if stop else 0], dtype=torch.int32, device="cpu" if self.host_reduce else self.device)
+            dist.broadcast(flag, src=0)
+            stop = bool(flag.item())
+        return stop
 
     def _continue_timed(self, t0, minutes):
         go = (self.clock() - t0) / 60.0 < minutes
@@ -380,11 +501,18 @@ class RenderDriver:
             go = bool(flag.item())
         return go
 
-    def render_frame(self, rounds=None, minutes=None, output_file=None, checkpoint=None, aov_files=None, denoised_file=None):
+    def render_frame(self, rounds=None, minutes=None, output_file=None, checkpoint=None, aov_files=None, denoised_file=None,
+                     until_noise=None, noise_file=None, on_noise=None):
         """RenderFrame: Rounds mode (render_driver.cpp:229-235) or Timed mode (:237-247); with `output_file` the
         normalised image is rewritten after every round, as the reference does (rank 0 only).
         aov_files: {"albedo" / "normal" / "depth": path} -- the feature planes, written once (depth replicated to R, G, B).
-        denoised_file: rewritten after every round that rewrites output_file, normalised with the scale output_file got."""
+        denoised_file: rewritten after every round that rewrites output_file, normalised with the scale output_file got.
+        With track_noise -- until_noise: stop once noise()["rel"] <= until_noise, checked after every round from the second on
+        (`rounds` / `minutes` still bound the frame); from the second round on denoised_file comes from the variance-guided
+        filter, and noise_file holds sqrt of that filter's output variance in R, G and B, scaled like output_file;
+        on_noise(rounds_done, rel) is called on rank 0 after every round that has an estimate."""
+        if (until_noise is not None or noise_file or on_noise) and not self.track_noise:
+            raise ValueError("until_noise, noise_file and on_noise need track_noise=True")
         rounds = self.cfg.render_rounds if rounds is None else rounds
         minutes = self.cfg.render_minutes if minutes is None else minutes
         t0 = self.clock()
@@ -398,16 +526,28 @@ class RenderDriver:
             self.render_round()
             if output_file and self.rank == 0:
                 val = self.total_ob.write(output_file, getattr(self.cfg, "output_scale", -1.0))
-                if denoised_file:
+                if self.track_noise and self.rounds_done >= 2 and (denoised_file or noise_file):
+                    den, var = self.denoise_variance()
+                    if denoised_file:
+                        write_exr(denoised_file, (den * val).cpu().numpy())
+                    if noise_file:
+                        write_exr(noise_file, (var.sqrt() * val).unsqueeze(-1).expand(-1, -1, 3).cpu().numpy())
+                elif denoised_file:
                     write_exr(denoised_file, (self.denoise() * val).cpu().numpy())
             if checkpoint and self.rank == 0:
                 self.save_checkpoint(checkpoint)
+            nz = self.noise() if on_noise or until_noise is not None else None
+            if on_noise and nz is not None:
+                on_noise(self.rounds_done, nz["rel"])
+            return until_noise is not None and self._noise_reached(until_noise, nz)
         if minutes is None:
             for _ in range(rounds):
-                one()
+                if one():
+                    break
         else:
             # Timed mode (render_driver.cpp:237-247).  With several ranks the decision to start another round is rank 0's,
             # broadcast to all: ranks reading their own clocks could disagree and leave a reduce unmatched.
             while self._continue_timed(t0, minutes):
-                one()
+                if one():
+                    break
         return self.total_ob
