@@ -93,6 +93,8 @@ struct RgkTuning {
     bool time_post = false;   // feature pass / denoiser: HIP events around their launches (rgk_scene_get_post_timing)
 };
 
+// rgk_scene_get_post_timing's `which` (rgk.h): the post-processing call whose launch times a slot holds
+enum PostSlot : uint32_t { POST_AOV = 0, POST_DENOISE = 1, POST_DENOISE_VARIANCE = 2, POST_NOISE = 3, POST_SLOTS = 4 };
 constexpr uint32_t RGK_SCENE_MAGIC = 0x53474b52u; // "RKGS": what a live scene handle starts with (rgk_scene_get_post_timing)
 struct rgk_scene {
     uint32_t magic = RGK_SCENE_MAGIC;
@@ -154,7 +156,7 @@ struct rgk_scene {
     DevBuf<uint32_t> scratch_u;
     DevBuf<float4> dn_col[2], dn_guide; // the denoiser's two colour planes and its guide plane {n.xyz, z}
     DevBuf<rgk_noise_tile> nz_tiles;    // the noise estimate's per-tile sums
-    std::vector<double> post_ms[4];     // launch times of the last feature pass [0] / denoise call [1] / variance-guided denoise call [2] / noise estimate [3] (tuning "time_post")
+    std::vector<double> post_ms[POST_SLOTS]; // launch times of the last call of each kind (tuning "time_post")
     std::vector<hipEvent_t> events;
     uint32_t* h_counters = nullptr; // pinned
     // progress, read by rgk_scene_get_progress from any thread
@@ -1169,6 +1171,59 @@ int check_aov_args(const rgk_scene* s, const rgk_camera* camera, const rgk_param
     if (prm->xres == 0 || prm->yres == 0 || prm->xres > 65535 || prm->yres > 65535) return fail(RGK_ERR_INVALID, "resolution out of range");
     return tile_offsets(prm, tiles, n_tiles, "feature pass", toff);
 }
+// What both denoise entries check besides their own parameter ranges, without touching the scene.  The fixed-sigma filter has no
+// half-buffer and no variance plane (NULL here); `p`: its parameters too, with albedo_floor 0 (sigma_k belongs to the entry).
+int check_denoise_args(const rgk_scene* s, uint32_t xres, uint32_t yres, const float* accum_rgb, const uint32_t* accum_count, const float* half_rgb,
+                       const uint32_t* half_count, const float* albedo, const float* normal, const float* depth, const rgk_denoise_var_params& p,
+                       const float* out_rgb, const float* out_variance) {
+    if (!s || !accum_rgb || !accum_count || !normal || !depth || !out_rgb) return fail(RGK_ERR_INVALID, "null argument");
+    if (p.demodulate && !albedo) return fail(RGK_ERR_INVALID, "demodulate without an albedo plane");
+    if (xres == 0 || yres == 0 || xres > 65535 || yres > 65535) return fail(RGK_ERR_INVALID, "resolution out of range");
+    if (p.iterations > 16 || p.normal_power_log2 > 16) return fail(RGK_ERR_INVALID, "iterations and normal_power_log2 must be <= 16");
+    const void* ins[] = {accum_rgb, accum_count, half_rgb, half_count, albedo, normal, depth};
+    for (const void* in : ins)
+        if (in && (in == out_rgb || in == out_variance)) return fail(RGK_ERR_INVALID, "an output plane must not be one of the inputs");
+    if (out_rgb == out_variance) return fail(RGK_ERR_INVALID, "out_rgb and out_variance must differ");
+    return RGK_OK;
+}
+// A whole denoise call once the entry's own checks have passed: the shared ones, then prepare -> [prefilter] -> iterations -> finish ->
+// [variance copy] on the scene's stream, waited for.  `wc[i]`: iteration i's colour-weight constant (sigma_i^2 / sigma_k^2).
+int denoise(rgk_scene* s, const char* entry, PostSlot slot, uint32_t xres, uint32_t yres, const float* accum_rgb, const uint32_t* accum_count, const float* half_rgb,
+            const uint32_t* half_count, const float* albedo, const float* normal, const float* depth, const rgk_denoise_var_params& p, const float* wc,
+            float* out_rgb, float* out_variance) {
+    int rc;
+    if ((rc = check_denoise_args(s, xres, yres, accum_rgb, accum_count, half_rgb, half_count, albedo, normal, depth, p, out_rgb, out_variance))) return rc;
+    if (s->prog_busy.load()) return fail(RGK_ERR_INVALID, "%s while a round is in flight on this scene", entry);
+    HIPCHK(hipSetDevice(s->device));
+    const size_t P = (size_t)xres * yres;
+    const uint32_t it = p.iterations, demod = (it && p.demodulate) ? 1u : 0u; // no iteration: out = c, variance = v, nothing to demodulate for
+    const RgkDnMode mode = half_rgb ? RGK_DN_VARIANCE_GUIDED : RGK_DN_FIXED_SIGMA;
+    if ((rc = s->dn_col[0].alloc(P)) || (it && ((rc = s->dn_col[1].alloc(P)) || (rc = s->dn_guide.alloc(P))))) return rc;
+    hipStream_t st = s->stream;
+    PostTimer tm(s);
+    s->post_ms[slot].clear();
+    uint32_t cur = 0; // the plane that holds the current image
+    const auto filter = [&](RgkDnMode m, uint32_t step, float c) {
+        rgk_launch_dn_atrous(st, m, xres, yres, step, c, p.sigma_depth, p.normal_power_log2, s->dn_guide.p, s->dn_col[cur].p, s->dn_col[cur ^ 1u].p);
+        cur ^= 1u;
+        return tm.mark();
+    };
+    if ((rc = tm.mark())) return rc;
+    rgk_launch_dn_prepare(st, P, accum_rgb, accum_count, half_rgb, half_count, albedo, normal, depth, demod, p.albedo_floor, s->dn_col[0].p, it ? s->dn_guide.p : nullptr);
+    if ((rc = tm.mark())) return rc;
+    if (it && mode == RGK_DN_VARIANCE_GUIDED && (rc = filter(RGK_DN_VARIANCE_MEAN, 1u, 0.0f))) return rc;
+    for (uint32_t i = 0; i < it; i++)
+        if ((rc = filter(mode, 1u << i, wc[i]))) return rc;
+    rgk_launch_dn_finish(st, P, s->dn_col[cur].p, albedo, demod, p.albedo_floor, out_rgb);
+    if ((rc = tm.mark())) return rc;
+    if (out_variance) {
+        rgk_launch_nz_finish(st, P, s->dn_col[cur].p, out_variance);
+        if ((rc = tm.mark())) return rc;
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    return tm.fold(s->post_ms[slot]);
+}
 } // namespace
 
 extern "C" {
@@ -1180,7 +1235,7 @@ int rgk_render_aov_device(rgk_scene* s, const rgk_camera* camera, const rgk_para
     if ((rc = check_aov_args(s, camera, prm, tiles, n_tiles, toff))) return rc;
     if (s->prog_busy.load()) return fail(RGK_ERR_INVALID, "rgk_render_aov_device while a round is in flight on this scene");
     const uint32_t n = toff[n_tiles];
-    s->post_ms[0].clear();
+    s->post_ms[POST_AOV].clear();
     if (n == 0) return RGK_OK;
     HIPCHK(hipSetDevice(s->device));
     // The round's own buffers: its pixel list (rebuilt by every round before it is read), two ray planes and the hit plane of
@@ -1202,7 +1257,7 @@ int rgk_render_aov_device(rgk_scene* s, const rgk_camera* camera, const rgk_para
     if ((rc = tm.mark())) return rc;
     HIPCHK(hipStreamSynchronize(st));
     HIPCHK(hipGetLastError());
-    return tm.fold(s->post_ms[0]);
+    return tm.fold(s->post_ms[POST_AOV]);
 }
 
 int rgk_render_aov(rgk_scene* s, const rgk_camera* camera, const rgk_params* prm, const rgk_tile* tiles, uint32_t n_tiles, float* albedo, float* normal,
@@ -1224,40 +1279,16 @@ int rgk_render_aov(rgk_scene* s, const rgk_camera* camera, const rgk_params* prm
 
 int rgk_denoise_device(rgk_scene* s, uint32_t xres, uint32_t yres, const float* d_accum_rgb, const uint32_t* d_accum_count, const float* d_albedo,
                        const float* d_normal, const float* d_depth, const rgk_denoise_params* dp, float* d_out_rgb) {
-    // (every check before the scene or the device is touched)
-    if (!s || !d_accum_rgb || !d_accum_count || !d_normal || !d_depth || !dp || !d_out_rgb) return fail(RGK_ERR_INVALID, "null argument");
-    if (dp->demodulate && !d_albedo) return fail(RGK_ERR_INVALID, "demodulate without an albedo plane");
-    if (xres == 0 || yres == 0 || xres > 65535 || yres > 65535) return fail(RGK_ERR_INVALID, "resolution out of range");
-    if (dp->iterations > 16 || dp->normal_power_log2 > 16) return fail(RGK_ERR_INVALID, "iterations and normal_power_log2 must be <= 16");
+    if (!dp) return fail(RGK_ERR_INVALID, "null argument");
     if (!(dp->sigma_color > 0.0f) || !(dp->sigma_depth >= 0.0f) || std::isinf(dp->sigma_color) || std::isinf(dp->sigma_depth)) return fail(RGK_ERR_INVALID, "sigma_color must be > 0 and sigma_depth >= 0, both finite");
-    if (d_out_rgb == d_accum_rgb || d_out_rgb == d_albedo || d_out_rgb == d_normal) return fail(RGK_ERR_INVALID, "out_rgb must not be one of the inputs");
     float sigma2[16];
-    for (uint32_t i = 0; i < dp->iterations; i++) {
+    for (uint32_t i = 0; i < dp->iterations && i < 16; i++) { // (iterations <= 16 is checked with what both entries share)
         const float si = dp->sigma_color * std::ldexp(1.0f, -(int)i); // sigma_color * 2^-i
         sigma2[i] = si * si;
         if (!(sigma2[i] > 0.0f) || std::isinf(sigma2[i])) return fail(RGK_ERR_INVALID, "sigma_color^2 leaves the float range at iteration %u", i);
     }
-    if (s->prog_busy.load()) return fail(RGK_ERR_INVALID, "rgk_denoise_device while a round is in flight on this scene");
-    HIPCHK(hipSetDevice(s->device));
-    const size_t P = (size_t)xres * yres;
-    const uint32_t it = dp->iterations, demod = (it && dp->demodulate) ? 1u : 0u; // no iteration: out = c, nothing to demodulate for
-    int rc;
-    if ((rc = s->dn_col[0].alloc(P)) || (it && ((rc = s->dn_col[1].alloc(P)) || (rc = s->dn_guide.alloc(P))))) return rc;
-    hipStream_t st = s->stream;
-    PostTimer tm(s);
-    s->post_ms[1].clear();
-    if ((rc = tm.mark())) return rc;
-    rgk_launch_dn_prepare(st, P, d_accum_rgb, d_accum_count, d_albedo, d_normal, d_depth, demod, s->dn_col[0].p, it ? s->dn_guide.p : nullptr);
-    if ((rc = tm.mark())) return rc;
-    for (uint32_t i = 0; i < it; i++) {
-        rgk_launch_dn_atrous(st, xres, yres, 1u << i, sigma2[i], dp->sigma_depth, dp->normal_power_log2, s->dn_guide.p, s->dn_col[i & 1].p, s->dn_col[(i & 1) ^ 1].p);
-        if ((rc = tm.mark())) return rc;
-    }
-    rgk_launch_dn_finish(st, P, s->dn_col[it & 1].p, d_albedo, demod, 0.0f, d_out_rgb);
-    if ((rc = tm.mark())) return rc;
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipGetLastError());
-    return tm.fold(s->post_ms[1]);
+    const rgk_denoise_var_params p = {dp->iterations, 0.0f, dp->sigma_depth, dp->normal_power_log2, dp->demodulate, 0.0f};
+    return denoise(s, "rgk_denoise_device", POST_DENOISE, xres, yres, d_accum_rgb, d_accum_count, nullptr, nullptr, d_albedo, d_normal, d_depth, p, sigma2, d_out_rgb, nullptr);
 }
 
 int rgk_noise_estimate_device(rgk_scene* s, uint32_t xres, uint32_t yres, uint32_t tile_size, const float* d_accum_rgb, const uint32_t* d_accum_count,
@@ -1276,69 +1307,32 @@ int rgk_noise_estimate_device(rgk_scene* s, uint32_t xres, uint32_t yres, uint32
     if ((rc = s->nz_tiles.alloc(g.count()))) return rc;
     hipStream_t st = s->stream;
     PostTimer tm(s);
-    s->post_ms[3].clear();
+    s->post_ms[POST_NOISE].clear();
     if ((rc = tm.mark())) return rc;
     rgk_launch_nz_tile_sums(st, xres, yres, tile_size, d_accum_rgb, d_accum_count, d_half_rgb, d_half_count, s->nz_tiles.p, d_variance);
     if ((rc = tm.mark())) return rc;
     HIPCHK(hipStreamSynchronize(st));
     HIPCHK(hipGetLastError());
     if ((rc = down(tiles, s->nz_tiles, g.count()))) return rc;
-    return tm.fold(s->post_ms[3]);
+    return tm.fold(s->post_ms[POST_NOISE]);
 }
 
 int rgk_denoise_variance_device(rgk_scene* s, uint32_t xres, uint32_t yres, const float* d_accum_rgb, const uint32_t* d_accum_count, const float* d_half_rgb,
                                 const uint32_t* d_half_count, const float* d_albedo, const float* d_normal, const float* d_depth,
                                 const rgk_denoise_var_params* dp, float* d_out_rgb, float* d_out_variance) {
-    // (every check before the scene or the device is touched)
-    if (!s || !d_accum_rgb || !d_accum_count || !d_half_rgb || !d_half_count || !d_normal || !d_depth || !dp || !d_out_rgb) return fail(RGK_ERR_INVALID, "null argument");
-    if (dp->demodulate && !d_albedo) return fail(RGK_ERR_INVALID, "demodulate without an albedo plane");
-    if (xres == 0 || yres == 0 || xres > 65535 || yres > 65535) return fail(RGK_ERR_INVALID, "resolution out of range");
-    if (dp->iterations > 16 || dp->normal_power_log2 > 16) return fail(RGK_ERR_INVALID, "iterations and normal_power_log2 must be <= 16");
+    if (!dp || !d_half_rgb || !d_half_count) return fail(RGK_ERR_INVALID, "null argument");
     if (!(dp->sigma_k > 0.0f) || !(dp->sigma_depth >= 0.0f) || !(dp->albedo_floor >= 0.0f) || std::isinf(dp->sigma_k) || std::isinf(dp->sigma_depth) || std::isinf(dp->albedo_floor))
         return fail(RGK_ERR_INVALID, "sigma_k must be > 0, sigma_depth and albedo_floor >= 0, all finite");
-    const float k2 = dp->sigma_k * dp->sigma_k;
-    if (!(k2 > 0.0f) || std::isinf(k2)) return fail(RGK_ERR_INVALID, "sigma_k^2 leaves the float range");
+    float k2[16];
+    std::fill(k2, k2 + 16, dp->sigma_k * dp->sigma_k);
+    if (!(k2[0] > 0.0f) || std::isinf(k2[0])) return fail(RGK_ERR_INVALID, "sigma_k^2 leaves the float range");
     if (d_half_rgb == d_accum_rgb || d_half_count == d_accum_count) return fail(RGK_ERR_INVALID, "the half-buffer must not be the accumulator");
-    const void* ins[] = {d_accum_rgb, d_accum_count, d_half_rgb, d_half_count, d_albedo, d_normal, d_depth};
-    for (const void* in : ins)
-        if (in && (in == (const void*)d_out_rgb || in == (const void*)d_out_variance)) return fail(RGK_ERR_INVALID, "out_rgb and out_variance must not be one of the inputs");
-    if ((const void*)d_out_rgb == (const void*)d_out_variance) return fail(RGK_ERR_INVALID, "out_rgb and out_variance must differ");
-    if (s->prog_busy.load()) return fail(RGK_ERR_INVALID, "rgk_denoise_variance_device while a round is in flight on this scene");
-    HIPCHK(hipSetDevice(s->device));
-    const size_t P = (size_t)xres * yres;
-    const uint32_t it = dp->iterations, demod = (it && dp->demodulate) ? 1u : 0u; // no iteration: out = c, variance = v, nothing to demodulate for
-    int rc;
-    if ((rc = s->dn_col[0].alloc(P)) || (it && ((rc = s->dn_col[1].alloc(P)) || (rc = s->dn_guide.alloc(P))))) return rc;
-    hipStream_t st = s->stream;
-    PostTimer tm(s);
-    s->post_ms[2].clear();
-    if ((rc = tm.mark())) return rc;
-    rgk_launch_nz_prepare(st, P, d_accum_rgb, d_accum_count, d_half_rgb, d_half_count, d_albedo, d_normal, d_depth, demod, dp->albedo_floor, s->dn_col[0].p,
-                          it ? s->dn_guide.p : nullptr);
-    if ((rc = tm.mark())) return rc;
-    uint32_t cur = 0; // the plane that holds the current image
-    if (it) {
-        rgk_launch_nz_prefilter(st, xres, yres, dp->sigma_depth, dp->normal_power_log2, s->dn_guide.p, s->dn_col[0].p, s->dn_col[1].p);
-        cur = 1;
-        if ((rc = tm.mark())) return rc;
-    }
-    for (uint32_t i = 0; i < it; i++, cur ^= 1u) {
-        rgk_launch_nz_atrous(st, xres, yres, 1u << i, k2, dp->sigma_depth, dp->normal_power_log2, s->dn_guide.p, s->dn_col[cur].p, s->dn_col[cur ^ 1u].p);
-        if ((rc = tm.mark())) return rc;
-    }
-    rgk_launch_dn_finish(st, P, s->dn_col[cur].p, d_albedo, demod, dp->albedo_floor, d_out_rgb);
-    if ((rc = tm.mark())) return rc;
-    if (d_out_variance) {
-        rgk_launch_nz_finish(st, P, s->dn_col[cur].p, d_out_variance);
-        if ((rc = tm.mark())) return rc;
-    }
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipGetLastError());
-    return tm.fold(s->post_ms[2]);
+    return denoise(s, "rgk_denoise_variance_device", POST_DENOISE_VARIANCE, xres, yres, d_accum_rgb, d_accum_count, d_half_rgb, d_half_count, d_albedo, d_normal, d_depth,
+                   *dp, k2, d_out_rgb, d_out_variance);
 }
 
 int rgk_scene_get_post_timing(const rgk_scene* s, uint32_t which, double* ms, uint32_t* n) {
-    if (!s || !n || which > 3 || (!ms && *n)) return fail(RGK_ERR_INVALID, "bad argument");
+    if (!s || !n || which >= POST_SLOTS || (!ms && *n)) return fail(RGK_ERR_INVALID, "bad argument");
     if (s->magic != RGK_SCENE_MAGIC) return fail(RGK_ERR_INVALID, "not a live scene handle");
     const std::vector<double>& v = s->post_ms[which];
     for (uint32_t i = 0; i < *n && i < v.size(); i++) ms[i] = v[i];

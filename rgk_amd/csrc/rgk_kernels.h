@@ -127,17 +127,15 @@ void rgk_launch_libm_eval(hipStream_t st, int fn, uint32_t n, const float* a, co
 void rgk_launch_aov_raygen(hipStream_t st, const DevCamera& cam, uint32_t xres, uint32_t yres, const uint32_t* pix_xy, uint32_t n, float4* rayA, float4* rayB);
 void rgk_launch_aov_gather(hipStream_t st, const DevScene& sc, float bumpmap_scale, uint32_t xres, const uint32_t* pix_xy, uint32_t n, const float4* rayA,
                            const float4* rayB, const float4* hit, float* albedo, float* normal, float* depth, int32_t* tri);
-void rgk_launch_dn_prepare(hipStream_t st, size_t P, const float* accum_rgb, const uint32_t* accum_count, const float* albedo, const float* normal, const float* depth,
-                           uint32_t demodulate, float4* col, float4* guide);
-void rgk_launch_dn_atrous(hipStream_t st, uint32_t xres, uint32_t yres, uint32_t step, float sigma2, float sigma_depth, uint32_t npow, const float4* guide,
-                          const float4* src, float4* dst);
+// ... both denoisers (grids: rgk_plan.h rgk_post_*).  half_rgb == NULL: no half-buffer, the plane's variance is 0.
+void rgk_launch_dn_prepare(hipStream_t st, size_t P, const float* accum_rgb, const uint32_t* accum_count, const float* half_rgb, const uint32_t* half_count,
+                           const float* albedo, const float* normal, const float* depth, uint32_t demodulate, float albedo_floor, float4* col, float4* guide);
+// one a-trous iteration; c: sigma_i^2 / sigma_k^2 / not read.  The variance mean is the variance-guided filter's prefilter, at step 1.
+enum RgkDnMode { RGK_DN_FIXED_SIGMA, RGK_DN_VARIANCE_GUIDED, RGK_DN_VARIANCE_MEAN };
+void rgk_launch_dn_atrous(hipStream_t st, RgkDnMode mode, uint32_t xres, uint32_t yres, uint32_t step, float c, float sigma_depth, uint32_t npow,
+                          const float4* guide, const float4* src, float4* dst);
 void rgk_launch_dn_finish(hipStream_t st, size_t P, const float4* col, const float* albedo, uint32_t demodulate, float albedo_floor, float* out_rgb);
-// ... the noise estimate from two half-buffers and the variance-guided filter (grids: rgk_plan.h rgk_nz_*)
+// ... and the noise estimate from two half-buffers
 void rgk_launch_nz_tile_sums(hipStream_t st, uint32_t xres, uint32_t yres, uint32_t tile_size, const float* accum_rgb, const uint32_t* accum_count,
                              const float* half_rgb, const uint32_t* half_count, rgk_noise_tile* tiles, float* variance);
-void rgk_launch_nz_prepare(hipStream_t st, size_t P, const float* accum_rgb, const uint32_t* accum_count, const float* half_rgb, const uint32_t* half_count,
-                           const float* albedo, const float* normal, const float* depth, uint32_t demodulate, float albedo_floor, float4* col, float4* guide);
-void rgk_launch_nz_prefilter(hipStream_t st, uint32_t xres, uint32_t yres, float sigma_depth, uint32_t npow, const float4* guide, const float4* src, float4* dst);
-void rgk_launch_nz_atrous(hipStream_t st, uint32_t xres, uint32_t yres, uint32_t step, float k2, float sigma_depth, uint32_t npow, const float4* guide,
-                          const float4* src, float4* dst);
 void rgk_launch_nz_finish(hipStream_t st, size_t P, const float4* col, float* out_variance);

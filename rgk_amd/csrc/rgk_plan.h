@@ -104,13 +104,13 @@ inline RgkResolvePlan rgk_resolve_plan(uint32_t npix, uint32_t gshift) {
     return {(int)std::min<uint32_t>((npix + PT - 1) / PT, RGK_CUS * 64), PT, (size_t)PT * (G + 1) * 16}; // (16: sizeof(float4))
 }
 
-// ------------------------------------------------------------------ noise estimate and variance-guided filter (rgk_post.hip, k_nz_*)
+// ------------------------------------------------------------------ denoisers and noise estimate (rgk_post.hip, k_dn_* / k_nz_*)
 // a thread per pixel in blocks of 256; the filters' 2-D workgroups of 32 x 8 pixels; the statistics' workgroup per tile of
 // tile_size x tile_size pixels (ragged at the right and bottom edges), tiles row-major
-constexpr int RGK_NZ_BLOCK = 256, RGK_NZ_BX = 32, RGK_NZ_BY = 8;
+constexpr int RGK_POST_BLOCK = 256, RGK_POST_BX = 32, RGK_POST_BY = 8;
 struct RgkGrid2 { uint32_t x, y; size_t count() const { return (size_t)x * y; } };
-inline uint32_t rgk_nz_pixel_grid(size_t P) { return (uint32_t)((P + RGK_NZ_BLOCK - 1) / RGK_NZ_BLOCK); }
-inline RgkGrid2 rgk_nz_filter_grid(uint32_t xres, uint32_t yres) { return {(xres + RGK_NZ_BX - 1) / RGK_NZ_BX, (yres + RGK_NZ_BY - 1) / RGK_NZ_BY}; }
+inline uint32_t rgk_post_pixel_grid(size_t P) { return (uint32_t)((P + RGK_POST_BLOCK - 1) / RGK_POST_BLOCK); }
+inline RgkGrid2 rgk_post_filter_grid(uint32_t xres, uint32_t yres) { return {(xres + RGK_POST_BX - 1) / RGK_POST_BX, (yres + RGK_POST_BY - 1) / RGK_POST_BY}; }
 inline RgkGrid2 rgk_nz_tile_grid(uint32_t xres, uint32_t yres, uint32_t tile_size) {
     return {(uint32_t)(((uint64_t)xres + tile_size - 1) / tile_size), (uint32_t)(((uint64_t)yres + tile_size - 1) / tile_size)};
 }

@@ -101,8 +101,8 @@ def test_post_launch_plans(tmp_path):
     """rgk_plan.h on the CPU: the grids of the new launches, expected values written out by hand."""
     src = tmp_path / "p.cpp"
     src.write_text('#include "rgk_plan.h"\n#include <cstdio>\nint main(){int bad=0;\n#define CHECK(c) do{ if(!(c)){std::fprintf(stderr,"%s\\n",#c);bad++;} }while(0)\n'
-                   "CHECK(rgk_nz_pixel_grid(1)==1u); CHECK(rgk_nz_pixel_grid(256)==1u); CHECK(rgk_nz_pixel_grid(257)==2u); CHECK(rgk_nz_pixel_grid((size_t)65535*65535)==16776705u);\n"
-                   "RgkGrid2 g=rgk_nz_filter_grid(67,45); CHECK(g.x==3u&&g.y==6u); g=rgk_nz_filter_grid(1,1); CHECK(g.x==1u&&g.y==1u); g=rgk_nz_filter_grid(1920,1080); CHECK(g.x==60u&&g.y==135u);\n"
+                   "CHECK(rgk_post_pixel_grid(1)==1u); CHECK(rgk_post_pixel_grid(256)==1u); CHECK(rgk_post_pixel_grid(257)==2u); CHECK(rgk_post_pixel_grid((size_t)65535*65535)==16776705u);\n"
+                   "RgkGrid2 g=rgk_post_filter_grid(67,45); CHECK(g.x==3u&&g.y==6u); g=rgk_post_filter_grid(1,1); CHECK(g.x==1u&&g.y==1u); g=rgk_post_filter_grid(1920,1080); CHECK(g.x==60u&&g.y==135u);\n"
                    "g=rgk_nz_tile_grid(67,45,32); CHECK(g.x==3u&&g.y==2u&&g.count()==6u); g=rgk_nz_tile_grid(67,45,5); CHECK(g.x==14u&&g.y==9u);\n"
                    "g=rgk_nz_tile_grid(65535,65535,1); CHECK(g.x==65535u&&g.y==65535u&&g.count()==(size_t)65535*65535); g=rgk_nz_tile_grid(65535,3,0xffffffffu); CHECK(g.x==1u&&g.y==1u);\n"
                    "return bad;}")
