@@ -447,7 +447,8 @@ int rgk_denoise_device(rgk_scene *scene, uint32_t xres, uint32_t yres, const flo
 
 /* HIP-event times of the launches of the LAST feature pass (which = 0: pixel list + ray generation, walker, gather) or denoise
  * call (which = 1: preparation, one per iteration, finish), variance-guided denoise call (which = 2: preparation, prefilter, one
- * per iteration, finish [, variance copy]) or noise estimate (which = 3: the tile sums) on this scene, in ms; recorded only while
+ * per iteration, finish [, variance copy]), noise estimate (which = 3: the tile sums) or round fold (which = 4: the copy of the tile
+ * list and the fold) on this scene, in ms; recorded only while
  * the tuning key "time_post" is 1. *n: in, room in ms; out, entries the call had (those that fit are written). */
 int rgk_scene_get_post_timing(const rgk_scene *scene, uint32_t which, double *ms, uint32_t *n);
 
@@ -497,6 +498,34 @@ int rgk_denoise_variance_device(rgk_scene *scene, uint32_t xres, uint32_t yres, 
                                 const float *d_half_rgb, const uint32_t *d_half_count, const float *d_albedo, const float *d_normal,
                                 const float *d_depth, const rgk_denoise_var_params *params, float *d_out_rgb,
                                 float *d_out_variance /* P, the filtered image's variance, may be NULL */);
+
+/* ---- adaptive tile sampling (DESIGN.md "Adaptive tile sampling") ----
+ *
+ * Which tiles of a frame the next round still renders, from the noise estimate's per-tile statistics.  HOST only: no scene, no
+ * device.  tiles / visits / live: ceil(xres/ts)*ceil(yres/ts) entries, row-major as rgk_noise_estimate_device writes them;
+ * visits[t]: rounds in which tile t was rendered.  In double, the tiles added in row-major order:
+ *   SV = sum of sum_var,  SQ = sum of sum_sq,  NE = sum of n_estimable
+ *   *done  = NE > 0 and SV <= target^2 * SQ       (the frame's relative noise is <= target), or no tile is live
+ *   live[t] = visits[t] < min_visits  or  n_estimable_t == 0  or  sum_var_t > (target^2 * SQ) * (n_estimable_t / NE)
+ * i.e. a tile stays live while its mean per-pixel variance is above the frame-wide per-pixel allowance.  The rule keeps no state: a
+ * tile that is not live is left out of the next round only and judged again after it.  target finite and >= 0; min_visits >= 2 (a
+ * tile is not estimable before its second visit).  Arguments are checked first; n_live and done may be NULL. */
+typedef struct rgk_adapt_params { float target; uint32_t min_visits; } rgk_adapt_params;
+int rgk_adapt_select(const rgk_noise_tile *tiles, const uint32_t *visits, uint32_t xres, uint32_t yres, uint32_t tile_size,
+                     const rgk_adapt_params *params, uint8_t *live, uint32_t *n_live, uint32_t *done);
+
+/* Folds a round rendered into a per-round accumulator {round} -- all zero outside the pixels the round rendered -- into the frame's
+ * accumulator {total} and, tile by tile, into the half-buffer {half}.  For every pixel of every listed tile, rgb and count alike:
+ *   total += round;   where to_half[i] != 0: half += round;   round = 0
+ * in float32 / uint32, one addition per element.  Pixels outside the listed tiles are neither read nor written in any of the six
+ * planes, so a round buffer that starts all zero is all zero again after the fold of the tiles rendered into it and never needs a
+ * whole-frame clear.  Tiles must lie in the frame, be non-empty and not overlap each other; the six planes must be six different
+ * buffers: checked on the host before the scene or the device is touched (the seed of a tile is not read).  tiles / to_half: HOST
+ * arrays of n_tiles; the planes: DEVICE pointers on the scene's GPU, 3P floats / P counts.  One launch on the scene's stream; blocking.
+ * Not while a round is in flight on this scene.  Uses a tile buffer of its own and nothing a round reads or writes. */
+int rgk_round_fold_device(rgk_scene *scene, uint32_t xres, uint32_t yres, const rgk_tile *tiles, uint32_t n_tiles,
+                          const uint8_t *to_half /* n_tiles */, float *d_round_rgb, uint32_t *d_round_count, float *d_total_rgb,
+                          uint32_t *d_total_count, float *d_half_rgb, uint32_t *d_half_count);
 
 /* The pinned transcendental functions of the path (include/rgk_libm.h) evaluated on the device, for the test that the GPU
  * and the CPU produce the same bits: fn 0 sin, 1 cos, 2 acos, 3 asin, 4 atan2(a[i], b[i]) (b may be NULL otherwise). */

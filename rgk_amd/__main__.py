@@ -24,6 +24,9 @@
                     rewrites the output, and makes --denoise use the variance-guided filter from round 2 on.  With --checkpoint
                     the half-buffer is saved beside the checkpoint as `F.half`; resuming a checkpoint that has none is refused
   --until-noise X   implies --noise; stops the frame once the relative noise is <= X (rounds / -t still bound it)
+  --adaptive [N]    needs --until-noise: from the second round on a round renders only the 32 x 32 tiles whose own noise is still above
+                    their share of the target; every tile is rendered at least N times (default 4, at least 2).  Not with
+                    bidirectional rounds ("reverse" > 0)
 FILE is a .json or .rtc scene config.  One process drives one GPU; several GPUs: python -m torch.distributed.run ... bench.py.
 """
 import argparse
@@ -85,10 +88,14 @@ def main(argv=None):
     ap.add_argument("--denoise", action="store_true")
     ap.add_argument("--noise", action="store_true")
     ap.add_argument("--until-noise", type=float, default=None, metavar="X")
+    ap.add_argument("--adaptive", type=int, nargs="?", const=4, default=None, metavar="MIN_VISITS")
     ap.add_argument("--frames", type=int, default=None, help="with -r: stop after this many frames (default: all 501)")
     args = ap.parse_args(argv)
     verbosity = max(0, 2 + args.v - args.q)
     say = lambda lvl, *a: print(*a) if verbosity >= lvl else None
+    if args.adaptive is not None and (args.until_noise is None or args.adaptive < 2):
+        print("ERROR: --adaptive needs --until-noise." if args.until_noise is None else "ERROR: Invalid argument for --adaptive (at least 2).")
+        return 1
     try:
         cfg = load_config(args.file)
     except ConfigFileException as e:
@@ -141,7 +148,12 @@ def main(argv=None):
             open(out, "ab").close()  # claim the frame before rendering it (processes sharing the directory skip it)
             say(1, f"Rendering frame #{frame_no} of ~{int(time_length * fps)} ({format_percent(t / time_length * 100.0)})")
         camera = cfg.get_camera(t / time_length if args.rotate else 0.0)
-        drv = rd.RenderDriver(scene, cfg, camera, device=device, track_noise=track_noise)
+        try:
+            drv = rd.RenderDriver(scene, cfg, camera, device=device, track_noise=track_noise,
+                                  adaptive=capi.AdaptParams(args.until_noise, args.adaptive) if args.adaptive is not None else None)
+        except ValueError as e:
+            print(f"ERROR: {e}")
+            return 1
         if args.debug:
             x, y = args.debug
             if not (0 <= x < cfg.xres and 0 <= y < cfg.yres):
@@ -176,7 +188,8 @@ def main(argv=None):
                              aov_files={k: insert_file_suffix(out, k) for k in ("albedo", "normal", "depth")} if args.aov else None,
                              denoised_file=insert_file_suffix(out, "denoised") if args.denoise else None,
                              **(dict(until_noise=args.until_noise, noise_file=insert_file_suffix(out, "noise"),
-                                     on_noise=lambda r, rel: say(1, f"Round {r}: relative noise {rel:.4g}")) if track_noise else {}))
+                                     on_noise=lambda r, rel, n_live=None: say(1, f"Round {r}: " + (f"{n_live} live tiles, " if n_live is not None else "") +
+                                                                                  f"relative noise {rel:.4g}")) if track_noise else {}))
             mon.rays_done = sum(c.path_rays for c in drv.counters)
     return 0
 

@@ -148,6 +148,15 @@ class DenoiseVarParams(C.Structure):
         super().__init__(iterations, sigma_k, sigma_depth, normal_power_log2, demodulate, albedo_floor)
 
 
+class AdaptParams(C.Structure):
+    """rgk_adapt_params: the noise target a frame renders to and the visits every tile gets before it may retire (the default 4 is a
+    guard against retiring on a lucky early estimate -- a stated choice, not a tuned value; at least 2)."""
+    _fields_ = [("target", C.c_float), ("min_visits", C.c_uint32)]
+
+    def __init__(self, target=0.0, min_visits=4):
+        super().__init__(target, min_visits)
+
+
 # every symbol include/rgk.h declares (tests check the .so exports all of them)
 EXPORTS = ["rgk_last_error", "rgk_device_count", "rgk_scene_create", "rgk_scene_destroy",
            "rgk_scene_get_info", "rgk_scene_get_progress", "rgk_scene_set_tuning", "rgk_scene_refit", "rgk_generate_task_list", "rgk_camera_init", "rgk_render_round",
@@ -158,7 +167,7 @@ EXPORTS = ["rgk_last_error", "rgk_device_count", "rgk_scene_create", "rgk_scene_
            "rgk_accum_download", "rgk_accum_upload", "rgk_accum_add", "rgk_accum_set_tag", "rgk_accum_save", "rgk_accum_load",
            "rgk_shard_tiles", "rgk_comm_get_unique_id", "rgk_comm_create", "rgk_comm_destroy", "rgk_accum_reduce",
            "rgk_render_aov_device", "rgk_render_aov", "rgk_denoise_device", "rgk_scene_get_post_timing",
-           "rgk_noise_estimate_device", "rgk_denoise_variance_device"]
+           "rgk_noise_estimate_device", "rgk_denoise_variance_device", "rgk_adapt_select", "rgk_round_fold_device"]
 
 _p = C.POINTER
 
@@ -220,6 +229,9 @@ def _bind(lib):
                                               _p(NoiseTile), C.c_void_p]
     lib.rgk_denoise_variance_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, _p(DenoiseVarParams), C.c_void_p, C.c_void_p]
+    lib.rgk_adapt_select.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, _p(AdaptParams), C.c_void_p, _p(C.c_uint32), _p(C.c_uint32)]
+    lib.rgk_round_fold_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, _p(Tile), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p]
     lib.rgk_scene_get_post_timing.argtypes = [C.c_void_p, C.c_uint32, _p(C.c_double), _p(C.c_uint32)]
     lib.rgk_float_to_half.argtypes = [C.c_float]
     lib.rgk_float_to_half.restype = C.c_uint16

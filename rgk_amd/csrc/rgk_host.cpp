@@ -22,6 +22,7 @@
 #include "rgk_commit.h"
 #include "rgk_kernels.h"
 #include "rgk_build.h"
+#include "rgk_adapt.h"
 
 namespace {
 
@@ -94,7 +95,7 @@ struct RgkTuning {
 };
 
 // rgk_scene_get_post_timing's `which` (rgk.h): the post-processing call whose launch times a slot holds
-enum PostSlot : uint32_t { POST_AOV = 0, POST_DENOISE = 1, POST_DENOISE_VARIANCE = 2, POST_NOISE = 3, POST_SLOTS = 4 };
+enum PostSlot : uint32_t { POST_AOV = 0, POST_DENOISE = 1, POST_DENOISE_VARIANCE = 2, POST_NOISE = 3, POST_FOLD = 4, POST_SLOTS = 5 };
 constexpr uint32_t RGK_SCENE_MAGIC = 0x53474b52u; // "RKGS": what a live scene handle starts with (rgk_scene_get_post_timing)
 struct rgk_scene {
     uint32_t magic = RGK_SCENE_MAGIC;
@@ -156,6 +157,7 @@ struct rgk_scene {
     DevBuf<uint32_t> scratch_u;
     DevBuf<float4> dn_col[2], dn_guide; // the denoiser's two colour planes and its guide plane {n.xyz, z}
     DevBuf<rgk_noise_tile> nz_tiles;    // the noise estimate's per-tile sums
+    DevBuf<uint32_t> fold_buf;          // the round fold's tile list (5 words per tile), then its flags (a byte per tile)
     std::vector<double> post_ms[POST_SLOTS]; // launch times of the last call of each kind (tuning "time_post")
     std::vector<hipEvent_t> events;
     uint32_t* h_counters = nullptr; // pinned
@@ -1329,6 +1331,50 @@ int rgk_denoise_variance_device(rgk_scene* s, uint32_t xres, uint32_t yres, cons
     if (d_half_rgb == d_accum_rgb || d_half_count == d_accum_count) return fail(RGK_ERR_INVALID, "the half-buffer must not be the accumulator");
     return denoise(s, "rgk_denoise_variance_device", POST_DENOISE_VARIANCE, xres, yres, d_accum_rgb, d_accum_count, d_half_rgb, d_half_count, d_albedo, d_normal, d_depth,
                    *dp, k2, d_out_rgb, d_out_variance);
+}
+
+int rgk_adapt_select(const rgk_noise_tile* tiles, const uint32_t* visits, uint32_t xres, uint32_t yres, uint32_t tile_size, const rgk_adapt_params* prm,
+                     uint8_t* live, uint32_t* n_live, uint32_t* done) {
+    if (const char* why = rgk_adapt_check(tiles, visits, xres, yres, tile_size, prm, live)) return fail(RGK_ERR_INVALID, "rgk_adapt_select: %s", why);
+    const RgkAdaptResult r = rgk_adapt_rule(tiles, visits, xres, yres, tile_size, *prm, live);
+    if (n_live) *n_live = r.n_live;
+    if (done) *done = r.done ? 1u : 0u;
+    return RGK_OK;
+}
+
+int rgk_round_fold_device(rgk_scene* s, uint32_t xres, uint32_t yres, const rgk_tile* tiles, uint32_t n_tiles, const uint8_t* to_half, float* d_round_rgb,
+                          uint32_t* d_round_count, float* d_total_rgb, uint32_t* d_total_count, float* d_half_rgb, uint32_t* d_half_count) {
+    // (every check before the scene or the device is touched)
+    if (!s || (n_tiles && (!tiles || !to_half)) || !d_round_rgb || !d_round_count || !d_total_rgb || !d_total_count || !d_half_rgb || !d_half_count)
+        return fail(RGK_ERR_INVALID, "null argument");
+    if (xres == 0 || yres == 0 || xres > 65535 || yres > 65535) return fail(RGK_ERR_INVALID, "resolution out of range");
+    const void* planes[6] = {d_round_rgb, d_round_count, d_total_rgb, d_total_count, d_half_rgb, d_half_count};
+    for (int i = 0; i < 6; i++)
+        for (int j = i + 1; j < 6; j++)
+            if (planes[i] == planes[j]) return fail(RGK_ERR_INVALID, "the six planes must be six different buffers");
+    uint32_t max_height = 0, bad = 0;
+    if (const char* why = rgk_fold_check_tiles(tiles, n_tiles, xres, yres, max_height, bad)) return fail(RGK_ERR_INVALID, "round fold: %s (tile %u)", why, bad);
+    if (s->prog_busy.load()) return fail(RGK_ERR_INVALID, "rgk_round_fold_device while a round is in flight on this scene");
+    s->post_ms[POST_FOLD].clear();
+    if (n_tiles == 0) return RGK_OK;
+    HIPCHK(hipSetDevice(s->device));
+    int rc;
+    static_assert(sizeof(rgk_tile) == 5 * sizeof(uint32_t), "rgk_tile layout");
+    if ((rc = s->fold_buf.alloc((size_t)n_tiles * 5 + (n_tiles + 3u) / 4u))) return rc;
+    hipStream_t st = s->stream;
+    PostTimer tm(s);
+    if ((rc = tm.mark())) return rc;
+    // (queued copies of the caller's arrays: they are the caller's until this call returns, and it waits for the stream first)
+    uint8_t* d_flags = reinterpret_cast<uint8_t*>(s->fold_buf.p + (size_t)n_tiles * 5);
+    HIPCHK(hipMemcpyAsync(s->fold_buf.p, tiles, (size_t)n_tiles * sizeof(rgk_tile), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_flags, to_half, n_tiles, hipMemcpyHostToDevice, st));
+    if ((rc = tm.mark())) return rc;
+    rgk_launch_round_fold(st, xres, reinterpret_cast<const rgk_tile*>(s->fold_buf.p), d_flags, n_tiles, max_height, d_round_rgb, d_round_count, d_total_rgb,
+                          d_total_count, d_half_rgb, d_half_count);
+    if ((rc = tm.mark())) return rc;
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    return tm.fold(s->post_ms[POST_FOLD]);
 }
 
 int rgk_scene_get_post_timing(const rgk_scene* s, uint32_t which, double* ms, uint32_t* n) {

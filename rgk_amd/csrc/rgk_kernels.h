@@ -139,3 +139,6 @@ void rgk_launch_dn_finish(hipStream_t st, size_t P, const float4* col, const flo
 void rgk_launch_nz_tile_sums(hipStream_t st, uint32_t xres, uint32_t yres, uint32_t tile_size, const float* accum_rgb, const uint32_t* accum_count,
                              const float* half_rgb, const uint32_t* half_count, rgk_noise_tile* tiles, float* variance);
 void rgk_launch_nz_finish(hipStream_t st, size_t P, const float4* col, float* out_variance);
+// the round fold: tiles / to_half on the device, n_tiles > 0 checked tiles (rgk_adapt.h rgk_fold_check_tiles gives max_tile_height)
+void rgk_launch_round_fold(hipStream_t st, uint32_t xres, const rgk_tile* tiles, const uint8_t* to_half, uint32_t n_tiles, uint32_t max_tile_height,
+                           float* round_rgb, uint32_t* round_count, float* total_rgb, uint32_t* total_count, float* half_rgb, uint32_t* half_count);

@@ -24,6 +24,11 @@
 // (Sponza proxy, ms per round: off 146.6; K, pixels = 4, 64: 138.8; 8, 64: 137.5; 4, 16: 139.4; 4, 8: 139.1; 6, 8: 136.3; 8, 8: 136.2)
 #endif
 #define RGK_ENTRY_PIX (1u << RGK_ENTRY_SHIFT)
+#if defined(__HIPCC__)
+#define RGK_PLAN_HD __host__ __device__ // what a kernel calls too
+#else
+#define RGK_PLAN_HD
+#endif
 
 // Compute units every full grid is sized for (MI355X).  A constant, not a device query: the grids are part of what was measured.
 constexpr int RGK_CUS = 256;
@@ -113,4 +118,23 @@ inline uint32_t rgk_post_pixel_grid(size_t P) { return (uint32_t)((P + RGK_POST_
 inline RgkGrid2 rgk_post_filter_grid(uint32_t xres, uint32_t yres) { return {(xres + RGK_POST_BX - 1) / RGK_POST_BX, (yres + RGK_POST_BY - 1) / RGK_POST_BY}; }
 inline RgkGrid2 rgk_nz_tile_grid(uint32_t xres, uint32_t yres, uint32_t tile_size) {
     return {(uint32_t)(((uint64_t)xres + tile_size - 1) / tile_size), (uint32_t)(((uint64_t)yres + tile_size - 1) / tile_size)};
+}
+
+// ------------------------------------------------------------------ the round fold (rgk_post.hip, k_round_fold)
+// Workgroup (i, b) of RGK_POST_BLOCK threads takes band b of listed tile i: its rows [b * RGK_FOLD_ROWS, + RGK_FOLD_ROWS), cut at
+// the tile's height (a band past it is empty: the grid is as high as the list's highest tile needs).  A band of `rows` rows of a
+// tile `tw` pixels wide is rows * tw * C consecutive elements k of a plane with C values per pixel, row after row; thread t takes
+// k = t, t + RGK_POST_BLOCK, ...: a wave's 64 lanes are 256 contiguous bytes of a row, or the end of one row and the start of
+// the next.  A 32-pixel tile row is 96 floats (384 B) of an rgb plane; 8 rows are 3 rgb elements and one count per thread.
+constexpr uint32_t RGK_FOLD_ROWS = 8;
+inline RgkGrid2 rgk_fold_grid(uint32_t n_tiles, uint32_t max_tile_height) { return {n_tiles, (max_tile_height + RGK_FOLD_ROWS - 1) / RGK_FOLD_ROWS}; }
+struct RgkRowRange { uint32_t r0, r1; };
+RGK_PLAN_HD inline RgkRowRange rgk_fold_band(uint32_t band, uint32_t tile_height) {
+    const uint64_t a = (uint64_t)band * RGK_FOLD_ROWS, b = a + RGK_FOLD_ROWS;
+    return {(uint32_t)(a < tile_height ? a : tile_height), (uint32_t)(b < tile_height ? b : tile_height)};
+}
+// element k of the band that starts at frame row y (tile column x0, width tw) -> its index in a plane of xres * C values per row
+RGK_PLAN_HD inline size_t rgk_fold_element(uint32_t xres, uint32_t x0, uint32_t y, uint32_t tw, uint32_t C, uint32_t k) {
+    const uint32_t row = k / (tw * C), col = k - row * (tw * C);
+    return ((size_t)(y + row) * xres + x0) * C + col;
 }

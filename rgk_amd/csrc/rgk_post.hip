@@ -11,6 +11,7 @@
 //   k_dn_finish              colour plane (float4) -> out_rgb (3 floats per pixel), remodulated on request
 //   k_nz_finish              the plane's 4th float -> a plane of P floats
 //   k_nz_tile_sums           accumulator + half-buffer -> per tile {sum of v, sum of |c|^2, estimable pixels} (doubles), raw v plane
+//   k_round_fold             the listed tiles of a per-round accumulator -> += into the frame's, per tile into the half-buffer, and cleared
 // (tests/noise_ref.py's k_nz_prepare, k_nz_prefilter and k_nz_atrous are k_dn_prepare<true> and k_dn_atrous<VarianceMean / VarianceGuided>)
 //
 // The traversal between raygen and gather is the round's own k_trace_closest (rgk_launch_trace_closest): no second walker.
@@ -372,4 +373,38 @@ void rgk_launch_dn_finish(hipStream_t st, size_t P, const float4* col, const flo
 }
 void rgk_launch_nz_finish(hipStream_t st, size_t P, const float4* col, float* out_variance) {
     k_nz_finish<<<rgk_post_pixel_grid(P), RGK_POST_BLOCK, 0, st>>>(P, col, out_variance);
+}
+
+// ------------------------------------------------------------------ the round fold (rgk.h rgk_round_fold_device)
+// One plane pair of one band (rgk_plan.h: which elements, in which order): total += round, half += round where the tile's flag
+// says so, round = 0.  One float32 / uint32 addition per element, nothing contracted: the bits of the whole-frame additions it stands
+// in for.  Pure streaming -- per element 2 or 3 loads and as many stores of 4 bytes, a wave's instruction 256 contiguous bytes -- and
+// nothing outside the band is touched.  (The planes are six different buffers: the host has checked.)
+template <uint32_t C, class T>
+__device__ __forceinline__ void fold_band(uint32_t xres, uint32_t x0, uint32_t y, uint32_t tw, uint32_t rows, bool to_half, T* __restrict__ round_,
+                                          T* __restrict__ total, T* __restrict__ half) {
+    const uint32_t n = rows * tw * C;
+    for (uint32_t k = threadIdx.x; k < n; k += RGK_POST_BLOCK) {
+        const size_t e = rgk_fold_element(xres, x0, y, tw, C, k);
+        const T r = round_[e];
+        total[e] = total[e] + r;
+        if (to_half) half[e] = half[e] + r; // (the same for a whole workgroup)
+        round_[e] = (T)0;
+    }
+}
+__global__ __launch_bounds__(RGK_POST_BLOCK) void k_round_fold(uint32_t xres, const rgk_tile* __restrict__ tiles, const uint8_t* __restrict__ to_half,
+                                                                float* __restrict__ round_rgb, uint32_t* __restrict__ round_count, float* __restrict__ total_rgb,
+                                                                uint32_t* __restrict__ total_count, float* __restrict__ half_rgb, uint32_t* __restrict__ half_count) {
+    const rgk_tile t = tiles[blockIdx.x];
+    const RgkRowRange rr = rgk_fold_band(blockIdx.y, t.y1 - t.y0);
+    if (rr.r0 == rr.r1) return; // a band below this tile's last row
+    const bool h = to_half[blockIdx.x] != 0;
+    const uint32_t tw = t.x1 - t.x0, y = t.y0 + rr.r0, rows = rr.r1 - rr.r0;
+    fold_band<3u>(xres, t.x0, y, tw, rows, h, round_rgb, total_rgb, half_rgb);
+    fold_band<1u>(xres, t.x0, y, tw, rows, h, round_count, total_count, half_count);
+}
+void rgk_launch_round_fold(hipStream_t st, uint32_t xres, const rgk_tile* tiles, const uint8_t* to_half, uint32_t n_tiles, uint32_t max_tile_height,
+                           float* round_rgb, uint32_t* round_count, float* total_rgb, uint32_t* total_count, float* half_rgb, uint32_t* half_count) {
+    const RgkGrid2 g = rgk_fold_grid(n_tiles, max_tile_height);
+    k_round_fold<<<dim3(g.x, g.y), RGK_POST_BLOCK, 0, st>>>(xres, tiles, to_half, round_rgb, round_count, total_rgb, total_count, half_rgb, half_count);
 }

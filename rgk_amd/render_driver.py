@@ -159,9 +159,17 @@ class Scene:
         capi.check(self.lib, self.lib.rgk_denoise_variance_device(self.h, xres, yres, d_accum_rgb, d_accum_count, d_half_rgb, d_half_count, d_albedo,
                                                                   d_normal, d_depth, C.byref(params), d_out_rgb, d_out_variance))
 
+    def round_fold_device(self, xres, yres, tiles, to_half, d_round_rgb, d_round_count, d_total_rgb, d_total_count, d_half_rgb, d_half_count):
+        """rgk_round_fold_device: total += round, half += round where to_half[i], round = 0 over the listed tiles' pixels and nowhere
+        else; DEVICE pointers (ints) on the scene's GPU, to_half one flag per tile."""
+        flags = np.ascontiguousarray(to_half, dtype=np.uint8)
+        assert flags.shape == (len(tiles),)
+        capi.check(self.lib, self.lib.rgk_round_fold_device(self.h, xres, yres, tiles, len(tiles), flags.ctypes.data, d_round_rgb, d_round_count,
+                                                            d_total_rgb, d_total_count, d_half_rgb, d_half_count))
+
     def post_timing(self, which):
         """HIP-event times (ms) of the launches of the last feature pass (0) / denoise call (1) / variance-guided denoise call (2) /
-        noise estimate (3); set_tuning(time_post=1) first."""
+        noise estimate (3) / round fold (4: the copy of its tile list, the fold); set_tuning(time_post=1) first."""
         ms, n = (C.c_double * 32)(), C.c_uint32(32)
         capi.check(self.lib, self.lib.rgk_scene_get_post_timing(self.h, which, ms, C.byref(n)))
         return list(ms[:min(n.value, 32)])
@@ -171,6 +179,24 @@ class Scene:
         capi.check(self.lib, self.lib.rgk_render_round_device(self.h, C.byref(camera), C.byref(params), tiles, len(tiles),
                                                               d_accum_ptr, d_count_ptr, C.byref(cnt)))
         return cnt
+
+
+def adapt_select(tiles, visits, xres, yres, params, tile_size=TILE_SIZE):
+    """rgk_adapt_select (host only): the tiles the next round still renders.  tiles: the (tiles_y, tiles_x) statistics of
+    noise_estimate_device; visits: rounds each tile was rendered in, same order; params: capi.AdaptParams.
+    -> (live: (tiles_y, tiles_x) bool, n_live, done)."""
+    lib = capi.load_product()
+    dt = np.dtype([("sum_var", "f8"), ("sum_sq", "f8"), ("n_estimable", "u8")])
+    st = np.ascontiguousarray(tiles, dtype=dt)
+    vis = np.ascontiguousarray(visits, dtype=np.uint32)
+    ty, tx = -(-yres // tile_size), -(-xres // tile_size)
+    if st.size != ty * tx or vis.size != ty * tx:
+        raise ValueError(f"{ty} x {tx} tiles expected, got {st.size} statistics and {vis.size} visit counts")
+    live = np.zeros(ty * tx, np.uint8)
+    n_live, done = C.c_uint32(0), C.c_uint32(0)
+    capi.check(lib, lib.rgk_adapt_select(st.ctypes.data, vis.ctypes.data, xres, yres, tile_size, C.byref(params), live.ctypes.data,
+                                         C.byref(n_live), C.byref(done)))
+    return live.astype(bool).reshape(ty, tx), n_live.value, bool(done.value)
 
 
 def sampler_eval(seed, index, dim, is2d):
@@ -264,7 +290,7 @@ class RenderDriver:
     """RenderDriver::RenderFrame / RenderRound for one process per GPU."""
 
     def __init__(self, scene, cfg, camera, rank=0, world_size=1, device=None, sampler=capi.SAMPLER_HALTON, flags=0,
-                 host_reduce=False, track_noise=False):
+                 host_reduce=False, track_noise=False, adaptive=None):
         import torch
         self.scene, self.cfg, self.camera = scene, cfg, camera
         self.rank, self.world_size = rank, world_size
@@ -288,17 +314,56 @@ class RenderDriver:
         # instead of to the running total, which may differ in the last place.  Off: every code path is the untracked one.
         self.track_noise = bool(track_noise)
         self.half_ob = EXRTexture(cfg.xres, cfg.yres, self.device) if self.track_noise and rank == 0 else None
+        # adaptive (a capi.AdaptParams; its target is render_frame's until_noise): a round renders a subset of the tiles -- those
+        # rgk_adapt_select leaves live -- into the per-round accumulator, and one launch over those tiles folds it into total_ob and,
+        # on a TILE's odd visits, into half_ob (rgk_round_fold_device).  The per-round accumulator is all zero between rounds.
+        # `visits`: rounds each tile was rendered in, in the row-major tile order of noise()["tiles"]; `task_tile`: for task i of
+        # the centre-out list, its index there.  None: every code path is the one without it.
+        self.adaptive = adaptive
+        if adaptive is not None:
+            if not self.track_noise:
+                raise ValueError("adaptive tile sampling needs track_noise=True: it retires tiles on the half-buffer noise estimate")
+            if int(self.params.reverse) > 0:
+                raise ValueError("adaptive tile sampling cannot be combined with reverse > 0: light-tracing splats land in tiles that "
+                                 "gained no sample count that round, which biases them")
+            if world_size > 1:
+                raise ValueError("adaptive tile sampling needs world_size == 1: the root adds a constant count per round")
+            if int(adaptive.min_visits) < 2:
+                raise ValueError("adaptive min_visits must be >= 2: a tile is not estimable before its second visit")
+            tx = -(-cfg.xres // TILE_SIZE)
+            self.task_tile = np.array([(t.y0 // TILE_SIZE) * tx + t.x0 // TILE_SIZE for t in self.tasks], dtype=np.int64)
+            self.visits = np.zeros(self.n_tasks, dtype=np.uint32)
 
-    def render_round(self, reduce=True):
+    def render_round(self, reduce=True, live=None):
         """One RenderRound: every rank renders its tiles into its private accumulator, then ONE sum-reduce of the RGB
         accumulator to rank 0 (no data-path collective inside the round).  Sample counts are not exchanged: every tile
         list covers the frame and every pixel of it gains `multisample` samples per round, splats add none
-        (tracer.cpp:18,25), so rank 0 adds that constant itself."""
+        (tracer.cpp:18,25), so rank 0 adds that constant itself.
+        live (adaptive drivers): a mask over the tiles in the order of noise()["tiles"]; only those are rendered.  None: all.  The
+        task counter advances by the whole list either way: a tile carries the seed it has in a uniform frame's round."""
         import torch
+        if live is not None and self.adaptive is None:
+            raise ValueError("render_round(live=...) needs an adaptive driver")
         tiles = generate_task_list(self.cfg.xres, self.cfg.yres, SEEDSTART, self.seedcount)
         self.seedcount += len(tiles)  # `c = seedcount++` per task, render_driver.cpp:160
         odd = self.rounds_done % 2 == 1
-        if self.world_size == 1 and self.track_noise:
+        if self.adaptive is not None:
+            if self.round_ob is None:
+                self.round_ob = EXRTexture(self.cfg.xres, self.cfg.yres, self.device)  # zero, and every fold leaves it so
+            mask = np.ones(self.n_tasks, bool) if live is None else np.asarray(live, dtype=bool).reshape(-1)
+            if mask.shape != (self.n_tasks,):
+                raise ValueError(f"live: {self.n_tasks} tiles expected, got {mask.size}")
+            idx = np.flatnonzero(mask[self.task_tile])  # centre-out order, as the whole list has it
+            mine = (capi.Tile * len(idx))(*[tiles[i] for i in idx])
+            which = self.task_tile[idx]
+            ob = self.round_ob
+            torch.cuda.current_stream(self.device).synchronize()
+            cnt = self.scene.render_round_device(self.camera, self.params, mine, ob.data.data_ptr(), ob.count.data_ptr())
+            self.scene.round_fold_device(self.cfg.xres, self.cfg.yres, mine, self.visits[which] & 1, ob.data.data_ptr(), ob.count.data_ptr(),
+                                         self.total_ob.data.data_ptr(), self.total_ob.count.data_ptr(), self.half_ob.data.data_ptr(),
+                                         self.half_ob.count.data_ptr())
+            self.visits[which] += 1
+        elif self.world_size == 1 and self.track_noise:
             if self.round_ob is None:
                 self.round_ob = EXRTexture(self.cfg.xres, self.cfg.yres, self.device)
             else:
@@ -460,6 +525,31 @@ class RenderDriver:
             if self._load_ob(self.half_ob, half) != (rounds_done, seedcount):
                 raise RuntimeError(f"`{half}` was not written together with `{path}`")
         self.rounds_done, self.seedcount = rounds_done, seedcount
+        if self.adaptive is not None:
+            self.visits = self._visits_from_counts(path)
+
+    def _visits_from_counts(self, path):
+        """An adaptive frame's per-tile state needs no file of its own: a tile's visits are its pixels' sample count over
+        `multisample`, and the half-buffer holds every second of them.  A tile whose pixels do not all say so is refused."""
+        ms = int(self.params.multisample)
+        n, nb = (ob.count.cpu().numpy().view(np.uint32) for ob in (self.total_ob, self.half_ob))
+        visits = np.zeros(self.n_tasks, dtype=np.uint32)
+        for t, k in zip(self.tasks, self.task_tile):
+            a, b = n[t.y0:t.y1, t.x0:t.x1], nb[t.y0:t.y1, t.x0:t.x1]
+            v = int(a[0, 0]) // ms
+            if not ((a == v * ms).all() and (b == (v // 2) * ms).all()):
+                raise RuntimeError(f"`{path}`: the tile at ({t.x0}, {t.y0}) is not uniform in its sample counts, or its half-buffer does not "
+                                   "hold every second visit: not a frame an adaptive driver can continue")
+            visits[k] = v
+        return visits
+
+    def adapt_select(self, target, nz=None):
+        """rgk_adapt_select on the current noise estimate (nz: what noise() returned, if the caller has it) with this driver's
+        visits and min_visits -> (live mask (tiles_y, tiles_x), n_live, done).  Needs two rounds."""
+        nz = nz or self.noise()
+        if self.adaptive is None or nz is None:
+            raise ValueError("adapt_select needs an adaptive driver and two rounds")
+        return adapt_select(nz["tiles"], self.visits, self.cfg.xres, self.cfg.yres, capi.AdaptParams(target, self.adaptive.min_visits))
 
     def _load_ob(self, ob, path):
         import torch
@@ -510,20 +600,29 @@ class RenderDriver:
         With track_noise -- until_noise: stop once noise()["rel"] <= until_noise, checked after every round from the second on
         (`rounds` / `minutes` still bound the frame); from the second round on denoised_file comes from the variance-guided
         filter, and noise_file holds sqrt of that filter's output variance in R, G and B, scaled like output_file;
-        on_noise(rounds_done, rel) is called on rank 0 after every round that has an estimate."""
+        on_noise(rounds_done, rel) is called on rank 0 after every round that has an estimate.
+        With an adaptive driver and until_noise: after every round from the second on rgk_adapt_select (target = until_noise) says
+        whether the frame is done and which tiles the next round renders; on_noise(rounds_done, rel, n_live) also gets their number.
+        The rule keeps no state, so a frame resumed from a checkpoint goes on with the tiles the interrupted one would have rendered."""
         if (until_noise is not None or noise_file or on_noise) and not self.track_noise:
             raise ValueError("until_noise, noise_file and on_noise need track_noise=True")
         rounds = self.cfg.render_rounds if rounds is None else rounds
         minutes = self.cfg.render_minutes if minutes is None else minutes
         t0 = self.clock()
+        adapting = self.adaptive is not None and until_noise is not None
+        live = [None]  # the next round's tiles (None: all)
         if aov_files and self.rank == 0:
             a = self.render_aov()
             for name, path in aov_files.items():
                 plane = a[name] if a[name].dim() == 3 else a[name].unsqueeze(-1).expand(-1, -1, 3)
                 write_exr(path, plane.cpu().numpy())
+        if adapting and self.rounds_done >= 2:  # resumed
+            live[0], _, done = self.adapt_select(until_noise)
+            if done:
+                return self.total_ob
 
         def one():
-            self.render_round()
+            self.render_round(live=live[0])
             if output_file and self.rank == 0:
                 val = self.total_ob.write(output_file, getattr(self.cfg, "output_scale", -1.0))
                 if self.track_noise and self.rounds_done >= 2 and (denoised_file or noise_file):
@@ -537,6 +636,11 @@ class RenderDriver:
             if checkpoint and self.rank == 0:
                 self.save_checkpoint(checkpoint)
             nz = self.noise() if on_noise or until_noise is not None else None
+            if adapting and nz is not None:
+                live[0], n_live, done = self.adapt_select(until_noise, nz)
+                if on_noise:
+                    on_noise(self.rounds_done, nz["rel"], n_live)
+                return done
             if on_noise and nz is not None:
                 on_noise(self.rounds_done, nz["rel"])
             return until_noise is not None and self._noise_reached(until_noise, nz)
