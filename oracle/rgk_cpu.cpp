@@ -1187,7 +1187,10 @@ struct PathPoint {
     Radiance light_from_source;
 };
 
-struct Counters { uint64_t path_rays = 0, shadow_rays = 0; TravStats closest, shadow; bool count_trav = false; };
+struct Counters {
+    uint64_t path_rays = 0, shadow_rays = 0; TravStats closest, shadow; bool count_trav = false;
+    uint64_t lv_kind[16] = {}, lv_none = 0; // light sub-path vertices by material kind; paths whose light sub-path has none (orc_render_round_split)
+};
 
 struct PathTracer {
     const Scene& scene;
@@ -1198,9 +1201,11 @@ struct PathTracer {
     unsigned samplerSeed;
     unsigned sampler_kind;
     Counters& cnt;
+    bool exhaustive = false; // orc_render_round_split: every ray answered by testing every triangle under the walkers' stated rule (no tree)
 
     bool Vis(vec3 a, vec3 b) const {
         cnt.shadow_rays++;
+        if (exhaustive) return scene.VisibilityExhaustive(a, b);
         return scene.Visibility(a, b, cnt.count_trav ? &cnt.shadow : nullptr);
     }
 
@@ -1214,7 +1219,8 @@ struct PathTracer {
         while (n < depth__) {
             n++;
             cnt.path_rays++;
-            Intersection i = scene.FindIntersectKdOtherThan(current_ray, last_triangle, cnt.count_trav ? &cnt.closest : nullptr);
+            Intersection i = exhaustive ? scene.FindExhaustive(current_ray, last_triangle)
+                                        : scene.FindIntersectKdOtherThan(current_ray, last_triangle, cnt.count_trav ? &cnt.closest : nullptr);
             PathPoint p;
             p.contribution = cumulative_transfer_coefficients;
             if (i.triangle < 0) {
@@ -1319,6 +1325,10 @@ struct PathTracer {
             // position lets the GPU generate the light sub-path before the forward path.
             sampler.Seek2D(bounce_dim0 + depth);
             light_path = GeneratePath(light_ray, reverse, -1.0f, sampler);
+            unsigned on_surface = 0;
+            for (const PathPoint& p : light_path)
+                if (!p.infinity) { on_surface++; cnt.lv_kind[p.mat->kind & 15u]++; }
+            if (!on_surface) cnt.lv_none++;
         }
         Radiance light_at_path_start =
             Radiance(main_light.color.r, main_light.color.g, main_light.color.b) *
@@ -1527,14 +1537,13 @@ int orc_generate_task_list(uint32_t tile_size, uint32_t xres, uint32_t yres, flo
     return 0;
 }
 
-// render_driver.cpp:144-190 + tracer.cpp:6-37 + texture.cpp:342-347,403-412
-int orc_render_round(void* h, const rgk_camera* cam, const rgk_params* prm, const rgk_tile* tiles, uint32_t n_tiles,
-                     float* accum_rgb, uint32_t* accum_count, rgk_counters* out_cnt, int n_threads) {
-    Scene* scene = (Scene*)h;
-    Camera camera(*cam);
+// render_driver.cpp:144-190 + tracer.cpp:6-37: every task rendered by a pool of workers; results[i] holds task i's own-pixel
+// sums (row-major inside the tile) and its splats in RenderPixel order.  Shared by orc_render_round and orc_render_round_split.
+static void render_tiles(Scene* scene, const Camera& camera, const rgk_params* prm, const rgk_tile* tiles, uint32_t n_tiles, int n_threads,
+                         std::vector<TileResult>& results, std::vector<Counters>& cnts, bool exhaustive = false) {
     if (n_threads <= 0) n_threads = std::max(1u, std::thread::hardware_concurrency() - 1); // render_driver.cpp:205-206
-    std::vector<TileResult> results(n_tiles);
-    std::vector<Counters> cnts(n_threads);
+    results.assign(n_tiles, TileResult());
+    cnts.assign(n_threads, Counters());
     std::atomic<uint32_t> next(0);
     auto worker = [&](int tid) {
         Counters& cnt = cnts[tid];
@@ -1544,7 +1553,7 @@ int orc_render_round(void* h, const rgk_camera* cam, const rgk_params* prm, cons
             if (i >= n_tiles) break;
             const rgk_tile& task = tiles[i];
             PathTracer rt{*scene, camera, prm->xres, prm->yres, prm->multisample, prm->bumpmap_scale, prm->clamp,
-                          prm->russian, prm->depth, prm->reverse, task.seed, prm->sampler, cnt};
+                          prm->russian, prm->depth, prm->reverse, task.seed, prm->sampler, cnt, exhaustive};
             TileResult& tr = results[i];
             tr.px.reserve((task.x1 - task.x0) * (task.y1 - task.y0));
             for (unsigned y = task.y0; y < task.y1; y++)
@@ -1559,6 +1568,27 @@ int orc_render_round(void* h, const rgk_camera* cam, const rgk_params* prm, cons
     for (int t = 1; t < n_threads; t++) th.emplace_back(worker, t);
     worker(0);
     for (auto& t : th) t.join();
+}
+
+static void sum_counters(const std::vector<Counters>& cnts, uint64_t paths, rgk_counters* out_cnt) {
+    if (!out_cnt) return;
+    std::memset(out_cnt, 0, sizeof(*out_cnt));
+    out_cnt->paths = paths;
+    for (auto& c : cnts) {
+        out_cnt->path_rays += c.path_rays; out_cnt->shadow_rays += c.shadow_rays;
+        out_cnt->node_visits += c.closest.nodes; out_cnt->tri_tests += c.closest.tris;
+        out_cnt->shadow_node_visits += c.shadow.nodes; out_cnt->shadow_tri_tests += c.shadow.tris;
+    }
+}
+
+// + texture.cpp:342-347,403-412 (AddPixel)
+int orc_render_round(void* h, const rgk_camera* cam, const rgk_params* prm, const rgk_tile* tiles, uint32_t n_tiles,
+                     float* accum_rgb, uint32_t* accum_count, rgk_counters* out_cnt, int n_threads) {
+    Scene* scene = (Scene*)h;
+    Camera camera(*cam);
+    std::vector<TileResult> results;
+    std::vector<Counters> cnts;
+    render_tiles(scene, camera, prm, tiles, n_tiles, n_threads, results, cnts);
     // merge in task order (deterministic; the reference merges in completion order)
     uint64_t paths = 0;
     for (uint32_t i = 0; i < n_tiles; i++) {
@@ -1578,15 +1608,57 @@ int orc_render_round(void* h, const rgk_camera* cam, const rgk_params* prm, cons
             accum_rgb[3 * p + 0] += s.r.r; accum_rgb[3 * p + 1] += s.r.g; accum_rgb[3 * p + 2] += s.r.b;
         }
     }
-    if (out_cnt) {
-        std::memset(out_cnt, 0, sizeof(*out_cnt));
-        out_cnt->paths = paths;
-        for (auto& c : cnts) {
-            out_cnt->path_rays += c.path_rays; out_cnt->shadow_rays += c.shadow_rays;
-            out_cnt->node_visits += c.closest.nodes; out_cnt->tri_tests += c.closest.tris;
-            out_cnt->shadow_node_visits += c.shadow.nodes; out_cnt->shadow_tri_tests += c.shadow.tris;
+    sum_counters(cnts, paths, out_cnt);
+    return 0;
+}
+
+// The same round with its terms kept apart (tests/bdpt_ref.py): main_rgb[yres][xres][3] float32 += the own-pixel sums
+// (PixelRenderResult::main_pixel, exactly the values orc_render_round adds), accum_count as orc_render_round; per pixel the
+// splats that land on it: splat_sum / splat_abs [yres][xres][3] float64 += their sum / the sum of their absolute values,
+// splat_n [yres][xres] uint32 += how many.  splat_list (optional, room for splat_cap records {x, y, task, r, g, b}): the
+// splats in the order orc_render_round adds them (task order; inside a task behind the task's own pixels); *n_splats = how
+// many the round made, whatever the room.  lv_stats (optional, 17 words): light sub-path vertices by material kind
+// [0..15] and, [16], the paths whose light sub-path has no vertex on a surface.  exhaustive != 0: every ray of the round is
+// answered by Scene::FindExhaustive instead of the kd-tree -- the walkers' stated rule without a tree, which the GPU's
+// traversal is pinned to bit for bit; the two differ where a ray meets a triangle inside the kd-tree's epsilon band.
+struct orc_splat { int32_t x, y; uint32_t task; float r, g, b; };
+int orc_render_round_split(void* h, const rgk_camera* cam, const rgk_params* prm, const rgk_tile* tiles, uint32_t n_tiles,
+                           float* main_rgb, double* splat_sum, double* splat_abs, uint32_t* splat_n, uint32_t* accum_count,
+                           orc_splat* splat_list, uint64_t splat_cap, uint64_t* n_splats, uint64_t* lv_stats,
+                           rgk_counters* out_cnt, int n_threads, int exhaustive) {
+    Scene* scene = (Scene*)h;
+    Camera camera(*cam);
+    std::vector<TileResult> results;
+    std::vector<Counters> cnts;
+    render_tiles(scene, camera, prm, tiles, n_tiles, n_threads, results, cnts, exhaustive != 0);
+    uint64_t paths = 0, ns = 0;
+    for (uint32_t i = 0; i < n_tiles; i++) {
+        const rgk_tile& task = tiles[i];
+        size_t k = 0;
+        for (unsigned y = task.y0; y < task.y1; y++)
+            for (unsigned x = task.x0; x < task.x1; x++, k++) {
+                size_t p = (size_t)y * prm->xres + x;
+                main_rgb[3 * p + 0] += results[i].px[k].r;
+                main_rgb[3 * p + 1] += results[i].px[k].g;
+                main_rgb[3 * p + 2] += results[i].px[k].b;
+                if (accum_count) accum_count[p] += prm->multisample;
+                paths += prm->multisample;
+            }
+        for (auto& s : results[i].splats) {
+            size_t p = (size_t)s.y * prm->xres + s.x;
+            const float v[3] = {s.r.r, s.r.g, s.r.b};
+            for (int c = 0; c < 3; c++) { splat_sum[3 * p + c] += (double)v[c]; splat_abs[3 * p + c] += std::fabs((double)v[c]); }
+            splat_n[p]++;
+            if (splat_list && ns < splat_cap) splat_list[ns] = orc_splat{s.x, s.y, i, v[0], v[1], v[2]};
+            ns++;
         }
     }
+    if (n_splats) *n_splats = ns;
+    if (lv_stats) {
+        for (int k = 0; k < 17; k++) lv_stats[k] = 0;
+        for (auto& c : cnts) { for (int k = 0; k < 16; k++) lv_stats[k] += c.lv_kind[k]; lv_stats[16] += c.lv_none; }
+    }
+    sum_counters(cnts, paths, out_cnt);
     return 0;
 }
 

@@ -37,6 +37,9 @@ def lib():
                                              C.c_uint32, C.c_uint32, _p(capi.Tile), _p(C.c_uint32)]
         L.orc_render_round.argtypes = [C.c_void_p, _p(capi.Camera), _p(capi.Params), _p(capi.Tile),
                                        C.c_uint32, C.c_void_p, C.c_void_p, _p(capi.Counters), C.c_int]
+        L.orc_render_round_split.argtypes = [C.c_void_p, _p(capi.Camera), _p(capi.Params), _p(capi.Tile), C.c_uint32,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                             _p(C.c_uint64), C.c_void_p, _p(capi.Counters), C.c_int, C.c_int]
         L.orc_trace_closest.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                         _p(capi.Counters)]
         L.orc_trace_visibility.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -70,6 +73,13 @@ def generate_task_list(xres, yres, seedstart=42, seedcount_base=0, tile_size=32,
     return tiles
 
 
+SPLAT_DTYPE = np.dtype([("x", "i4"), ("y", "i4"), ("task", "u4"), ("rgb", "f4", (3,))])
+
+
+class RoundSplit:
+    """What OracleScene.render_round_split returns."""
+
+
 class OracleScene:
     def __init__(self, desc):
         self.L = lib()
@@ -96,6 +106,40 @@ class OracleScene:
         self.L.orc_render_round(self.h, C.byref(camera), C.byref(params), tiles, n,
                                 accum.ctypes.data, count.ctypes.data, C.byref(cnt), n_threads)
         return accum, count, cnt
+
+    def render_round_split(self, camera, params, tiles, want_list=False, exhaustive=False, n_threads=0):
+        """render_round's round with its terms kept apart (tests/bdpt_ref.py).  Returns a RoundSplit: `main` float32 (yres, xres, 3),
+        the own-pixel sums exactly as render_round adds them; `splat_sum` / `splat_abs` float64 (yres, xres, 3), the sum of the
+        splats landing on each pixel and of their absolute values; `splat_n` uint32 (yres, xres), how many landed; `count`;
+        `counters`; `lv_kind` (16,) light sub-path vertices by material kind and `lv_none`, the paths whose light sub-path has no
+        vertex on a surface; with want_list `splats`, records (x, y, task, rgb) in the order render_round adds them.
+        exhaustive: every ray answered by testing every triangle under the walkers' stated rule (trace_closest_exhaustive /
+        visibility_exhaustive) instead of the kd-tree: the round the GPU's traversal is pinned to, free of the kd-tree's own
+        epsilon-band decisions.  Small scenes only: the cost is rays x triangles."""
+        shape = (params.yres, params.xres)
+        r = RoundSplit()
+        r.main = np.zeros(shape + (3,), np.float32)
+        r.splat_sum, r.splat_abs = np.zeros(shape + (3,), np.float64), np.zeros(shape + (3,), np.float64)
+        r.splat_n, r.count = np.zeros(shape, np.uint32), np.zeros(shape, np.uint32)
+        r.counters = capi.Counters()
+        stats = np.zeros(17, np.uint64)
+        n, lst = C.c_uint64(0), None
+        for _ in range(2 if want_list else 1):          # the second time with room for the list
+            if want_list and n.value:
+                lst = np.zeros(n.value, SPLAT_DTYPE)
+                for a in (r.main, r.splat_sum, r.splat_abs, r.splat_n, r.count):
+                    a[...] = 0
+            self.L.orc_render_round_split(self.h, C.byref(camera), C.byref(params), tiles, len(tiles), r.main.ctypes.data,
+                                          r.splat_sum.ctypes.data, r.splat_abs.ctypes.data, r.splat_n.ctypes.data, r.count.ctypes.data,
+                                          None if lst is None else lst.ctypes.data, 0 if lst is None else len(lst), C.byref(n),
+                                          stats.ctypes.data, C.byref(r.counters), n_threads, int(exhaustive))
+            if not n.value:
+                break
+        r.n_splats = int(n.value)
+        r.lv_kind, r.lv_none = stats[:16].astype(np.int64), int(stats[16])
+        if want_list:
+            r.splats = lst if lst is not None else np.zeros(0, SPLAT_DTYPE)
+        return r
 
     def trace_closest(self, rays, ignore=None):
         rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)

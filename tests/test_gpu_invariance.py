@@ -157,26 +157,41 @@ def test_counting_and_timing_flags_do_not_change_the_image(rd, oracle, shape):
 
 # ----------------------------------------------------------------------- bidirectional
 def test_bidirectional_small_batches(rd, oracle):
-    """reverse = 2 with passes split over pixels and samples: splats are float atomics (any pixel, any order), so the image is
-    held to the bar of the dragon halves test (relative L2 1e-5); counts and ray counts stay exact."""
+    """reverse = 2 with passes split over pixels and samples: splats are float atomics (any pixel, any order), so every plan is
+    held per pixel to the oracle's terms (tests/bdpt_ref.py; extra_terms = multisample, as for every plan that may split the
+    samples).  At 256 x 256 x 16 the kd-tree oracle itself differs from the GPU in two pixels WITHOUT reverse (epsilon-band ties:
+    5 of 2.5 M path rays), so against it the project's gate of 99.9 % of the pixels holds (measured: 3 outside of 65 536), and
+    against the oracle's round with every ray answered by exhaustive search -- the rule the traversal is pinned to -- no pixel is
+    outside and path_rays is exact; counts and ray counts stay exact between the plans."""
     from rgk_amd.workloads import Workload
+    import bdpt_ref as B
     wl = Workload("cornell-256", spp=16)
     prm = make_params(wl.xres, wl.yres, wl.multisample, 5, clamp=20.0, russian=0.7, reverse=2)
     tiles = rd.generate_task_list(wl.xres, wl.yres)
     a0, c0, k0 = render_fresh(rd, wl, prm, tiles)[0]
     o = oracle.OracleScene(wl.builder.to_desc())
+    split = o.render_round_split(wl.camera, prm, oracle.generate_task_list(wl.xres, wl.yres))
     ao, co, ko = o.render_round(wl.camera, prm, oracle.generate_task_list(wl.xres, wl.yres))
     rel_o = float(np.linalg.norm(a0 - ao) / np.linalg.norm(ao))
-    assert np.array_equal(c0, co) and rel_o <= 2e-3, rel_o                       # test_bidirectional_reverse_parity's bars
-    assert abs(int(k0.path_rays) - int(ko.path_rays)) <= 1e-3 * ko.path_rays
-    worst = 0.0
+    planes, s0 = B.check_split(a0, c0, split, extra_terms=wl.multisample)
+    assert np.array_equal(c0, co) and s0["outside"] <= 1e-3 * s0["pixels"] and s0["bad_values"] == 0, s0
+    assert abs(int(k0.path_rays) - int(ko.path_rays)) <= 1e-5 * ko.path_rays and k0.shadow_rays <= ko.shadow_rays, (k0.path_rays, ko.path_rays)
+    exact = o.render_round_split(wl.camera, prm, oracle.generate_task_list(wl.xres, wl.yres), exhaustive=True)
+    planes, sx = B.check_split(a0, c0, exact, extra_terms=wl.multisample)
+    assert sx["outside"] == 0 and sx["exact_n0"] == 1.0 and sx["bad_values"] == 0, sx
+    assert k0.path_rays == exact.counters.path_rays and k0.shadow_rays <= exact.counters.shadow_rays, (k0.path_rays, exact.counters.path_rays)
+    worst, worst_ratio = 0.0, sx["worst_ratio"]
     for batch in (20000, 300000):    # 20 000: ranges of 20 000 pixels x 16 single-sample passes; 300 000: 4 sample passes of 4
         a1, c1, k1 = render_fresh(rd, wl, prm, tiles, batch_paths=batch)[0]
         assert np.array_equal(c0, c1) and (k0.path_rays, k0.shadow_rays) == (k1.path_rays, k1.shadow_rays), batch
         rel = float(np.linalg.norm(a1 - a0) / np.linalg.norm(a0))
         worst = max(worst, rel)
-        assert rel <= 1e-5, (batch, rel)
-    record_parity("test_bidirectional_small_batches", rel_l2_vs_oracle=rel_o, rel_l2_small_batches=worst, size="256x256x16 reverse=2")
+        planes, s1 = B.check_split(a1, c1, exact, extra_terms=wl.multisample)
+        worst_ratio = max(worst_ratio, s1["worst_ratio"])
+        assert s1["outside"] == 0 and s1["exact_n0"] == 1.0 and s1["bad_values"] == 0, (batch, s1)
+    record_parity("test_bidirectional_small_batches", rel_l2_vs_oracle=rel_o, rel_l2_small_batches=worst, size="256x256x16 reverse=2",
+                  outside_vs_kd_oracle=s0["outside"], **{k: v for k, v in B.record_fields(sx).items() if k != "worst_err_over_bound"},
+                  worst_err_over_bound=worst_ratio)
 
 
 # ----------------------------------------------------------------------- tree builders
