@@ -221,6 +221,20 @@ int down(T* dst, const DevBuf<T>& b, size_t count) {
     return 0;
 }
 
+// Event `i` of the scene's pool, which grows on demand and goes with the scene.  A round and a post call never overlap on a scene
+// (prog_busy), so each call counts from 0.
+int scene_event(rgk_scene* s, size_t i, hipEvent_t& e) {
+    while (s->events.size() <= i) { hipEvent_t n; HIPCHK(hipEventCreate(&n)); s->events.push_back(n); }
+    e = s->events[i];
+    return 0;
+}
+
+// The frame sizes the kernels' 16-bit pixel coordinates can hold.
+int check_frame_size(uint32_t xres, uint32_t yres) {
+    if (xres == 0 || yres == 0 || xres > 65535 || yres > 65535) return fail(RGK_ERR_INVALID, "resolution out of range");
+    return RGK_OK;
+}
+
 // The eight traversal-stats words: closest nodes / triangles, shadow nodes / triangles, and the walker's occupancy counters.
 int read_stats(const rgk_scene* s, unsigned long long (&h)[8]) { return down(h, s->stats, 8); }
 
@@ -603,11 +617,7 @@ struct KernelLog {
     static bool closest(int k) { return k == RGK_K_TRACE_CAMERA || k == RGK_K_TRACE_CLOSEST || k == RGK_K_LIGHT_TRACE; }
     static bool shadow(int k) { return k == RGK_K_SHADOW_FIRST || k == RGK_K_SHADOW || k == RGK_K_SHADOW_JOBS || k == RGK_K_LIGHT_SPLAT; }
     static bool shade(int k) { return k == RGK_K_SHADE_FIRST || k == RGK_K_SHADE || k == RGK_K_CONNECT || k == RGK_K_LIGHT_SHADE; }
-    int event(hipEvent_t& e) {
-        if (ev_used == s->events.size()) { hipEvent_t n; HIPCHK(hipEventCreate(&n)); s->events.push_back(n); }
-        e = s->events[ev_used++];
-        return 0;
-    }
+    int event(hipEvent_t& e) { return scene_event(s, ev_used++, e); }
     template <class Launch>
     int run(int cls, Launch&& launch) {
         Ev ev{cls, nullptr, nullptr};
@@ -878,7 +888,7 @@ extern "C" {
 int rgk_render_round_device(rgk_scene* s, const rgk_camera* camera, const rgk_params* prm, const rgk_tile* tiles, uint32_t n_tiles,
                             float* d_accum_rgb, uint32_t* d_accum_count, rgk_counters* counters) {
     if (!s || !camera || !prm || (!tiles && n_tiles) || !d_accum_rgb || !d_accum_count) return fail(RGK_ERR_INVALID, "null argument");
-    if (prm->xres == 0 || prm->yres == 0 || prm->xres > 65535 || prm->yres > 65535) return fail(RGK_ERR_INVALID, "resolution out of range");
+    if (int rc = check_frame_size(prm->xres, prm->yres)) return rc;
     if (prm->multisample == 0) return fail(RGK_ERR_INVALID, "multisample must be >= 1");
     if (prm->depth > RGK_MAX_DEPTH) return fail(RGK_ERR_UNSUPPORTED, "recursion depth %u > %d", prm->depth, RGK_MAX_DEPTH);
     if (prm->reverse > 7) return fail(RGK_ERR_UNSUPPORTED, "reverse %u > 7 light sub-path vertices", prm->reverse);
@@ -962,23 +972,13 @@ int rgk_render_round(rgk_scene* s, const rgk_camera* camera, const rgk_params* p
     if (!s || !prm || !accum_rgb || !accum_count) return fail(RGK_ERR_INVALID, "null argument");
     HIPCHK(hipSetDevice(s->device));
     const size_t P = (size_t)prm->xres * prm->yres;
-    float* d_rgb = nullptr;
-    uint32_t* d_cnt = nullptr;
-    HIPCHK(hipMalloc((void**)&d_rgb, P * 3 * sizeof(float)));
-    hipError_t e = hipMalloc((void**)&d_cnt, P * sizeof(uint32_t));
-    if (e != hipSuccess) { (void)hipFree(d_rgb); return fail(RGK_ERR_OOM, "hipMalloc: %s", hipGetErrorString(e)); }
-    int rc = RGK_OK;
-    auto chk = [&](hipError_t x, const char* what) { if (x != hipSuccess && rc == RGK_OK) rc = fail(RGK_ERR_DEVICE, "%s: %s", what, hipGetErrorString(x)); };
-    chk(hipMemcpy(d_rgb, accum_rgb, P * 3 * sizeof(float), hipMemcpyHostToDevice), "upload accumulator");
-    chk(hipMemcpy(d_cnt, accum_count, P * sizeof(uint32_t), hipMemcpyHostToDevice), "upload counts");
-    if (rc == RGK_OK) rc = rgk_render_round_device(s, camera, prm, tiles, n_tiles, d_rgb, d_cnt, counters);
-    if (rc == RGK_OK) {
-        chk(hipMemcpy(accum_rgb, d_rgb, P * 3 * sizeof(float), hipMemcpyDeviceToHost), "download accumulator");
-        chk(hipMemcpy(accum_count, d_cnt, P * sizeof(uint32_t), hipMemcpyDeviceToHost), "download counts");
-    }
-    (void)hipFree(d_rgb);
-    (void)hipFree(d_cnt);
-    return rc;
+    DevBuf<float> d_rgb;
+    DevBuf<uint32_t> d_cnt;
+    int rc;
+    if ((rc = d_rgb.upload(accum_rgb, 3 * P)) || (rc = d_cnt.upload(accum_count, P))) return rc;
+    if ((rc = rgk_render_round_device(s, camera, prm, tiles, n_tiles, d_rgb.p, d_cnt.p, counters))) return rc;
+    if ((rc = down(accum_rgb, d_rgb, 3 * P)) || (rc = down(accum_count, d_cnt, P))) return rc;
+    return RGK_OK;
 }
 
 int rgk_trace_closest(rgk_scene* s, uint32_t n, const float* rays, const int32_t* ignore, rgk_hit* hits, rgk_counters* counters) {
@@ -1001,7 +1001,10 @@ int rgk_trace_closest(rgk_scene* s, uint32_t n, const float* rays, const int32_t
     rgk_launch_pack_rays(st, n, s->scratch_f.p, d_ign, s->rayA[0].p, s->rayB[0].p, s->nearfar.p);
     const RgkWalk w = {n, s->counters.p + RGK_CNT_QUEUE, s->counters.p + RGK_CNT_FETCH_T};
     hipEvent_t e0 = nullptr, e1 = nullptr; // kernel time of the traversal alone, for counters->ms_trace
-    if (counters) { HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1)); HIPCHK(hipEventRecord(e0, st)); }
+    if (counters) {
+        if ((rc = scene_event(s, 0, e0)) || (rc = scene_event(s, 1, e1))) return rc;
+        HIPCHK(hipEventRecord(e0, st));
+    }
     rgk_launch_trace_closest(st, s->dev, s->tcfg, false, s->rayA[0].p, s->rayB[0].p, s->nearfar.p, s->hit.p, w, s->stats.p);
     if (counters) {
         HIPCHK(hipEventRecord(e1, st));
@@ -1024,7 +1027,6 @@ int rgk_trace_closest(rgk_scene* s, uint32_t n, const float* rays, const int32_t
         float ms = 0.f;
         HIPCHK(hipEventElapsedTime(&ms, e0, e1));
         counters->ms_trace = ms; counters->n_trace_launches = 1;
-        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     }
     return RGK_OK;
 }
@@ -1141,36 +1143,49 @@ int rgk_sampler_eval(uint32_t n, const uint32_t* seed, const uint32_t* index, co
 
 // ------------------------------------------------------------------ feature buffers and the denoiser (kernels: rgk_post.hip)
 namespace {
-// HIP events around the launches of one feature pass / denoise call, when the scene's "time_post" switch is on.
+// HIP events (the scene's pool, from its first) around the launches of one post call, when the scene's "time_post" switch is on.
 struct PostTimer {
     rgk_scene* s;
-    bool on;
-    std::vector<hipEvent_t> ev;
-    PostTimer(rgk_scene* s_) : s(s_), on(s_->tune.time_post) {}
-    ~PostTimer() { for (auto e : ev) (void)hipEventDestroy(e); }
+    size_t n = 0; // marks so far
     int mark() { // between two launches
-        if (!on) return 0;
+        if (!s->tune.time_post) return 0;
         hipEvent_t e;
-        HIPCHK(hipEventCreate(&e));
-        ev.push_back(e);
+        if (int rc = scene_event(s, n, e)) return rc;
+        n++;
         HIPCHK(hipEventRecord(e, s->stream));
         return 0;
     }
-    int fold(std::vector<double>& out) { // after the stream has been waited for
+    int fold(std::vector<double>& out) const { // after the stream has been waited for
         out.clear();
-        for (size_t i = 0; on && i + 1 < ev.size(); i++) {
+        for (size_t i = 0; i + 1 < n; i++) {
             float ms = 0.f;
-            HIPCHK(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
+            HIPCHK(hipEventElapsedTime(&ms, s->events[i], s->events[i + 1]));
             out.push_back(ms);
         }
         return 0;
     }
 };
 
+// A post call once the entry's own argument checks have passed: refused while a round is in flight; the slot's old times go; with no
+// `work` to do that is all, and the device is not touched.  Else body(tm) -- the entry's allocations and its launches on the scene's
+// stream, tm.mark() between them -- then a wait for the stream, and the launch times go into the slot.
+template <class Body>
+int post_call(rgk_scene* s, const char* entry, PostSlot slot, bool work, Body&& body) {
+    if (s->prog_busy.load()) return fail(RGK_ERR_INVALID, "%s while a round is in flight on this scene", entry);
+    s->post_ms[slot].clear();
+    if (!work) return RGK_OK;
+    HIPCHK(hipSetDevice(s->device));
+    PostTimer tm{s};
+    if (int rc = body(tm)) return rc;
+    HIPCHK(hipStreamSynchronize(s->stream));
+    HIPCHK(hipGetLastError());
+    return tm.fold(s->post_ms[slot]);
+}
+
 // (every check before the scene or the device is touched; `toff`: tile_offsets)
 int check_aov_args(const rgk_scene* s, const rgk_camera* camera, const rgk_params* prm, const rgk_tile* tiles, uint32_t n_tiles, std::vector<uint32_t>& toff) {
     if (!s || !camera || !prm || (!tiles && n_tiles)) return fail(RGK_ERR_INVALID, "null argument");
-    if (prm->xres == 0 || prm->yres == 0 || prm->xres > 65535 || prm->yres > 65535) return fail(RGK_ERR_INVALID, "resolution out of range");
+    if (int rc = check_frame_size(prm->xres, prm->yres)) return rc;
     return tile_offsets(prm, tiles, n_tiles, "feature pass", toff);
 }
 // What both denoise entries check besides their own parameter ranges, without touching the scene.  The fixed-sigma filter has no
@@ -1180,7 +1195,7 @@ int check_denoise_args(const rgk_scene* s, uint32_t xres, uint32_t yres, const f
                        const float* out_rgb, const float* out_variance) {
     if (!s || !accum_rgb || !accum_count || !normal || !depth || !out_rgb) return fail(RGK_ERR_INVALID, "null argument");
     if (p.demodulate && !albedo) return fail(RGK_ERR_INVALID, "demodulate without an albedo plane");
-    if (xres == 0 || yres == 0 || xres > 65535 || yres > 65535) return fail(RGK_ERR_INVALID, "resolution out of range");
+    if (int rc = check_frame_size(xres, yres)) return rc;
     if (p.iterations > 16 || p.normal_power_log2 > 16) return fail(RGK_ERR_INVALID, "iterations and normal_power_log2 must be <= 16");
     const void* ins[] = {accum_rgb, accum_count, half_rgb, half_count, albedo, normal, depth};
     for (const void* in : ins)
@@ -1195,36 +1210,30 @@ int denoise(rgk_scene* s, const char* entry, PostSlot slot, uint32_t xres, uint3
             float* out_rgb, float* out_variance) {
     int rc;
     if ((rc = check_denoise_args(s, xres, yres, accum_rgb, accum_count, half_rgb, half_count, albedo, normal, depth, p, out_rgb, out_variance))) return rc;
-    if (s->prog_busy.load()) return fail(RGK_ERR_INVALID, "%s while a round is in flight on this scene", entry);
-    HIPCHK(hipSetDevice(s->device));
-    const size_t P = (size_t)xres * yres;
-    const uint32_t it = p.iterations, demod = (it && p.demodulate) ? 1u : 0u; // no iteration: out = c, variance = v, nothing to demodulate for
-    const RgkDnMode mode = half_rgb ? RGK_DN_VARIANCE_GUIDED : RGK_DN_FIXED_SIGMA;
-    if ((rc = s->dn_col[0].alloc(P)) || (it && ((rc = s->dn_col[1].alloc(P)) || (rc = s->dn_guide.alloc(P))))) return rc;
-    hipStream_t st = s->stream;
-    PostTimer tm(s);
-    s->post_ms[slot].clear();
-    uint32_t cur = 0; // the plane that holds the current image
-    const auto filter = [&](RgkDnMode m, uint32_t step, float c) {
-        rgk_launch_dn_atrous(st, m, xres, yres, step, c, p.sigma_depth, p.normal_power_log2, s->dn_guide.p, s->dn_col[cur].p, s->dn_col[cur ^ 1u].p);
-        cur ^= 1u;
-        return tm.mark();
-    };
-    if ((rc = tm.mark())) return rc;
-    rgk_launch_dn_prepare(st, P, accum_rgb, accum_count, half_rgb, half_count, albedo, normal, depth, demod, p.albedo_floor, s->dn_col[0].p, it ? s->dn_guide.p : nullptr);
-    if ((rc = tm.mark())) return rc;
-    if (it && mode == RGK_DN_VARIANCE_GUIDED && (rc = filter(RGK_DN_VARIANCE_MEAN, 1u, 0.0f))) return rc;
-    for (uint32_t i = 0; i < it; i++)
-        if ((rc = filter(mode, 1u << i, wc[i]))) return rc;
-    rgk_launch_dn_finish(st, P, s->dn_col[cur].p, albedo, demod, p.albedo_floor, out_rgb);
-    if ((rc = tm.mark())) return rc;
-    if (out_variance) {
-        rgk_launch_nz_finish(st, P, s->dn_col[cur].p, out_variance);
+    return post_call(s, entry, slot, true, [&](PostTimer& tm) -> int {
+        const size_t P = (size_t)xres * yres;
+        const uint32_t it = p.iterations, demod = (it && p.demodulate) ? 1u : 0u; // no iteration: out = c, variance = v, nothing to demodulate for
+        const RgkDnMode mode = half_rgb ? RGK_DN_VARIANCE_GUIDED : RGK_DN_FIXED_SIGMA;
+        if ((rc = s->dn_col[0].alloc(P)) || (it && ((rc = s->dn_col[1].alloc(P)) || (rc = s->dn_guide.alloc(P))))) return rc;
+        hipStream_t st = s->stream;
+        uint32_t cur = 0; // the plane that holds the current image
+        const auto filter = [&](RgkDnMode m, uint32_t step, float c) {
+            rgk_launch_dn_atrous(st, m, xres, yres, step, c, p.sigma_depth, p.normal_power_log2, s->dn_guide.p, s->dn_col[cur].p, s->dn_col[cur ^ 1u].p);
+            cur ^= 1u;
+            return tm.mark();
+        };
         if ((rc = tm.mark())) return rc;
-    }
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipGetLastError());
-    return tm.fold(s->post_ms[slot]);
+        rgk_launch_dn_prepare(st, P, accum_rgb, accum_count, half_rgb, half_count, albedo, normal, depth, demod, p.albedo_floor, s->dn_col[0].p, it ? s->dn_guide.p : nullptr);
+        if ((rc = tm.mark())) return rc;
+        if (it && mode == RGK_DN_VARIANCE_GUIDED && (rc = filter(RGK_DN_VARIANCE_MEAN, 1u, 0.0f))) return rc;
+        for (uint32_t i = 0; i < it; i++)
+            if ((rc = filter(mode, 1u << i, wc[i]))) return rc;
+        rgk_launch_dn_finish(st, P, s->dn_col[cur].p, albedo, demod, p.albedo_floor, out_rgb);
+        if ((rc = tm.mark())) return rc;
+        if (!out_variance) return 0;
+        rgk_launch_nz_finish(st, P, s->dn_col[cur].p, out_variance);
+        return tm.mark();
+    });
 }
 } // namespace
 
@@ -1235,31 +1244,25 @@ int rgk_render_aov_device(rgk_scene* s, const rgk_camera* camera, const rgk_para
     int rc;
     std::vector<uint32_t> toff; // (read by a queued copy: lives until the stream has been waited for)
     if ((rc = check_aov_args(s, camera, prm, tiles, n_tiles, toff))) return rc;
-    if (s->prog_busy.load()) return fail(RGK_ERR_INVALID, "rgk_render_aov_device while a round is in flight on this scene");
     const uint32_t n = toff[n_tiles];
-    s->post_ms[POST_AOV].clear();
-    if (n == 0) return RGK_OK;
-    HIPCHK(hipSetDevice(s->device));
-    // The round's own buffers: its pixel list (rebuilt by every round before it is read), two ray planes and the hit plane of
-    // the workspace (written by every pass before they are read).  The frame's cached lists -- entry nodes, their caps, the
-    // light-side entries -- are neither read nor written here, so the rounds of a frame compute the same with or without this call.
-    if ((rc = ensure_workspace(s, n))) return rc;
-    hipStream_t st = s->stream;
-    PostTimer tm(s);
-    DevCamera cam;
-    make_camera(camera, cam);
-    cam.lens_size = 0.0f; // every feature ray leaves from the camera's origin
-    if ((rc = tm.mark()) || (rc = queue_pixel_list(s, tiles, n_tiles, toff))) return rc;
-    rgk_launch_init_counters(st, s->counters.p, n);
-    rgk_launch_aov_raygen(st, cam, prm->xres, prm->yres, s->pix_xy.p, n, s->rayA[0].p, s->rayB[0].p);
-    if ((rc = tm.mark())) return rc;
-    rgk_launch_trace_closest(st, s->dev, s->tcfg, false, s->rayA[0].p, s->rayB[0].p, nullptr, s->hit.p, {n, s->counters.p + RGK_CNT_QUEUE, s->counters.p + RGK_CNT_FETCH_T}, s->stats.p);
-    if ((rc = tm.mark())) return rc;
-    rgk_launch_aov_gather(st, s->dev, prm->bumpmap_scale, prm->xres, s->pix_xy.p, n, s->rayA[0].p, s->rayB[0].p, s->hit.p, d_albedo, d_normal, d_depth, d_tri);
-    if ((rc = tm.mark())) return rc;
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipGetLastError());
-    return tm.fold(s->post_ms[POST_AOV]);
+    return post_call(s, "rgk_render_aov_device", POST_AOV, n != 0, [&](PostTimer& tm) -> int {
+        // The round's own buffers: its pixel list (rebuilt by every round before it is read), two ray planes and the hit plane of
+        // the workspace (written by every pass before they are read).  The frame's cached lists -- entry nodes, their caps, the
+        // light-side entries -- are neither read nor written here, so the rounds of a frame compute the same with or without this call.
+        if ((rc = ensure_workspace(s, n))) return rc;
+        hipStream_t st = s->stream;
+        DevCamera cam;
+        make_camera(camera, cam);
+        cam.lens_size = 0.0f; // every feature ray leaves from the camera's origin
+        if ((rc = tm.mark()) || (rc = queue_pixel_list(s, tiles, n_tiles, toff))) return rc;
+        rgk_launch_init_counters(st, s->counters.p, n);
+        rgk_launch_aov_raygen(st, cam, prm->xres, prm->yres, s->pix_xy.p, n, s->rayA[0].p, s->rayB[0].p);
+        if ((rc = tm.mark())) return rc;
+        rgk_launch_trace_closest(st, s->dev, s->tcfg, false, s->rayA[0].p, s->rayB[0].p, nullptr, s->hit.p, {n, s->counters.p + RGK_CNT_QUEUE, s->counters.p + RGK_CNT_FETCH_T}, s->stats.p);
+        if ((rc = tm.mark())) return rc;
+        rgk_launch_aov_gather(st, s->dev, prm->bumpmap_scale, prm->xres, s->pix_xy.p, n, s->rayA[0].p, s->rayB[0].p, s->hit.p, d_albedo, d_normal, d_depth, d_tri);
+        return tm.mark();
+    });
 }
 
 int rgk_render_aov(rgk_scene* s, const rgk_camera* camera, const rgk_params* prm, const rgk_tile* tiles, uint32_t n_tiles, float* albedo, float* normal,
@@ -1297,26 +1300,19 @@ int rgk_noise_estimate_device(rgk_scene* s, uint32_t xres, uint32_t yres, uint32
                               const float* d_half_rgb, const uint32_t* d_half_count, rgk_noise_tile* tiles, float* d_variance) {
     // (every check before the scene or the device is touched)
     if (!s || !d_accum_rgb || !d_accum_count || !d_half_rgb || !d_half_count || !tiles) return fail(RGK_ERR_INVALID, "null argument");
-    if (xres == 0 || yres == 0 || xres > 65535 || yres > 65535) return fail(RGK_ERR_INVALID, "resolution out of range");
+    if (int rc = check_frame_size(xres, yres)) return rc;
     if (tile_size == 0) return fail(RGK_ERR_INVALID, "tile_size must be >= 1");
     if (d_variance && (d_variance == d_accum_rgb || d_variance == d_half_rgb || (const void*)d_variance == d_accum_count || (const void*)d_variance == d_half_count))
         return fail(RGK_ERR_INVALID, "variance must not be one of the inputs");
     if (d_half_rgb == d_accum_rgb || d_half_count == d_accum_count) return fail(RGK_ERR_INVALID, "the half-buffer must not be the accumulator");
-    if (s->prog_busy.load()) return fail(RGK_ERR_INVALID, "rgk_noise_estimate_device while a round is in flight on this scene");
-    HIPCHK(hipSetDevice(s->device));
     const RgkGrid2 g = rgk_nz_tile_grid(xres, yres, tile_size);
-    int rc;
-    if ((rc = s->nz_tiles.alloc(g.count()))) return rc;
-    hipStream_t st = s->stream;
-    PostTimer tm(s);
-    s->post_ms[POST_NOISE].clear();
-    if ((rc = tm.mark())) return rc;
-    rgk_launch_nz_tile_sums(st, xres, yres, tile_size, d_accum_rgb, d_accum_count, d_half_rgb, d_half_count, s->nz_tiles.p, d_variance);
-    if ((rc = tm.mark())) return rc;
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipGetLastError());
-    if ((rc = down(tiles, s->nz_tiles, g.count()))) return rc;
-    return tm.fold(s->post_ms[POST_NOISE]);
+    const int rc = post_call(s, "rgk_noise_estimate_device", POST_NOISE, true, [&](PostTimer& tm) -> int {
+        int rc;
+        if ((rc = s->nz_tiles.alloc(g.count())) || (rc = tm.mark())) return rc;
+        rgk_launch_nz_tile_sums(s->stream, xres, yres, tile_size, d_accum_rgb, d_accum_count, d_half_rgb, d_half_count, s->nz_tiles.p, d_variance);
+        return tm.mark();
+    });
+    return rc ? rc : down(tiles, s->nz_tiles, g.count());
 }
 
 int rgk_denoise_variance_device(rgk_scene* s, uint32_t xres, uint32_t yres, const float* d_accum_rgb, const uint32_t* d_accum_count, const float* d_half_rgb,
@@ -1347,34 +1343,27 @@ int rgk_round_fold_device(rgk_scene* s, uint32_t xres, uint32_t yres, const rgk_
     // (every check before the scene or the device is touched)
     if (!s || (n_tiles && (!tiles || !to_half)) || !d_round_rgb || !d_round_count || !d_total_rgb || !d_total_count || !d_half_rgb || !d_half_count)
         return fail(RGK_ERR_INVALID, "null argument");
-    if (xres == 0 || yres == 0 || xres > 65535 || yres > 65535) return fail(RGK_ERR_INVALID, "resolution out of range");
+    if (int rc = check_frame_size(xres, yres)) return rc;
     const void* planes[6] = {d_round_rgb, d_round_count, d_total_rgb, d_total_count, d_half_rgb, d_half_count};
     for (int i = 0; i < 6; i++)
         for (int j = i + 1; j < 6; j++)
             if (planes[i] == planes[j]) return fail(RGK_ERR_INVALID, "the six planes must be six different buffers");
     uint32_t max_height = 0, bad = 0;
     if (const char* why = rgk_fold_check_tiles(tiles, n_tiles, xres, yres, max_height, bad)) return fail(RGK_ERR_INVALID, "round fold: %s (tile %u)", why, bad);
-    if (s->prog_busy.load()) return fail(RGK_ERR_INVALID, "rgk_round_fold_device while a round is in flight on this scene");
-    s->post_ms[POST_FOLD].clear();
-    if (n_tiles == 0) return RGK_OK;
-    HIPCHK(hipSetDevice(s->device));
-    int rc;
-    static_assert(sizeof(rgk_tile) == 5 * sizeof(uint32_t), "rgk_tile layout");
-    if ((rc = s->fold_buf.alloc((size_t)n_tiles * 5 + (n_tiles + 3u) / 4u))) return rc;
-    hipStream_t st = s->stream;
-    PostTimer tm(s);
-    if ((rc = tm.mark())) return rc;
-    // (queued copies of the caller's arrays: they are the caller's until this call returns, and it waits for the stream first)
-    uint8_t* d_flags = reinterpret_cast<uint8_t*>(s->fold_buf.p + (size_t)n_tiles * 5);
-    HIPCHK(hipMemcpyAsync(s->fold_buf.p, tiles, (size_t)n_tiles * sizeof(rgk_tile), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_flags, to_half, n_tiles, hipMemcpyHostToDevice, st));
-    if ((rc = tm.mark())) return rc;
-    rgk_launch_round_fold(st, xres, reinterpret_cast<const rgk_tile*>(s->fold_buf.p), d_flags, n_tiles, max_height, d_round_rgb, d_round_count, d_total_rgb,
-                          d_total_count, d_half_rgb, d_half_count);
-    if ((rc = tm.mark())) return rc;
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipGetLastError());
-    return tm.fold(s->post_ms[POST_FOLD]);
+    return post_call(s, "rgk_round_fold_device", POST_FOLD, n_tiles != 0, [&](PostTimer& tm) -> int {
+        int rc;
+        static_assert(sizeof(rgk_tile) == 5 * sizeof(uint32_t), "rgk_tile layout");
+        if ((rc = s->fold_buf.alloc((size_t)n_tiles * 5 + (n_tiles + 3u) / 4u)) || (rc = tm.mark())) return rc;
+        hipStream_t st = s->stream;
+        // (queued copies of the caller's arrays: they are the caller's until this call returns, and it waits for the stream first)
+        uint8_t* d_flags = reinterpret_cast<uint8_t*>(s->fold_buf.p + (size_t)n_tiles * 5);
+        HIPCHK(hipMemcpyAsync(s->fold_buf.p, tiles, (size_t)n_tiles * sizeof(rgk_tile), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_flags, to_half, n_tiles, hipMemcpyHostToDevice, st));
+        if ((rc = tm.mark())) return rc;
+        rgk_launch_round_fold(st, xres, reinterpret_cast<const rgk_tile*>(s->fold_buf.p), d_flags, n_tiles, max_height, d_round_rgb, d_round_count, d_total_rgb,
+                              d_total_count, d_half_rgb, d_half_count);
+        return tm.mark();
+    });
 }
 
 int rgk_scene_get_post_timing(const rgk_scene* s, uint32_t which, double* ms, uint32_t* n) {

@@ -14,6 +14,7 @@ reduce).  Seeds depend only on (round, tile index, pixel-in-tile): the image doe
 depend on the number of GPUs.
 """
 import ctypes as C
+import itertools
 import time
 
 import numpy as np
@@ -26,6 +27,13 @@ SEEDSTART = 42  # src/render_driver.cpp:222
 # minimises the summed relative L2 error of the CPU sweep in DESIGN.md ("Feature buffers and the a-trous denoiser";
 # tools/denoise_sweep.py reproduces it).
 DENOISE_SIGMA_K = 6.0
+# rgk_noise_tile: the per-tile sums of rgk_noise_estimate_device, which rgk_adapt_select reads
+NOISE_TILE_DTYPE = np.dtype([("sum_var", "f8"), ("sum_sq", "f8"), ("n_estimable", "u8")])
+
+
+def tile_grid(xres, yres, tile_size=TILE_SIZE):
+    """(tiles_y, tiles_x) of a frame; in the row-major order of noise()["tiles"] a tile is (y0 // tile_size) * tiles_x + x0 // tile_size."""
+    return -(-yres // tile_size), -(-xres // tile_size)
 
 
 def generate_task_list(xres, yres, seedstart=SEEDSTART, seedcount_base=0, tile_size=TILE_SIZE, mid=None):
@@ -146,12 +154,11 @@ class Scene:
     def noise_estimate_device(self, xres, yres, tile_size, d_accum_rgb, d_accum_count, d_half_rgb, d_half_count, d_variance=None):
         """rgk_noise_estimate_device: DEVICE pointers (ints) on the scene's GPU -> a (tiles_y, tiles_x) structured array with the
         fields sum_var, sum_sq (float64) and n_estimable (uint64)."""
-        ty, tx = -(-yres // tile_size), -(-xres // tile_size)
+        ty, tx = tile_grid(xres, yres, tile_size)
         tiles = (capi.NoiseTile * (ty * tx))()
         capi.check(self.lib, self.lib.rgk_noise_estimate_device(self.h, xres, yres, tile_size, d_accum_rgb, d_accum_count, d_half_rgb, d_half_count,
                                                                 tiles, d_variance))
-        dt = np.dtype([("sum_var", "f8"), ("sum_sq", "f8"), ("n_estimable", "u8")])
-        return np.frombuffer(tiles, dtype=dt).reshape(ty, tx).copy()
+        return np.frombuffer(tiles, dtype=NOISE_TILE_DTYPE).reshape(ty, tx).copy()
 
     def denoise_variance_device(self, xres, yres, d_accum_rgb, d_accum_count, d_half_rgb, d_half_count, d_albedo, d_normal, d_depth, params,
                                 d_out_rgb, d_out_variance=None):
@@ -186,10 +193,9 @@ def adapt_select(tiles, visits, xres, yres, params, tile_size=TILE_SIZE):
     noise_estimate_device; visits: rounds each tile was rendered in, same order; params: capi.AdaptParams.
     -> (live: (tiles_y, tiles_x) bool, n_live, done)."""
     lib = capi.load_product()
-    dt = np.dtype([("sum_var", "f8"), ("sum_sq", "f8"), ("n_estimable", "u8")])
-    st = np.ascontiguousarray(tiles, dtype=dt)
+    st = np.ascontiguousarray(tiles, dtype=NOISE_TILE_DTYPE)
     vis = np.ascontiguousarray(visits, dtype=np.uint32)
-    ty, tx = -(-yres // tile_size), -(-xres // tile_size)
+    ty, tx = tile_grid(xres, yres, tile_size)
     if st.size != ty * tx or vis.size != ty * tx:
         raise ValueError(f"{ty} x {tx} tiles expected, got {st.size} statistics and {vis.size} visit counts")
     live = np.zeros(ty * tx, np.uint8)
@@ -280,6 +286,39 @@ class EXRTexture:
         capi.check(lib, lib.rgk_output_write_exr(str(path).encode(), self.xsize, self.ysize, out.ctypes.data))
         return val.value
 
+    def save(self, path, device_index, tag, rounds_done, seedcount):
+        """rgk_accum_save: this accumulator with `tag`, the rounds done and the running task counter."""
+        lib = capi.load_product()
+        acc = C.c_void_p()
+        capi.check(lib, lib.rgk_accum_create(self.xsize, self.ysize, device_index, C.byref(acc)))
+        try:
+            a = np.ascontiguousarray(self.data.cpu().numpy(), dtype=np.float32)
+            c = np.ascontiguousarray(self.count.cpu().numpy()).view(np.uint32)
+            capi.check(lib, lib.rgk_accum_upload(acc, a.ctypes.data, c.ctypes.data))
+            capi.check(lib, lib.rgk_accum_set_tag(acc, tag))
+            capi.check(lib, lib.rgk_accum_save(acc, str(path).encode(), rounds_done, seedcount))
+        finally:
+            lib.rgk_accum_destroy(acc)
+
+    def load(self, path, device_index, tag):
+        """rgk_accum_load, which refuses a file with another tag -> (rounds_done, seedcount) of the saved run."""
+        import torch
+        lib = capi.load_product()
+        acc = C.c_void_p()
+        capi.check(lib, lib.rgk_accum_create(self.xsize, self.ysize, device_index, C.byref(acc)))
+        try:
+            rd_, sc_ = C.c_uint32(0), C.c_uint32(0)
+            capi.check(lib, lib.rgk_accum_set_tag(acc, tag))
+            capi.check(lib, lib.rgk_accum_load(acc, str(path).encode(), C.byref(rd_), C.byref(sc_)))
+            a = np.empty((self.ysize, self.xsize, 3), np.float32)
+            c = np.empty((self.ysize, self.xsize), np.uint32)
+            capi.check(lib, lib.rgk_accum_download(acc, a.ctypes.data, c.ctypes.data))
+        finally:
+            lib.rgk_accum_destroy(acc)
+        self.data.copy_(torch.from_numpy(a))
+        self.count.copy_(torch.from_numpy(c.view(np.int32)))
+        return rd_.value, sc_.value
+
 
 def missing_half_message(path):
     return (f"`{path}` has no half-buffer `{path}.half` beside it: it was written without noise tracking, and the noise estimate "
@@ -308,15 +347,15 @@ class RenderDriver:
         self.checkpoint_tag = 0  # digest of scene + camera + parameters (rgk_accum_set_tag); 0: checkpoints are not compared
         self.aov = None  # the frame's feature planes once render_aov() has made them
         # track_noise: rank 0 keeps a second accumulator, the sum of the ODD rounds (the second, fourth, ...), for the half-buffer
-        # noise estimate.  A single-rank driver then renders every round into the cleared per-round accumulator (the one a
-        # multi-rank driver has anyway) and adds it to total_ob itself: when a round is one pass -- one addition per pixel --
-        # total_ob has the bits it has without tracking (0 + s == s); a round of several passes adds its passes to 0 first
-        # instead of to the running total, which may differ in the last place.  Off: every code path is the untracked one.
+        # noise estimate.  A single-rank driver then renders every round into the per-round accumulator (the one a multi-rank
+        # driver has anyway) and one launch over the rendered tiles folds it into total_ob, into half_ob too on odd rounds, and
+        # clears it (rgk_round_fold_device): when a round is one pass -- one addition per pixel -- total_ob has the bits it has
+        # without tracking (0 + s == s); a round of several passes adds its passes to 0 first instead of to the running total,
+        # which may differ in the last place.  Off: every code path is the untracked one.
         self.track_noise = bool(track_noise)
         self.half_ob = EXRTexture(cfg.xres, cfg.yres, self.device) if self.track_noise and rank == 0 else None
         # adaptive (a capi.AdaptParams; its target is render_frame's until_noise): a round renders a subset of the tiles -- those
-        # rgk_adapt_select leaves live -- into the per-round accumulator, and one launch over those tiles folds it into total_ob and,
-        # on a TILE's odd visits, into half_ob (rgk_round_fold_device).  The per-round accumulator is all zero between rounds.
+        # rgk_adapt_select leaves live -- and the fold's odd rounds are each TILE's odd visits.
         # `visits`: rounds each tile was rendered in, in the row-major tile order of noise()["tiles"]; `task_tile`: for task i of
         # the centre-out list, its index there.  None: every code path is the one without it.
         self.adaptive = adaptive
@@ -330,7 +369,7 @@ class RenderDriver:
                 raise ValueError("adaptive tile sampling needs world_size == 1: the root adds a constant count per round")
             if int(adaptive.min_visits) < 2:
                 raise ValueError("adaptive min_visits must be >= 2: a tile is not estimable before its second visit")
-            tx = -(-cfg.xres // TILE_SIZE)
+            tx = tile_grid(cfg.xres, cfg.yres)[1]
             self.task_tile = np.array([(t.y0 // TILE_SIZE) * tx + t.x0 // TILE_SIZE for t in self.tasks], dtype=np.int64)
             self.visits = np.zeros(self.n_tasks, dtype=np.uint32)
 
@@ -346,69 +385,51 @@ class RenderDriver:
             raise ValueError("render_round(live=...) needs an adaptive driver")
         tiles = generate_task_list(self.cfg.xres, self.cfg.yres, SEEDSTART, self.seedcount)
         self.seedcount += len(tiles)  # `c = seedcount++` per task, render_driver.cpp:160
-        odd = self.rounds_done % 2 == 1
-        if self.adaptive is not None:
-            if self.round_ob is None:
-                self.round_ob = EXRTexture(self.cfg.xres, self.cfg.yres, self.device)  # zero, and every fold leaves it so
-            mask = np.ones(self.n_tasks, bool) if live is None else np.asarray(live, dtype=bool).reshape(-1)
+        which = self.task_tile if self.adaptive is not None else None  # adaptive: the rendered tiles' indices in `visits`
+        if self.world_size > 1:
+            tiles = shard_tiles(tiles, self.rank, self.world_size)
+        elif live is not None:
+            mask = np.asarray(live, dtype=bool).reshape(-1)
             if mask.shape != (self.n_tasks,):
                 raise ValueError(f"live: {self.n_tasks} tiles expected, got {mask.size}")
             idx = np.flatnonzero(mask[self.task_tile])  # centre-out order, as the whole list has it
-            mine = (capi.Tile * len(idx))(*[tiles[i] for i in idx])
+            tiles = (capi.Tile * len(idx))(*[tiles[i] for i in idx])
             which = self.task_tile[idx]
-            ob = self.round_ob
-            torch.cuda.current_stream(self.device).synchronize()
-            cnt = self.scene.render_round_device(self.camera, self.params, mine, ob.data.data_ptr(), ob.count.data_ptr())
-            self.scene.round_fold_device(self.cfg.xres, self.cfg.yres, mine, self.visits[which] & 1, ob.data.data_ptr(), ob.count.data_ptr(),
-                                         self.total_ob.data.data_ptr(), self.total_ob.count.data_ptr(), self.half_ob.data.data_ptr(),
-                                         self.half_ob.count.data_ptr())
-            self.visits[which] += 1
-        elif self.world_size == 1 and self.track_noise:
+        # The untracked single-rank round accumulates in place.  Every other one renders into the per-round accumulator, which is
+        # all zero between rounds: whatever takes a round out of it clears it.
+        ob = self.total_ob
+        if self.world_size > 1 or self.track_noise:
             if self.round_ob is None:
                 self.round_ob = EXRTexture(self.cfg.xres, self.cfg.yres, self.device)
-            else:
-                self.round_ob.data.zero_()
-                self.round_ob.count.zero_()
             ob = self.round_ob
-            torch.cuda.current_stream(self.device).synchronize()
-            cnt = self.scene.render_round_device(self.camera, self.params, tiles, ob.data.data_ptr(), ob.count.data_ptr())
-            for dst in (self.total_ob, self.half_ob) if odd else (self.total_ob,):
-                dst.data += ob.data
-                dst.count += ob.count
-        elif self.world_size == 1:
-            torch.cuda.current_stream(self.device).synchronize()
-            cnt = self.scene.render_round_device(self.camera, self.params, tiles, self.total_ob.data.data_ptr(), self.total_ob.count.data_ptr())
-        else:
-            mine = shard_tiles(tiles, self.rank, self.world_size)
-            if self.round_ob is None:  # one private accumulator per rank for the whole frame, cleared per round
-                self.round_ob = EXRTexture(self.cfg.xres, self.cfg.yres, self.device)
-            else:
-                self.round_ob.data.zero_()
-                self.round_ob.count.zero_()
-            ob = self.round_ob
-            torch.cuda.current_stream(self.device).synchronize()
-            cnt = self.scene.render_round_device(self.camera, self.params, mine, ob.data.data_ptr(), ob.count.data_ptr())
+        torch.cuda.current_stream(self.device).synchronize()
+        cnt = self.scene.render_round_device(self.camera, self.params, tiles, ob.data.data_ptr(), ob.count.data_ptr())
+        if self.world_size > 1:
             if reduce:
-                import torch.distributed as dist
-                if self.host_reduce:
-                    hd = ob.data.cpu()
-                    dist.reduce(hd, dst=0, op=dist.ReduceOp.SUM)
-                    if self.rank == 0:
-                        red = hd.to(self.total_ob.data.device)
-                        self.total_ob.data += red
-                else:
-                    dist.reduce(ob.data, dst=0, op=dist.ReduceOp.SUM)
-                    if self.rank == 0:
-                        red = ob.data
-                        self.total_ob.data += red
-                if self.rank == 0:
-                    self.total_ob.count += int(self.params.multisample)
-                    if self.track_noise and odd:
-                        self.half_ob.data += red
-                        self.half_ob.count += int(self.params.multisample)
+                self._reduce_round()
+            ob.data.zero_()
+            ob.count.zero_()
+        elif self.track_noise:
+            to_half = np.full(len(tiles), self.rounds_done & 1, np.uint8) if which is None else self.visits[which] & 1
+            self.scene.round_fold_device(self.cfg.xres, self.cfg.yres, tiles, to_half, ob.data.data_ptr(), ob.count.data_ptr(),
+                                         self.total_ob.data.data_ptr(), self.total_ob.count.data_ptr(), self.half_ob.data.data_ptr(),
+                                         self.half_ob.count.data_ptr())
+            if which is not None:
+                self.visits[which] += 1
         self.rounds_done += 1
         self.counters.append(cnt)
         return cnt
+
+    def _reduce_round(self):
+        """The ranks' per-round accumulators summed to rank 0, which adds the sum to total_ob, and to half_ob on odd rounds."""
+        import torch.distributed as dist
+        red = self.round_ob.data.cpu() if self.host_reduce else self.round_ob.data
+        dist.reduce(red, dst=0, op=dist.ReduceOp.SUM)
+        if self.rank == 0:
+            red = red.to(self.device)
+            for dst in (self.total_ob, self.half_ob) if self.track_noise and self.rounds_done & 1 else (self.total_ob,):
+                dst.data += red
+                dst.count += int(self.params.multisample)
 
     def render_aov(self):
         """First-hit feature planes of the whole frame, one ray per pixel through the pixel centre: a dict of torch tensors
@@ -496,22 +517,10 @@ class RenderDriver:
     def save_checkpoint(self, path):
         """Raw-accumulator checkpoint (rgk_accum_save): accumulator + rounds done + the running task counter.  With track_noise the
         half-buffer goes beside it as `<path>.half`, same format, same tag."""
-        self._save_ob(self.total_ob, path)
+        state = (self.scene.device, self.checkpoint_tag, self.rounds_done, self.seedcount)
+        self.total_ob.save(path, *state)
         if self.track_noise:
-            self._save_ob(self.half_ob, str(path) + ".half")
-
-    def _save_ob(self, ob, path):
-        lib = capi.load_product()
-        acc = C.c_void_p()
-        capi.check(lib, lib.rgk_accum_create(self.cfg.xres, self.cfg.yres, self.scene.device, C.byref(acc)))
-        try:
-            a = np.ascontiguousarray(ob.data.cpu().numpy(), dtype=np.float32)
-            c = np.ascontiguousarray(ob.count.cpu().numpy()).view(np.uint32)
-            capi.check(lib, lib.rgk_accum_upload(acc, a.ctypes.data, c.ctypes.data))
-            capi.check(lib, lib.rgk_accum_set_tag(acc, self.checkpoint_tag))
-            capi.check(lib, lib.rgk_accum_save(acc, str(path).encode(), self.rounds_done, self.seedcount))
-        finally:
-            lib.rgk_accum_destroy(acc)
+            self.half_ob.save(str(path) + ".half", *state)
 
     def load_checkpoint(self, path):
         """Resume: the next render_round continues the seed sequence where the saved run stopped.  With track_noise the
@@ -520,9 +529,9 @@ class RenderDriver:
         half = str(path) + ".half"
         if self.track_noise and not os.path.exists(half):
             raise RuntimeError(missing_half_message(path))
-        rounds_done, seedcount = self._load_ob(self.total_ob, path)
+        rounds_done, seedcount = self.total_ob.load(path, self.scene.device, self.checkpoint_tag)
         if self.track_noise:
-            if self._load_ob(self.half_ob, half) != (rounds_done, seedcount):
+            if self.half_ob.load(half, self.scene.device, self.checkpoint_tag) != (rounds_done, seedcount):
                 raise RuntimeError(f"`{half}` was not written together with `{path}`")
         self.rounds_done, self.seedcount = rounds_done, seedcount
         if self.adaptive is not None:
@@ -551,45 +560,16 @@ class RenderDriver:
             raise ValueError("adapt_select needs an adaptive driver and two rounds")
         return adapt_select(nz["tiles"], self.visits, self.cfg.xres, self.cfg.yres, capi.AdaptParams(target, self.adaptive.min_visits))
 
-    def _load_ob(self, ob, path):
-        import torch
-        lib = capi.load_product()
-        acc = C.c_void_p()
-        capi.check(lib, lib.rgk_accum_create(self.cfg.xres, self.cfg.yres, self.scene.device, C.byref(acc)))
-        try:
-            rd_, sc_ = C.c_uint32(0), C.c_uint32(0)
-            capi.check(lib, lib.rgk_accum_set_tag(acc, self.checkpoint_tag))
-            capi.check(lib, lib.rgk_accum_load(acc, str(path).encode(), C.byref(rd_), C.byref(sc_)))
-            a = np.empty((self.cfg.yres, self.cfg.xres, 3), np.float32)
-            c = np.empty((self.cfg.yres, self.cfg.xres), np.uint32)
-            capi.check(lib, lib.rgk_accum_download(acc, a.ctypes.data, c.ctypes.data))
-        finally:
-            lib.rgk_accum_destroy(acc)
-        ob.data.copy_(torch.from_numpy(a))
-        ob.count.copy_(torch.from_numpy(c.view(np.int32)))
-        return rd_.value, sc_.value
-
-    def _noise_reached(self, until_noise, nz):
-        """After a round: has the frame's relative noise (nz: rank 0's noise()) come down to `until_noise`?  Rank 0's decision,
-        broadcast as in _continue_timed."""
-        stop = nz is not None and nz["rel"] <= until_noise
+    def _root_decides(self, yes):
+        """Rank 0's yes or no, on every rank.  With several ranks a decision to stop or to go on is rank 0's, broadcast to all:
+        ranks deciding by their own clocks or estimates could disagree and leave a reduce unmatched."""
         if self.world_size > 1:
             import torch
             import torch.distributed as dist
-            flag = torch.tensor([1 if stop else 0], dtype=torch.int32, device="cpu" if self.host_reduce else self.device)
+            flag = torch.tensor([1 if yes else 0], dtype=torch.int32, device="cpu" if self.host_reduce else self.device)
             dist.broadcast(flag, src=0)
-            stop = bool(flag.item())
-        return stop
-
-    def _continue_timed(self, t0, minutes):
-        go = (self.clock() - t0) / 60.0 < minutes
-        if self.world_size > 1:
-            import torch
-            import torch.distributed as dist
-            flag = torch.tensor([1 if go else 0], dtype=torch.int32, device="cpu" if self.host_reduce else self.device)
-            dist.broadcast(flag, src=0)
-            go = bool(flag.item())
-        return go
+            yes = bool(flag.item())
+        return yes
 
     def render_frame(self, rounds=None, minutes=None, output_file=None, checkpoint=None, aov_files=None, denoised_file=None,
                      until_noise=None, noise_file=None, on_noise=None):
@@ -610,19 +590,21 @@ class RenderDriver:
         minutes = self.cfg.render_minutes if minutes is None else minutes
         t0 = self.clock()
         adapting = self.adaptive is not None and until_noise is not None
-        live = [None]  # the next round's tiles (None: all)
+        live = None  # the next round's tiles (None: all)
         if aov_files and self.rank == 0:
             a = self.render_aov()
             for name, path in aov_files.items():
                 plane = a[name] if a[name].dim() == 3 else a[name].unsqueeze(-1).expand(-1, -1, 3)
                 write_exr(path, plane.cpu().numpy())
         if adapting and self.rounds_done >= 2:  # resumed
-            live[0], _, done = self.adapt_select(until_noise)
+            live, _, done = self.adapt_select(until_noise)
             if done:
                 return self.total_ob
-
-        def one():
-            self.render_round(live=live[0])
+        # Rounds mode (render_driver.cpp:229-235), or Timed mode (:237-247): whether another round starts is asked before each
+        for _ in range(rounds) if minutes is None else itertools.repeat(None):
+            if minutes is not None and not self._root_decides((self.clock() - t0) / 60.0 < minutes):
+                break
+            self.render_round(live=live)
             if output_file and self.rank == 0:
                 val = self.total_ob.write(output_file, getattr(self.cfg, "output_scale", -1.0))
                 if self.track_noise and self.rounds_done >= 2 and (denoised_file or noise_file):
@@ -637,21 +619,14 @@ class RenderDriver:
                 self.save_checkpoint(checkpoint)
             nz = self.noise() if on_noise or until_noise is not None else None
             if adapting and nz is not None:
-                live[0], n_live, done = self.adapt_select(until_noise, nz)
+                live, n_live, done = self.adapt_select(until_noise, nz)
                 if on_noise:
                     on_noise(self.rounds_done, nz["rel"], n_live)
-                return done
-            if on_noise and nz is not None:
-                on_noise(self.rounds_done, nz["rel"])
-            return until_noise is not None and self._noise_reached(until_noise, nz)
-        if minutes is None:
-            for _ in range(rounds):
-                if one():
-                    break
-        else:
-            # Timed mode (render_driver.cpp:237-247).  With several ranks the decision to start another round is rank 0's,
-            # broadcast to all: ranks reading their own clocks could disagree and leave a reduce unmatched.
-            while self._continue_timed(t0, minutes):
-                if one():
-                    break
+            else:
+                if on_noise and nz is not None:
+                    on_noise(self.rounds_done, nz["rel"])
+                # (nz is rank 0's: the other ranks have none)
+                done = until_noise is not None and self._root_decides(nz is not None and nz["rel"] <= until_noise)
+            if done:
+                break
         return self.total_ob

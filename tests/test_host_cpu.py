@@ -408,7 +408,7 @@ def _rank_main(rank, world, port, q, case):
     real_tl = rd.generate_task_list
     rd.generate_task_list = lambda *a, **k: O.generate_task_list(*a, **k)   # host-only twin (needs no HIP runtime)
     torch.cuda.current_stream = lambda dev=None: type("S", (), {"synchronize": lambda self: None})()
-    drv = rd.RenderDriver(HostScene(), Cfg, wl.camera, rank=rank, world_size=world, device=torch.device("cpu"))
+    drv = rd.RenderDriver(HostScene(), Cfg, wl.camera, rank=rank, world_size=world, device=torch.device("cpu"), track_noise=case == "tracked")
     if case == "timed":
         # skewed clocks: rank 0's clock allows exactly two rounds, every other rank's says the time was up before the first.
         # The decision is rank 0's (broadcast), so all ranks run two rounds and every reduce is matched.
@@ -426,7 +426,9 @@ def _rank_main(rank, world, port, q, case):
     else:
         drv.render_frame()
     rd.generate_task_list = real_tl
-    q.put((rank, drv.rounds_done, drv.total_ob.data.numpy().copy() if rank == 0 else None, drv.total_ob.count.numpy().copy() if rank == 0 else None))
+    half = (drv.half_ob.data.numpy().copy(), drv.half_ob.count.numpy().copy()) if case == "tracked" and rank == 0 else None
+    zero = bool((drv.round_ob.data == 0).all()) and bool((drv.round_ob.count == 0).all())  # the per-round accumulator between rounds
+    q.put((rank, drv.rounds_done, drv.total_ob.data.numpy().copy() if rank == 0 else None, drv.total_ob.count.numpy().copy() if rank == 0 else None, half, zero))
     dist.barrier()
     dist.destroy_process_group()
 
@@ -443,9 +445,10 @@ def _run_ranks(world, case):
     for p in procs:
         p.join(timeout=60)
         assert p.exitcode == 0
-    rounds = {r: n for r, n, _, _ in got}
-    data, count = next((d, c) for r, _, d, c in got if r == 0)
-    return rounds, data, count
+    rounds = {r: n for r, n, *_ in got}
+    assert all(zero for *_, zero in got)
+    data, count, half = next((d, c, h) for r, _, d, c, h, _ in got if r == 0)
+    return (rounds, data, count, half) if case == "tracked" else (rounds, data, count)
 
 
 def _single_process(oracle, case, rounds=2):
@@ -465,6 +468,21 @@ def test_tile_sharding_and_reduce(oracle, world):
     acc, cnt = _single_process(oracle, "rounds")  # two rounds over the whole tile list
     assert np.array_equal(count.view(np.uint32), cnt)
     assert np.array_equal(data, acc)      # disjoint tiles: the reduce is exact, the image does not depend on G
+
+
+def test_tracked_ranks_keep_the_half_buffer_of_the_odd_rounds(oracle):
+    """track_noise with two ranks: the root's half-buffer is the second round alone -- the oracle's second round rendered into zero
+    buffers, bit for bit (disjoint tiles, reverse == 0: every pixel is one rank's sum plus zeros) -- and its accumulator is still the
+    single-process image of both rounds."""
+    rounds, data, count, (half_data, half_count) = _run_ranks(2, "tracked")
+    assert rounds == {0: 2, 1: 2}
+    acc, cnt = _single_process(oracle, "tracked")
+    assert np.array_equal(count.view(np.uint32), cnt) and np.array_equal(data, acc)
+    wl = _case_workload("tracked")
+    n = len(oracle.generate_task_list(wl.xres, wl.yres))
+    acc2, cnt2, _ = oracle.OracleScene(wl.builder.to_desc()).render_round(wl.camera, wl.params(), oracle.generate_task_list(wl.xres, wl.yres, seedcount_base=n))
+    assert np.array_equal(half_count.view(np.uint32), cnt2) and (cnt2 == wl.multisample).all()
+    assert np.array_equal(half_data.view(np.uint32), acc2.view(np.uint32))
 
 
 def test_timed_mode_is_a_collective_decision(oracle):

@@ -3,7 +3,7 @@ rendered to a fixed noise level costs with and without it.
 
     python tools/adaptive_timing.py [--workload sponza-1080p] [--spp 4] [--reps 20] [--warmup 3] [--rounds 32] [--min-visits 4] [--out FILE]
 
-1. The fold.  A tracked driver without `adaptive` clears its per-round accumulator (two whole-frame fills) and adds it to the total
+1. The fold.  Done in torch, a tracked round clears the per-round accumulator (two whole-frame fills) and adds it to the total
    (two additions) and, on odd rounds, to the half-buffer (two more).  Those torch calls, between two events on torch's stream, are
    the baseline; rgk_round_fold_device over every tile of the frame, with the scene's "time_post" switch (rgk_scene_get_post_timing
    4: the copy of the tile list, the fold), is what stands in for them.  The two alternate in one process, `reps` times after
