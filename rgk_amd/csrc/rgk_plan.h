@@ -1,7 +1,7 @@
 // Launch plans, the part that needs no device: how a round is cut into passes, which walker a launch takes and how large
 // every grid is.  Pure functions over plain integers -- no call into the HIP runtime, no stream, no device buffer -- so the
 // unit builds with any host compiler and runs under sanitizers (tests/cpp/plan_main.cpp includes it alone).  The host
-// (rgk_host.cpp) and the launch wrappers (rgk_kernels.hip) call these instead of restating the formulas.
+// (rgk_scene.cpp, rgk_round.cpp) and the launch wrappers (rgk_kernels.hip) call these instead of restating the formulas.
 #pragma once
 #include <algorithm>
 #include <cstddef>

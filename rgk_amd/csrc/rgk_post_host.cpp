@@ -1,0 +1,241 @@
+// The post-processing entries: feature buffers, both denoisers, the noise estimate, tile selection and the round fold
+// (kernels: rgk_post.hip).
+#include <algorithm>
+#include <cmath>
+
+#include "rgk_scene_impl.h"
+#include "rgk_adapt.h"
+
+namespace {
+// HIP events (the scene's pool, from its first) around the launches of one post call, when the scene's "time_post" switch is on.
+struct PostTimer {
+    rgk_scene* s;
+    size_t n = 0; // marks so far
+    int mark() { // between two launches
+        if (!s->tune.time_post) return 0;
+        hipEvent_t e;
+        if (int rc = scene_event(s, n, e)) return rc;
+        n++;
+        HIPCHK(hipEventRecord(e, s->stream));
+        return 0;
+    }
+    int fold(std::vector<double>& out) const { // after the stream has been waited for
+        out.clear();
+        for (size_t i = 0; i + 1 < n; i++) {
+            float ms = 0.f;
+            HIPCHK(hipEventElapsedTime(&ms, s->events[i], s->events[i + 1]));
+            out.push_back(ms);
+        }
+        return 0;
+    }
+};
+
+// A post call once the entry's own argument checks have passed: refused while a round is in flight; the slot's old times go; with no
+// `work` to do that is all, and the device is not touched.  Else body(tm) -- the entry's allocations and its launches on the scene's
+// stream, tm.mark() between them -- then a wait for the stream, and the launch times go into the slot.
+template <class Body>
+int post_call(rgk_scene* s, const char* entry, PostSlot slot, bool work, Body&& body) {
+    if (s->prog_busy.load()) return fail(RGK_ERR_INVALID, "%s while a round is in flight on this scene", entry);
+    s->post_ms[slot].clear();
+    if (!work) return RGK_OK;
+    HIPCHK(hipSetDevice(s->device));
+    PostTimer tm{s};
+    if (int rc = body(tm)) return rc;
+    HIPCHK(hipStreamSynchronize(s->stream));
+    HIPCHK(hipGetLastError());
+    return tm.fold(s->post_ms[slot]);
+}
+
+// (every check before the scene or the device is touched; `toff`: tile_offsets)
+int check_aov_args(const rgk_scene* s, const rgk_camera* camera, const rgk_params* prm, const rgk_tile* tiles, uint32_t n_tiles, std::vector<uint32_t>& toff) {
+    if (!s || !camera || !prm || (!tiles && n_tiles)) return fail(RGK_ERR_INVALID, "null argument");
+    if (int rc = check_frame_size(prm->xres, prm->yres)) return rc;
+    return tile_offsets(prm, tiles, n_tiles, "feature pass", toff);
+}
+// What both denoise entries check besides their own parameter ranges, without touching the scene.  The fixed-sigma filter has no
+// half-buffer and no variance plane (NULL here); `p`: its parameters too, with albedo_floor 0 (sigma_k belongs to the entry).
+int check_denoise_args(const rgk_scene* s, uint32_t xres, uint32_t yres, const float* accum_rgb, const uint32_t* accum_count, const float* half_rgb,
+                       const uint32_t* half_count, const float* albedo, const float* normal, const float* depth, const rgk_denoise_var_params& p,
+                       const float* out_rgb, const float* out_variance) {
+    if (!s || !accum_rgb || !accum_count || !normal || !depth || !out_rgb) return fail(RGK_ERR_INVALID, "null argument");
+    if (p.demodulate && !albedo) return fail(RGK_ERR_INVALID, "demodulate without an albedo plane");
+    if (int rc = check_frame_size(xres, yres)) return rc;
+    if (p.iterations > 16 || p.normal_power_log2 > 16) return fail(RGK_ERR_INVALID, "iterations and normal_power_log2 must be <= 16");
+    const void* ins[] = {accum_rgb, accum_count, half_rgb, half_count, albedo, normal, depth};
+    for (const void* in : ins)
+        if (in && (in == out_rgb || in == out_variance)) return fail(RGK_ERR_INVALID, "an output plane must not be one of the inputs");
+    if (out_rgb == out_variance) return fail(RGK_ERR_INVALID, "out_rgb and out_variance must differ");
+    return RGK_OK;
+}
+// A whole denoise call once the entry's own checks have passed: the shared ones, then prepare -> [prefilter] -> iterations -> finish ->
+// [variance copy] on the scene's stream, waited for.  `wc[i]`: iteration i's colour-weight constant (sigma_i^2 / sigma_k^2).
+int denoise(rgk_scene* s, const char* entry, PostSlot slot, uint32_t xres, uint32_t yres, const float* accum_rgb, const uint32_t* accum_count, const float* half_rgb,
+            const uint32_t* half_count, const float* albedo, const float* normal, const float* depth, const rgk_denoise_var_params& p, const float* wc,
+            float* out_rgb, float* out_variance) {
+    int rc;
+    if ((rc = check_denoise_args(s, xres, yres, accum_rgb, accum_count, half_rgb, half_count, albedo, normal, depth, p, out_rgb, out_variance))) return rc;
+    return post_call(s, entry, slot, true, [&](PostTimer& tm) -> int {
+        const size_t P = (size_t)xres * yres;
+        const uint32_t it = p.iterations, demod = (it && p.demodulate) ? 1u : 0u; // no iteration: out = c, variance = v, nothing to demodulate for
+        const RgkDnMode mode = half_rgb ? RGK_DN_VARIANCE_GUIDED : RGK_DN_FIXED_SIGMA;
+        if ((rc = s->dn_col[0].alloc(P)) || (it && ((rc = s->dn_col[1].alloc(P)) || (rc = s->dn_guide.alloc(P))))) return rc;
+        hipStream_t st = s->stream;
+        uint32_t cur = 0; // the plane that holds the current image
+        const auto filter = [&](RgkDnMode m, uint32_t step, float c) {
+            rgk_launch_dn_atrous(st, m, xres, yres, step, c, p.sigma_depth, p.normal_power_log2, s->dn_guide.p, s->dn_col[cur].p, s->dn_col[cur ^ 1u].p);
+            cur ^= 1u;
+            return tm.mark();
+        };
+        if ((rc = tm.mark())) return rc;
+        rgk_launch_dn_prepare(st, P, accum_rgb, accum_count, half_rgb, half_count, albedo, normal, depth, demod, p.albedo_floor, s->dn_col[0].p, it ? s->dn_guide.p : nullptr);
+        if ((rc = tm.mark())) return rc;
+        if (it && mode == RGK_DN_VARIANCE_GUIDED && (rc = filter(RGK_DN_VARIANCE_MEAN, 1u, 0.0f))) return rc;
+        for (uint32_t i = 0; i < it; i++)
+            if ((rc = filter(mode, 1u << i, wc[i]))) return rc;
+        rgk_launch_dn_finish(st, P, s->dn_col[cur].p, albedo, demod, p.albedo_floor, out_rgb);
+        if ((rc = tm.mark())) return rc;
+        if (!out_variance) return 0;
+        rgk_launch_nz_finish(st, P, s->dn_col[cur].p, out_variance);
+        return tm.mark();
+    });
+}
+} // namespace
+
+extern "C" {
+
+int rgk_render_aov_device(rgk_scene* s, const rgk_camera* camera, const rgk_params* prm, const rgk_tile* tiles, uint32_t n_tiles, float* d_albedo,
+                          float* d_normal, float* d_depth, int32_t* d_tri) {
+    int rc;
+    std::vector<uint32_t> toff; // (read by a queued copy: lives until the stream has been waited for)
+    if ((rc = check_aov_args(s, camera, prm, tiles, n_tiles, toff))) return rc;
+    const uint32_t n = toff[n_tiles];
+    return post_call(s, "rgk_render_aov_device", POST_AOV, n != 0, [&](PostTimer& tm) -> int {
+        // The round's own buffers: its pixel list (rebuilt by every round before it is read), two ray planes and the hit plane of
+        // the workspace (written by every pass before they are read).  The frame's cached lists -- entry nodes, their caps, the
+        // light-side entries -- are neither read nor written here, so the rounds of a frame compute the same with or without this call.
+        if ((rc = ensure_workspace(s, n))) return rc;
+        hipStream_t st = s->stream;
+        DevCamera cam;
+        make_camera(camera, cam);
+        cam.lens_size = 0.0f; // every feature ray leaves from the camera's origin
+        if ((rc = tm.mark()) || (rc = queue_pixel_list(s, tiles, n_tiles, toff))) return rc;
+        rgk_launch_init_counters(st, s->counters.p, n);
+        rgk_launch_aov_raygen(st, cam, prm->xres, prm->yres, s->pix_xy.p, n, s->rayA[0].p, s->rayB[0].p);
+        if ((rc = tm.mark())) return rc;
+        rgk_launch_trace_closest(st, s->dev, s->tcfg, false, s->rayA[0].p, s->rayB[0].p, nullptr, s->hit.p, {n, s->counters.p + RGK_CNT_QUEUE, s->counters.p + RGK_CNT_FETCH_T}, s->stats.p);
+        if ((rc = tm.mark())) return rc;
+        rgk_launch_aov_gather(st, s->dev, prm->bumpmap_scale, prm->xres, s->pix_xy.p, n, s->rayA[0].p, s->rayB[0].p, s->hit.p, d_albedo, d_normal, d_depth, d_tri);
+        return tm.mark();
+    });
+}
+
+int rgk_render_aov(rgk_scene* s, const rgk_camera* camera, const rgk_params* prm, const rgk_tile* tiles, uint32_t n_tiles, float* albedo, float* normal,
+                   float* depth, int32_t* tri) {
+    int rc;
+    std::vector<uint32_t> toff;
+    if ((rc = check_aov_args(s, camera, prm, tiles, n_tiles, toff))) return rc;
+    HIPCHK(hipSetDevice(s->device));
+    const size_t P = (size_t)prm->xres * prm->yres;
+    DevBuf<float> d_alb, d_nrm, d_z;
+    DevBuf<int32_t> d_tri;
+    // (the planes go up first: pixels outside the tiles keep what the caller had there)
+    if ((albedo && (rc = d_alb.upload(albedo, 3 * P))) || (normal && (rc = d_nrm.upload(normal, 3 * P))) || (depth && (rc = d_z.upload(depth, P))) || (tri && (rc = d_tri.upload(tri, P))))
+        return rc;
+    if ((rc = rgk_render_aov_device(s, camera, prm, tiles, n_tiles, albedo ? d_alb.p : nullptr, normal ? d_nrm.p : nullptr, depth ? d_z.p : nullptr, tri ? d_tri.p : nullptr))) return rc;
+    if ((albedo && (rc = down(albedo, d_alb, 3 * P))) || (normal && (rc = down(normal, d_nrm, 3 * P))) || (depth && (rc = down(depth, d_z, P))) || (tri && (rc = down(tri, d_tri, P)))) return rc;
+    return RGK_OK;
+}
+
+int rgk_denoise_device(rgk_scene* s, uint32_t xres, uint32_t yres, const float* d_accum_rgb, const uint32_t* d_accum_count, const float* d_albedo,
+                       const float* d_normal, const float* d_depth, const rgk_denoise_params* dp, float* d_out_rgb) {
+    if (!dp) return fail(RGK_ERR_INVALID, "null argument");
+    if (!(dp->sigma_color > 0.0f) || !(dp->sigma_depth >= 0.0f) || std::isinf(dp->sigma_color) || std::isinf(dp->sigma_depth)) return fail(RGK_ERR_INVALID, "sigma_color must be > 0 and sigma_depth >= 0, both finite");
+    float sigma2[16];
+    for (uint32_t i = 0; i < dp->iterations && i < 16; i++) { // (iterations <= 16 is checked with what both entries share)
+        const float si = dp->sigma_color * std::ldexp(1.0f, -(int)i); // sigma_color * 2^-i
+        sigma2[i] = si * si;
+        if (!(sigma2[i] > 0.0f) || std::isinf(sigma2[i])) return fail(RGK_ERR_INVALID, "sigma_color^2 leaves the float range at iteration %u", i);
+    }
+    const rgk_denoise_var_params p = {dp->iterations, 0.0f, dp->sigma_depth, dp->normal_power_log2, dp->demodulate, 0.0f};
+    return denoise(s, "rgk_denoise_device", POST_DENOISE, xres, yres, d_accum_rgb, d_accum_count, nullptr, nullptr, d_albedo, d_normal, d_depth, p, sigma2, d_out_rgb, nullptr);
+}
+
+int rgk_noise_estimate_device(rgk_scene* s, uint32_t xres, uint32_t yres, uint32_t tile_size, const float* d_accum_rgb, const uint32_t* d_accum_count,
+                              const float* d_half_rgb, const uint32_t* d_half_count, rgk_noise_tile* tiles, float* d_variance) {
+    // (every check before the scene or the device is touched)
+    if (!s || !d_accum_rgb || !d_accum_count || !d_half_rgb || !d_half_count || !tiles) return fail(RGK_ERR_INVALID, "null argument");
+    if (int rc = check_frame_size(xres, yres)) return rc;
+    if (tile_size == 0) return fail(RGK_ERR_INVALID, "tile_size must be >= 1");
+    if (d_variance && (d_variance == d_accum_rgb || d_variance == d_half_rgb || (const void*)d_variance == d_accum_count || (const void*)d_variance == d_half_count))
+        return fail(RGK_ERR_INVALID, "variance must not be one of the inputs");
+    if (d_half_rgb == d_accum_rgb || d_half_count == d_accum_count) return fail(RGK_ERR_INVALID, "the half-buffer must not be the accumulator");
+    const RgkGrid2 g = rgk_nz_tile_grid(xres, yres, tile_size);
+    const int rc = post_call(s, "rgk_noise_estimate_device", POST_NOISE, true, [&](PostTimer& tm) -> int {
+        int rc;
+        if ((rc = s->nz_tiles.alloc(g.count())) || (rc = tm.mark())) return rc;
+        rgk_launch_nz_tile_sums(s->stream, xres, yres, tile_size, d_accum_rgb, d_accum_count, d_half_rgb, d_half_count, s->nz_tiles.p, d_variance);
+        return tm.mark();
+    });
+    return rc ? rc : down(tiles, s->nz_tiles, g.count());
+}
+
+int rgk_denoise_variance_device(rgk_scene* s, uint32_t xres, uint32_t yres, const float* d_accum_rgb, const uint32_t* d_accum_count, const float* d_half_rgb,
+                                const uint32_t* d_half_count, const float* d_albedo, const float* d_normal, const float* d_depth,
+                                const rgk_denoise_var_params* dp, float* d_out_rgb, float* d_out_variance) {
+    if (!dp || !d_half_rgb || !d_half_count) return fail(RGK_ERR_INVALID, "null argument");
+    if (!(dp->sigma_k > 0.0f) || !(dp->sigma_depth >= 0.0f) || !(dp->albedo_floor >= 0.0f) || std::isinf(dp->sigma_k) || std::isinf(dp->sigma_depth) || std::isinf(dp->albedo_floor))
+        return fail(RGK_ERR_INVALID, "sigma_k must be > 0, sigma_depth and albedo_floor >= 0, all finite");
+    float k2[16];
+    std::fill(k2, k2 + 16, dp->sigma_k * dp->sigma_k);
+    if (!(k2[0] > 0.0f) || std::isinf(k2[0])) return fail(RGK_ERR_INVALID, "sigma_k^2 leaves the float range");
+    if (d_half_rgb == d_accum_rgb || d_half_count == d_accum_count) return fail(RGK_ERR_INVALID, "the half-buffer must not be the accumulator");
+    return denoise(s, "rgk_denoise_variance_device", POST_DENOISE_VARIANCE, xres, yres, d_accum_rgb, d_accum_count, d_half_rgb, d_half_count, d_albedo, d_normal, d_depth,
+                   *dp, k2, d_out_rgb, d_out_variance);
+}
+
+int rgk_adapt_select(const rgk_noise_tile* tiles, const uint32_t* visits, uint32_t xres, uint32_t yres, uint32_t tile_size, const rgk_adapt_params* prm,
+                     uint8_t* live, uint32_t* n_live, uint32_t* done) {
+    if (const char* why = rgk_adapt_check(tiles, visits, xres, yres, tile_size, prm, live)) return fail(RGK_ERR_INVALID, "rgk_adapt_select: %s", why);
+    const RgkAdaptResult r = rgk_adapt_rule(tiles, visits, xres, yres, tile_size, *prm, live);
+    if (n_live) *n_live = r.n_live;
+    if (done) *done = r.done ? 1u : 0u;
+    return RGK_OK;
+}
+
+int rgk_round_fold_device(rgk_scene* s, uint32_t xres, uint32_t yres, const rgk_tile* tiles, uint32_t n_tiles, const uint8_t* to_half, float* d_round_rgb,
+                          uint32_t* d_round_count, float* d_total_rgb, uint32_t* d_total_count, float* d_half_rgb, uint32_t* d_half_count) {
+    // (every check before the scene or the device is touched)
+    if (!s || (n_tiles && (!tiles || !to_half)) || !d_round_rgb || !d_round_count || !d_total_rgb || !d_total_count || !d_half_rgb || !d_half_count)
+        return fail(RGK_ERR_INVALID, "null argument");
+    if (int rc = check_frame_size(xres, yres)) return rc;
+    const void* planes[6] = {d_round_rgb, d_round_count, d_total_rgb, d_total_count, d_half_rgb, d_half_count};
+    for (int i = 0; i < 6; i++)
+        for (int j = i + 1; j < 6; j++)
+            if (planes[i] == planes[j]) return fail(RGK_ERR_INVALID, "the six planes must be six different buffers");
+    uint32_t max_height = 0, bad = 0;
+    if (const char* why = rgk_fold_check_tiles(tiles, n_tiles, xres, yres, max_height, bad)) return fail(RGK_ERR_INVALID, "round fold: %s (tile %u)", why, bad);
+    return post_call(s, "rgk_round_fold_device", POST_FOLD, n_tiles != 0, [&](PostTimer& tm) -> int {
+        int rc;
+        if ((rc = s->fold_buf.alloc((size_t)n_tiles * 5 + (n_tiles + 3u) / 4u)) || (rc = tm.mark())) return rc;
+        hipStream_t st = s->stream;
+        // (queued copies of the caller's arrays: they are the caller's until this call returns, and it waits for the stream first)
+        uint8_t* d_flags = reinterpret_cast<uint8_t*>(s->fold_buf.p + (size_t)n_tiles * 5);
+        HIPCHK(hipMemcpyAsync(s->fold_buf.p, tiles, (size_t)n_tiles * sizeof(rgk_tile), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_flags, to_half, n_tiles, hipMemcpyHostToDevice, st));
+        if ((rc = tm.mark())) return rc;
+        rgk_launch_round_fold(st, xres, reinterpret_cast<const rgk_tile*>(s->fold_buf.p), d_flags, n_tiles, max_height, d_round_rgb, d_round_count, d_total_rgb,
+                              d_total_count, d_half_rgb, d_half_count);
+        return tm.mark();
+    });
+}
+
+int rgk_scene_get_post_timing(const rgk_scene* s, uint32_t which, double* ms, uint32_t* n) {
+    if (!s || !n || which >= POST_SLOTS || (!ms && *n)) return fail(RGK_ERR_INVALID, "bad argument");
+    if (s->magic != RGK_SCENE_MAGIC) return fail(RGK_ERR_INVALID, "not a live scene handle");
+    const std::vector<double>& v = s->post_ms[which];
+    for (uint32_t i = 0; i < *n && i < v.size(); i++) ms[i] = v[i];
+    *n = (uint32_t)v.size();
+    return RGK_OK;
+}
+
+} // extern "C"

@@ -37,7 +37,7 @@ BUILDERS = {   # name -> (build flags, environment of rgk_scene_create)
     # the walkers' <STACK, LDSN> variants (rgk_plan.h rgk_walker_variant): 256/16 is what the four above run
     "host-sah-stack256-lds16": (capi.BUILD_HOST_SAH, {"RGK_STACK_OVF": "1", "RGK_STACK_LDS": "16"}),
     "host-sah-stack256-lds32": (capi.BUILD_HOST_SAH, {"RGK_STACK_OVF": "1", "RGK_STACK_LDS": "32"}),
-    # all-LDS 32/32: taken only where max_stack + 1 + RGK_ENTRY_K <= 32 (rgk_host.cpp configure_stack), else 256/16 runs without a
+    # all-LDS 32/32: taken only where max_stack + 1 + RGK_ENTRY_K <= 32 (rgk_round_plan.h rgk_stack_plan), else 256/16 runs without a
     # word.  Which one ran cannot be read through the C ABI; max_depth can, and max_stack <= 3 (max_depth + 1): see the test.
     "host-sah-stack32-lds32": (capi.BUILD_HOST_SAH, {"RGK_STACK_OVF": "0"}),
 }
