@@ -93,9 +93,8 @@ __global__ __launch_bounds__(RGK_LIGHT_BLOCK) void k_raygen_light(const DevScene
             a = make_float4(o.x, o.y, o.z, d.x);
             b = make_float4(d.y, d.z, __uint_as_float(0xffffffffu), __uint_as_float(slot));
             pp.lvmask[slot] = 0u; // no light vertex yet
-            const bool nan_ray = (o.x != o.x) | (o.y != o.y) | (o.z != o.z) | (d.x != d.x) | (d.y != d.y) | (d.z != d.z);
             float t0, t1;
-            queue = !nan_ray && clip_to_scene(sc, o, d, 0.0f, 10000.0f, t0, t1); // Ray::near / Ray::far defaults, src/ray.hpp:25-26
+            queue = !ray_has_nan(o, d) && clip_to_scene(sc, o, d, 0.0f, 10000.0f, t0, t1); // Ray::near / Ray::far defaults, src/ray.hpp:25-26
         }
         const unsigned long long m = __ballot(queue);
         if (lane == 0) s_cnt[w] = __popcll(m);

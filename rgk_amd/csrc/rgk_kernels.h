@@ -86,10 +86,11 @@ void rgk_launch_trace_camera(hipStream_t st, const DevScene& sc, const DevCamera
                              const RgkWalk& w, unsigned long long* stats);
 void rgk_launch_trace_closest(hipStream_t st, const DevScene& sc, const RgkTraceCfg& tc, bool count_stats, const float4* rayA, const float4* rayB,
                               const float2* nearfar, float4* hit, const RgkWalk& w, unsigned long long* stats);
+// first_pp: these are the shadow rays of the pass's first vertices in a single-light scene (entry lists in pp.lentry), else null;
+// rec32: the 32-byte records of the constant-light route (below).  The launch picks its kernel from the two.
 void rgk_launch_trace_shadow(hipStream_t st, const DevScene& sc, const RgkTraceCfg& tc, bool count_stats, const float4* shA, const float4* shB,
-                             const float4* shC, float4* tot, uint8_t* vis_out, int mode, float* splat_rgb, const RgkWalk& w, unsigned long long* stats);
-void rgk_launch_trace_shadow_first(hipStream_t st, const DevScene& sc, const PassParams& pp, const RgkTraceCfg& tc, bool count_stats, const float4* shA, const float4* shB,
-                                   const float4* shC, float4* tot, const RgkWalk& w, unsigned long long* stats);
+                             const float4* shC, float4* tot, uint8_t* vis_out, int mode, float* splat_rgb, const RgkWalk& w, unsigned long long* stats,
+                             const PassParams* first_pp = nullptr, bool rec32 = false);
 void rgk_launch_raygen_light(hipStream_t st, const DevScene& sc, const DevCamera& cam, const PassParams& pp, float4* rayA, float4* rayB,
                              float4* thr, uint32_t* counters);
 void rgk_launch_shade_light(hipStream_t st, const DevScene& sc, const DevCamera& cam, const PassParams& pp, uint32_t k, const float4* rayA,
@@ -103,12 +104,9 @@ void rgk_launch_shade(hipStream_t st, const DevScene& sc, const DevCamera& cam, 
                       const float4* rayB, const float4* hit, float4* thr, float4* tot, float4* nextA, float4* nextB, float4* shA,
                       float4* shB, float4* shC, uint32_t* counters, uint32_t bound, bool bdpt = false, bool const_light = false);
 // the constant-light route (rgk.h rgk_scene_info::const_light; never with bdpt): rgk_launch_shade(const_light = true) queues shadow
-// rays as shA = {d.xyz, far}, shB = {radiance.rgb, slot} when rgk_const_light_records() says so, and these two trace them
+// rays as shA = {d.xyz, far}, shB = {radiance.rgb, slot} when rgk_const_light_records() says so, and rgk_launch_trace_shadow(rec32 =
+// true) traces them
 bool rgk_const_light_records();
-void rgk_launch_trace_shadow_cl(hipStream_t st, const DevScene& sc, const RgkTraceCfg& tc, bool count_stats, const float4* shA, const float4* shB,
-                                float4* tot, const RgkWalk& w, unsigned long long* stats);
-void rgk_launch_trace_shadow_first_cl(hipStream_t st, const DevScene& sc, const PassParams& pp, const RgkTraceCfg& tc, bool count_stats, const float4* shA, const float4* shB,
-                                      float4* tot, const RgkWalk& w, unsigned long long* stats);
 void rgk_launch_resolve(hipStream_t st, const PassParams& pp, const float4* tot, float4* pixsum, float* accum_rgb, uint32_t* accum_count);
 void rgk_launch_pack_rays(hipStream_t st, uint32_t n, const float* rays, const int32_t* ignore, float4* rayA, float4* rayB, float2* nearfar);
 void rgk_launch_pack_visibility(hipStream_t st, const DevScene& sc, uint32_t n, const float* a, const float* b, float4* shA, float4* shB,

@@ -563,17 +563,19 @@ void rgk_launch_texture_sample(hipStream_t st, const DevScene& sc, uint32_t n, c
 }
 
 // ------------------------------------------------------------------ launch wrappers (host)
-// Grids, walker variants and the bounds that shrink them: rgk_plan.h.  A walker launch takes its variant from the scene's stack
-// configuration `tc` and its grid from the bound the caller passes.
-#define RGK_TRACE_LAUNCH(K, S, L, ...) { if (count_stats) K<true, S, L><<<grid, RGK_TRACE_BLOCK, 0, st>>>(__VA_ARGS__); else K<false, S, L><<<grid, RGK_TRACE_BLOCK, 0, st>>>(__VA_ARGS__); }
-#define RGK_TRACE_DISPATCH(K, BOUND, ...)                                                       \
-    {                                                                                           \
-        const int grid = rgk_bounded_grid(rgk_trace_grid(tc.lds), BOUND, RGK_TRACE_BLOCK);      \
-        const RgkWalker v = rgk_walker_variant(tc);                                             \
-        if (v.stack == 32) RGK_TRACE_LAUNCH(K, 32, 32, __VA_ARGS__)                             \
-        else if (v.lds == 32) RGK_TRACE_LAUNCH(K, 256, 32, __VA_ARGS__)                         \
-        else RGK_TRACE_LAUNCH(K, 256, 16, __VA_ARGS__)                                          \
-    }
+// Grids, walker variants and the bounds that shrink them: rgk_plan.h.  A walker launch takes its grid from the bound the caller
+// passes and its kernel's <COUNT, STACK, LDSN> from `count_stats` and the scene's stack configuration `tc`: launch(grid, variant)
+// gets the three as the constants of the variant's type.
+template <bool C, int S, int L>
+struct WalkerKernel { static constexpr bool COUNT = C; static constexpr int STACK = S, LDSN = L; };
+template <class Launch>
+static void trace_dispatch(const RgkTraceCfg& tc, bool count_stats, uint32_t bound, Launch launch) {
+    const int grid = rgk_bounded_grid(rgk_trace_grid(tc.lds), bound, RGK_TRACE_BLOCK);
+    const RgkWalker v = rgk_walker_variant(tc);
+    if (v.stack == 32) { if (count_stats) launch(grid, WalkerKernel<true, 32, 32>{}); else launch(grid, WalkerKernel<false, 32, 32>{}); }
+    else if (v.lds == 32) { if (count_stats) launch(grid, WalkerKernel<true, 256, 32>{}); else launch(grid, WalkerKernel<false, 256, 32>{}); }
+    else { if (count_stats) launch(grid, WalkerKernel<true, 256, 16>{}); else launch(grid, WalkerKernel<false, 256, 16>{}); }
+}
 
 // ------------------------------------------------------------------ entry points of the camera rays
 // All camera rays through a group of RGK_ENTRY_PIX consecutive pixels of the round's list (a row of an 8x8 block, or whatever a
@@ -820,37 +822,41 @@ void rgk_launch_trace_camera(hipStream_t st, const DevScene& sc, const DevCamera
         // 8 stack entries per lane in LDS (the rest in the overflow area): with the bundle's 32 floats per lane that makes 40 KB per
         // workgroup, four workgroups per CU
         const int grid = rgk_bounded_grid(rgk_trace_grid(tc.lds), rgk_beam_bound(w.bound), RGK_TRACE_BLOCK);
-        RGK_TRACE_LAUNCH(k_trace_camera_beam, 256, 8, sc, cam, pp, hit, w.count_ptr, w.fetch, stats, tc.ovf)
+        if (count_stats) k_trace_camera_beam<true, 256, 8><<<grid, RGK_TRACE_BLOCK, 0, st>>>(sc, cam, pp, hit, w.count_ptr, w.fetch, stats, tc.ovf);
+        else k_trace_camera_beam<false, 256, 8><<<grid, RGK_TRACE_BLOCK, 0, st>>>(sc, cam, pp, hit, w.count_ptr, w.fetch, stats, tc.ovf);
         return;
     }
-    RGK_TRACE_DISPATCH(k_trace_camera, w.bound, sc, cam, pp, hit, w.count_ptr, w.fetch, stats, tc.ovf)
+    trace_dispatch(tc, count_stats, w.bound, [&](int grid, auto k) { k_trace_camera<k.COUNT, k.STACK, k.LDSN><<<grid, RGK_TRACE_BLOCK, 0, st>>>(sc, cam, pp, hit, w.count_ptr, w.fetch, stats, tc.ovf);
+    });
 }
 
 void rgk_launch_trace_closest(hipStream_t st, const DevScene& sc, const RgkTraceCfg& tc, bool count_stats, const float4* rayA, const float4* rayB,
                               const float2* nearfar, float4* hit, const RgkWalk& w, unsigned long long* stats) {
-    RGK_TRACE_DISPATCH(k_trace_closest, w.bound, sc, rayA, rayB, nearfar, hit, w.count_ptr, w.fetch, stats, tc.ovf)
+    trace_dispatch(tc, count_stats, w.bound, [&](int grid, auto k) {
+        k_trace_closest<k.COUNT, k.STACK, k.LDSN><<<grid, RGK_TRACE_BLOCK, 0, st>>>(sc, rayA, rayB, nearfar, hit, w.count_ptr, w.fetch, stats, tc.ovf);
+    });
 }
 
-void rgk_launch_trace_shadow(hipStream_t st, const DevScene& sc, const RgkTraceCfg& tc, bool count_stats, const float4* shA, const float4* shB,
-                             const float4* shC, float4* tot, uint8_t* vis_out, int mode, float* splat_rgb, const RgkWalk& w, unsigned long long* stats) {
-    RGK_TRACE_DISPATCH(k_trace_shadow, w.bound, sc, shA, shB, shC, tot, vis_out, mode, splat_rgb, w.count_ptr, w.fetch, stats, tc.ovf)
-}
-
-void rgk_launch_trace_shadow_first(hipStream_t st, const DevScene& sc, const PassParams& pp, const RgkTraceCfg& tc, bool count_stats, const float4* shA, const float4* shB,
-                                   const float4* shC, float4* tot, const RgkWalk& w, unsigned long long* stats) {
-    RGK_TRACE_DISPATCH(k_trace_shadow_first, w.bound, sc, pp, shA, shB, shC, tot, w.count_ptr, w.fetch, stats, tc.ovf)
-}
-
-// The same two for the 32-byte records of the constant-light route: shA = {d.xyz, far}, shB = {radiance.rgb, slot}; every ray
-// starts at sc.cl_pos with near = 20 eps.
+// Shadow rays, four kernels behind one entry.  first_pp: the pass whose FIRST vertices these rays leave, in a single-light scene:
+// they start at the light-side entry nodes of their pixel group (pp.lentry).  rec32: the 32-byte records of the constant-light
+// route, shA = {d.xyz, far}, shB = {radiance.rgb, slot}, every ray from sc.cl_pos with near = 20 eps (shC is not read).  Either of
+// the two means a round's shadow launch: tot[slot] += radiance, so vis_out, mode and splat_rgb are for the plain kernel alone.
 bool rgk_const_light_records() { return RGK_CL_REC32 != 0; }
-void rgk_launch_trace_shadow_cl(hipStream_t st, const DevScene& sc, const RgkTraceCfg& tc, bool count_stats, const float4* shA, const float4* shB,
-                                float4* tot, const RgkWalk& w, unsigned long long* stats) {
-    RGK_TRACE_DISPATCH(k_trace_shadow_cl, w.bound, sc, shA, shB, tot, w.count_ptr, w.fetch, stats, tc.ovf)
-}
-void rgk_launch_trace_shadow_first_cl(hipStream_t st, const DevScene& sc, const PassParams& pp, const RgkTraceCfg& tc, bool count_stats, const float4* shA, const float4* shB,
-                                      float4* tot, const RgkWalk& w, unsigned long long* stats) {
-    RGK_TRACE_DISPATCH(k_trace_shadow_first_cl, w.bound, sc, pp, shA, shB, tot, w.count_ptr, w.fetch, stats, tc.ovf)
+void rgk_launch_trace_shadow(hipStream_t st, const DevScene& sc, const RgkTraceCfg& tc, bool count_stats, const float4* shA, const float4* shB,
+                             const float4* shC, float4* tot, uint8_t* vis_out, int mode, float* splat_rgb, const RgkWalk& w, unsigned long long* stats,
+                             const PassParams* first_pp, bool rec32) {
+    if (!first_pp && !rec32) trace_dispatch(tc, count_stats, w.bound, [&](int grid, auto k) {
+        k_trace_shadow<k.COUNT, k.STACK, k.LDSN><<<grid, RGK_TRACE_BLOCK, 0, st>>>(sc, shA, shB, shC, tot, vis_out, mode, splat_rgb, w.count_ptr, w.fetch, stats, tc.ovf);
+    });
+    else if (!rec32) trace_dispatch(tc, count_stats, w.bound, [&](int grid, auto k) {
+        k_trace_shadow_first<k.COUNT, k.STACK, k.LDSN><<<grid, RGK_TRACE_BLOCK, 0, st>>>(sc, *first_pp, shA, shB, shC, tot, w.count_ptr, w.fetch, stats, tc.ovf);
+    });
+    else if (!first_pp) trace_dispatch(tc, count_stats, w.bound, [&](int grid, auto k) {
+        k_trace_shadow_cl<k.COUNT, k.STACK, k.LDSN><<<grid, RGK_TRACE_BLOCK, 0, st>>>(sc, shA, shB, tot, w.count_ptr, w.fetch, stats, tc.ovf);
+    });
+    else trace_dispatch(tc, count_stats, w.bound, [&](int grid, auto k) {
+        k_trace_shadow_first_cl<k.COUNT, k.STACK, k.LDSN><<<grid, RGK_TRACE_BLOCK, 0, st>>>(sc, *first_pp, shA, shB, tot, w.count_ptr, w.fetch, stats, tc.ovf);
+    });
 }
 
 void rgk_launch_shade(hipStream_t st, const DevScene& sc, const DevCamera& cam, const PassParams& pp, uint32_t bounce, const float4* rayA,
@@ -911,5 +917,7 @@ void rgk_launch_list_hits(hipStream_t st, const float4* hit, const uint32_t* cou
 }
 void rgk_launch_trace_shadow_jobs(hipStream_t st, const DevScene& sc, const PassParams& pp, const RgkTraceCfg& tc, bool count_stats, const float4* jobs, const float4* rads,
                                   float4* tot, const RgkWalk& w, unsigned long long* stats) {
-    RGK_TRACE_DISPATCH(k_trace_shadow_jobs, w.bound, sc, pp, jobs, rads, tot, w.count_ptr, w.fetch, stats, tc.ovf)
+    trace_dispatch(tc, count_stats, w.bound, [&](int grid, auto k) {
+        k_trace_shadow_jobs<k.COUNT, k.STACK, k.LDSN><<<grid, RGK_TRACE_BLOCK, 0, st>>>(sc, pp, jobs, rads, tot, w.count_ptr, w.fetch, stats, tc.ovf);
+    });
 }

@@ -247,12 +247,7 @@ int queue_pass(rgk_scene* s, KernelLog& kl, const DevCamera& cam, PassParams& pp
             return rc;
         // (the constant-light route: the shading launches above left 32-byte records, shA = {d, far}, shB = {radiance, slot})
         const bool first = b == 0 && light_entry, rec32 = const_light && rgk_const_light_records();
-        rc = kl.run(first ? RGK_K_SHADOW_FIRST : RGK_K_SHADOW, [&] {
-            if (rec32 && first) rgk_launch_trace_shadow_first_cl(st, s->dev, pp, tc, count_stats, shA, shB, tot, ws, s->stats.p);
-            else if (rec32) rgk_launch_trace_shadow_cl(st, s->dev, tc, count_stats, shA, shB, tot, ws, s->stats.p);
-            else if (first) rgk_launch_trace_shadow_first(st, s->dev, pp, tc, count_stats, shA, shB, shC, tot, ws, s->stats.p);
-            else rgk_launch_trace_shadow(st, s->dev, tc, count_stats, shA, shB, shC, tot, nullptr, RGK_SHADOW_ADD, nullptr, ws, s->stats.p);
-        });
+        rc = kl.run(first ? RGK_K_SHADOW_FIRST : RGK_K_SHADOW, [&] { rgk_launch_trace_shadow(st, s->dev, tc, count_stats, shA, shB, shC, tot, nullptr, RGK_SHADOW_ADD, nullptr, ws, s->stats.p, first ? &pp : nullptr, rec32); });
         // (the vertex queue after the plain rays: both add into the slot sums, a slot has a vertex in ONE of the two queues)
         if (rc || (R > 0 && (rc = kl.run(RGK_K_SHADOW_JOBS, [&] { rgk_launch_trace_shadow_jobs(st, s->dev, pp, tc, count_stats, s->jobs.p, s->rads.p, tot, {ub, cn + RGK_CNT_CONN + b, cn + RGK_CNT_FETCH_J + b}, s->stats.p); }))))
             return rc;

@@ -31,6 +31,12 @@
 #ifndef RGK_TRACE_WAVES
 #define RGK_TRACE_WAVES 8 // waves per SIMD the 16-LDS-entry traversal kernels are compiled for (64 VGPRs); the 32-entry ones are LDS-bound at 5
 #endif
+#ifndef RGK_BEAM_WAVES
+#define RGK_BEAM_WAVES 4 // ... the beam walker (k_trace_camera_beam)
+#endif
+#ifndef RGK_JOB_WAVES
+#define RGK_JOB_WAVES 6 // ... the vertex queue's walker: its vertex state costs ~12 VGPRs over a plain shadow ray, 8 waves per SIMD would spill 44 bytes
+#endif
 #ifndef RGK_JOB_REFILL_BELOW
 #define RGK_JOB_REFILL_BELOW 24 // the vertex queue's walker: lanes between two rays of their vertex wait for the refill too
 #endif
@@ -149,13 +155,124 @@ __device__ __forceinline__ uint32_t fetch_chunk(uint32_t count, uint32_t nwaves,
 
 __device__ __forceinline__ float cvt_ubyte(uint32_t w, int c) { return (float)((w >> (8 * c)) & 0xffu); }
 
-// ANY = false: closest hit, results to hit[i] = {t, alpha, beta, tri}.
-// ANY = true : Scene::Visibility; vis_out[i] = visible, or (path mode) tot[slot] += radiance if visible.
-//   q0 = {o.xyz, d.x}; q1 = {d.y, d.z, ignore | far, slot}; q2 = {radiance.rgb, near} (shadow only)
-// STACK: entries the tree can need (host bound); LDSN <= STACK of them live in LDS, the rest -- reached only on the
-// deepest walks of a deep tree -- in a per-lane global overflow area, so that a deep tree does not halve the occupancy.
-// RAYGEN (closest hit, bounce 0): there is no ray queue -- ray i is the camera ray of path slot i, made here.
-// JOB (any hit, bidirectional rounds): a queue entry is not a ray but a camera-path VERTEX with its 1 + reverse shadow rays --
+// ------------------------------------------------------------------ what the per-ray walker and the beam walker share
+// Each piece has the one shape found to compile to the very code of the text it replaced (tools/device_code_diff.sh; the shapes
+// that did not, and the pieces that are still written out in place for want of one: profiles/walker_pieces_device_code.txt).
+// The wave's queue cursor.  A wave's FIRST slice is dealt statically (wave w takes [w * chunk, (w + 1) * chunk)), the later ones
+// through the device-wide cursor, which therefore counts from n_waves * chunk.  With the cursor alone every one of a launch's ~8000
+// waves started with a returning atomic on one word (~88 per microsecond chip-wide): ~90 us per launch whatever its work -- for the
+// hundreds of short launches of a deep path loop, most of their time.  A wave whose static slice lies beyond the queue leaves at once.
+// The walkers keep [w_next, w_end) and `exhausted` (the device cursor has passed `count`) themselves, all wave-uniform.
+__device__ __forceinline__ uint32_t walk_waves() { return gridDim.x * (RGK_TRACE_BLOCK / 64); }
+__device__ __forceinline__ uint32_t first_slice(const uint32_t chunk, const uint32_t count) {
+    return min((blockIdx.x * (RGK_TRACE_BLOCK / 64) + (threadIdx.x >> 6)) * chunk, count);
+}
+// where the wave's next slice starts; >= count: there is none
+__device__ __forceinline__ uint32_t next_slice(uint32_t* __restrict__ fetch, const uint32_t chunk, const uint32_t count, const int lane) {
+    const uint32_t n_waves = walk_waves();
+    uint32_t base = 0;
+    if (n_waves * chunk >= count) base = count; // (the static slices covered the queue: no cursor traffic at all)
+    else if (lane == 0) base = atomicAdd(fetch, chunk) + n_waves * chunk;
+    return __builtin_amdgcn_readfirstlane(base);
+}
+
+// one stack entry from LDS by an explicit ds_read_b32: LaneStack::pop says why
+__device__ __forceinline__ int lds_pop(const int* p) {
+    int v;
+    asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"((uint32_t)(uintptr_t)p) : "memory");
+    return v;
+}
+// A lane's traversal stack.  STACK: entries the tree can need (host bound); the first LDSN <= STACK of them live in LDS as
+// [entry][lane] (bank = lane: conflict-free), the rest -- reached only on the deepest walks of a deep tree -- in a global overflow
+// area, [entry][thread of the launch], so that a deep tree does not halve the occupancy.  The number of entries held, `sp`, stays
+// a local of the walker: as a member it changed the code.
+template <int STACK, int LDSN>
+struct LaneStack {
+    int *lds, *ovf;
+    uint32_t ostride;
+    // write entry sp (the branch-free pushes write first and count the entry only if it is a real child)
+    __device__ __forceinline__ void put(const int sp, const int x) const {
+        if (LDSN >= STACK || sp < LDSN) lds[sp * RGK_TRACE_BLOCK] = x;
+        else ovf[(size_t)(sp - LDSN) * ostride] = x;
+    }
+    __device__ __forceinline__ void put_lds(const int sp, const int x) const { lds[sp * RGK_TRACE_BLOCK] = x; } // the caller knows sp < LDSN
+    // (The LDS part is read with an explicit ds_read_b32.  Written as a plain conditional the compiler folds the two sources into ONE
+    // flat_load of a selected pointer -- also with the sides forced to values, also through a volatile pointer: then a system-coherent
+    // flat load -- and every pop, nearly all of which come from LDS, takes the flat path: a vector-memory AND an LDS operation, waited
+    // for as both.  The low half of a generic pointer into LDS is its LDS address.  The plain form, kept behind a switch while the
+    // two were measured, is gone.)
+    __device__ __forceinline__ int pop(const int sp) const {
+        return (LDSN >= STACK || sp < LDSN) ? lds_pop(lds + sp * RGK_TRACE_BLOCK) : ovf[(size_t)(sp - LDSN) * ostride];
+    }
+};
+// ... of this thread, from the workgroup's LDS block and the launch's overflow area
+template <int STACK, int LDSN>
+__device__ __forceinline__ LaneStack<STACK, LDSN> lane_stack(int* lds_block, int* ovf_base) {
+    return {lds_block + threadIdx.x, ovf_base + (blockIdx.x * RGK_TRACE_BLOCK + threadIdx.x), gridDim.x * RGK_TRACE_BLOCK};
+}
+
+// A ray with a NaN coordinate (a connection between coincident points normalises a zero vector) can never record a hit -- every
+// plane solve and barycentric test on it compares false -- but its NaN slab distances drop out of the box tests, so it would walk
+// the WHOLE tree first: on the 1 M-triangle scene a handful of such rays kept every late-bounce shadow launch alive for 5-9 ms.
+// Same answer, at once: whoever starts a ray asks this before clip_to_scene.
+__device__ __forceinline__ bool ray_has_nan(const f3 o, const f3 d) { return (o.x != o.x) | (o.y != o.y) | (o.z != o.z) | (d.x != d.x) | (d.y != d.y) | (d.z != d.z); }
+// 1/d for the box tests only, clamped to +-1e30: with an infinite reciprocal (a ray lying exactly in an axis-aligned wall:
+// connections between two points of one wall) q*inf + (-inf) is NaN, the axis drops out of every slab test and the ray visits
+// every box along its way -- thousands of nodes per ray kept the late-bounce shadow launches of the 1 M-triangle scene alive for
+// 5-9 ms.  A huge finite reciprocal keeps the slab test exact enough (boxes are eps-padded); results never depend on it.
+__device__ __forceinline__ f3 ray_reciprocal(const f3 d) {
+    return mk3(fminf(fmaxf(1.f / d.x, -1e30f), 1e30f), fminf(fmaxf(1.f / d.y, -1e30f), 1e30f), fminf(fmaxf(1.f / d.z, -1e30f), 1e30f));
+}
+
+// One 64-byte QNode: {p.xyz, sx} {child[4]} {qlo.x qlo.y qlo.z qhi.x} {qhi.y qhi.z sy sz} -- the corner the 8-bit plane codes count
+// from, the per-axis quantisation step (a power of two), per axis one word of four low and one of four high plane codes, and the
+// four child codes (inner node >= 0, leaf < 0, unused slot = sentinel).  The distance arithmetic on them is the walker's own.
+// (the SGPR-base + 32-bit-offset load form of rgk_device.h gld_* was measured here: 23.8 vs 23.0 ms, not kept)
+struct NodeWords { f3 p; float sx, sy, sz; uint32_t lx, ly, lz, hx, hy, hz; };
+__device__ __forceinline__ NodeWords node_words(const float4* __restrict__ nodes, const int cur, int& c0, int& c1, int& c2, int& c3) {
+    const float4 n0 = nodes[4 * cur + 0], n1 = nodes[4 * cur + 1], n2 = nodes[4 * cur + 2], n3 = nodes[4 * cur + 3];
+    NodeWords w;
+    w.p = mk3(n0.x, n0.y, n0.z);
+    w.sx = n0.w; w.sy = n3.z; w.sz = n3.w;
+    w.lx = __float_as_uint(n2.x); w.ly = __float_as_uint(n2.y); w.lz = __float_as_uint(n2.z);
+    w.hx = __float_as_uint(n2.w); w.hy = __float_as_uint(n3.x); w.hz = __float_as_uint(n3.y);
+    c0 = __float_as_int(n1.x); c1 = __float_as_int(n1.y); c2 = __float_as_int(n1.z); c3 = __float_as_int(n1.w);
+    return w;
+}
+
+// Sort the four (entry distance, child) pairs of a node ascending: a 5-comparator network.  Misses carry distance = inf and
+// child = sentinel and sort to the back.
+__device__ __forceinline__ void cswap(float& ta, float& tb, int& ra, int& rb) {
+    const bool sw = tb < ta; const float tt = sw ? tb : ta, tu = sw ? ta : tb; const int rr = sw ? rb : ra, ru = sw ? ra : rb;
+    ta = tt; tb = tu; ra = rr; rb = ru;
+}
+__device__ __forceinline__ void sort4(float& t0, float& t1, float& t2, float& t3, int& r0, int& r1, int& r2, int& r3) {
+    cswap(t0, t1, r0, r1); cswap(t2, t3, r2, r3); cswap(t0, t2, r0, r2); cswap(t1, t3, r1, r3); cswap(t1, t2, r1, r2);
+}
+
+// A leaf's child code is ~code, code = first << 4 | count - 1: 1 ... 16 consecutive triangle records of three float4 (TriIsect,
+// what tri_test takes; the triangle's id is the last word).
+__device__ __forceinline__ uint32_t leaf_first(const uint32_t code) { return code >> 4; }
+__device__ __forceinline__ uint32_t leaf_count(const uint32_t code) { return (code & 15u) + 1u; }
+__device__ __forceinline__ const float4* tri_record(const float4* tris, const uint32_t i) { return tris + 3 * i; }
+// COUNT: what a walker adds to the launch's statistics, nodes visited and triangles tested (closest-hit launches stats[0..1],
+// shadow launches stats[2..3])
+template <bool COUNT>
+__device__ __forceinline__ void flush_walk_counts(unsigned long long* __restrict__ stats, const uint32_t n_nodes, const uint32_t n_tris) {
+    if (COUNT) { atomicAdd(&stats[0], (unsigned long long)n_nodes); atomicAdd(&stats[1], (unsigned long long)n_tris); }
+}
+
+// The ray kinds of the per-ray walker:
+enum class RayKind {
+    Closest,          // closest hit of queued rays: results to hit[i] = {t, alpha, beta, tri}
+    Camera,           // closest hit at bounce 0: there is no ray queue -- ray i is the camera ray of path slot i, made here
+    Shadow,           // any hit, Scene::Visibility: vis_out[i] = visible, or (path mode) tot[slot] += radiance if visible
+    ShadowConstLight, // any hit on the constant-light route of a unidirectional round: 32-byte records (below)
+    ShadowJobs,       // any hit in bidirectional rounds: a queue entry is a camera-path vertex with its shadow rays (below)
+};
+
+//   q0 = {o.xyz, d.x}; q1 = {d.y, d.z, ignore | far, slot}; q2 = {radiance.rgb, near} (shadow only); STACK, LDSN: LaneStack
+// ShadowJobs (JOB below): a queue entry is not a ray but a camera-path VERTEX with its 1 + reverse shadow rays --
 // NEE to the path's light and the connections to the path's light vertices (path_tracer.cpp:427-480).  They all END at the
 // vertex and START at points the slot already holds (pp.light, pp.lv), so the entry carries only the vertex, its contribution,
 // and one radiance per ray: q0[i] = {p.xyz, slot}, q0[batch + i] = {contribution.rgb, mask}, q0[2 batch + i] = {emission.rgb}
@@ -166,39 +283,30 @@ __device__ __forceinline__ float cvt_ubyte(uint32_t w, int c) { return (float)((
 // Most vertices have the NEE ray only (a light sub-path needs its first ray to hit the scene), so everything that ray needs sits
 // behind the queue index alone: one round of loads per refill, as for a plain shadow ray.  Between rays a lane keeps the sum,
 // the mask and the queue index; the vertex itself is read again for the (rare) later rays and for the total.
-__device__ __forceinline__ int lds_pop(const int* p) {
-    int v;
-    asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"((uint32_t)(uintptr_t)p) : "memory");
-    return v;
-}
-// CLO (any hit, the constant-light route of a unidirectional round): every ray starts at the scene's one point light with
+// ShadowConstLight (CLO below): every ray starts at the scene's one point light with
 // near = 20 eps, so the queue holds q0 = {d.xyz, far}, q1 = {radiance.rgb, slot} only.  (Origin and near distance are still kept
 // per lane, copied from the kernel arguments at each refill behind an empty asm: left visible as loop invariants, everything that
 // depends on them alone -- the scene box relative to the origin, for one -- is hoisted out of the walk and held in VGPRs for the
 // whole kernel, 63 -> 70 of them; behind the asm the kernel has the registers of k_trace_shadow.)
-template <bool ANY, bool COUNT, int STACK, int LDSN, bool RAYGEN = false, bool JOB = false, bool CLO = false>
-__device__ __forceinline__ void trace_persistent(const DevScene& sc, const float4* __restrict__ q0, const float4* __restrict__ q1,
-                                                 const float4* __restrict__ q2, const float2* __restrict__ nearfar,
-                                                 float4* __restrict__ hit, float4* __restrict__ tot, uint8_t* __restrict__ vis_out,
-                                                 const int mode, float* __restrict__ splat_rgb,
-                                                 const uint32_t count, uint32_t* __restrict__ fetch, int* __restrict__ stack, int* __restrict__ ovf, const uint32_t ostride,
-                                                 uint32_t& n_nodes, uint32_t& n_tris, const DevCamera* cam = nullptr, const PassParams* pp = nullptr,
-                                                 unsigned long long* __restrict__ util = nullptr) {
+// pp: Camera and ShadowJobs need it; Shadow and ShadowConstLight take it for the first vertex of a single-light scene (entry lists).
+template <RayKind KIND, bool COUNT, int STACK, int LDSN>
+__device__ __forceinline__ void trace_persistent(
+    const DevScene& sc, const float4* __restrict__ q0, const float4* __restrict__ q1, const float4* __restrict__ q2, const float2* __restrict__ nearfar,
+    float4* __restrict__ hit, float4* __restrict__ tot, uint8_t* __restrict__ vis_out, const int mode, float* __restrict__ splat_rgb, const uint32_t count,
+    uint32_t* __restrict__ fetch, int* __restrict__ lds_stack, int* __restrict__ ovf_base, uint32_t& n_nodes, uint32_t& n_tris,
+    unsigned long long* __restrict__ stats, const DevCamera* cam = nullptr, const PassParams* pp = nullptr) {
+    const LaneStack<STACK, LDSN> stk = lane_stack<STACK, LDSN>(lds_stack, ovf_base);
+    constexpr bool RAYGEN = KIND == RayKind::Camera, CLO = KIND == RayKind::ShadowConstLight, JOB = KIND == RayKind::ShadowJobs;
+    constexpr bool ANY = KIND == RayKind::Shadow || CLO || JOB;
     const int lane = threadIdx.x & 63;
     uint32_t u_node_it = 0, u_leaf_it = 0, u_outer_it = 0, u_refill = 0; // COUNT: wave-level iteration counts (lane occupancy per phase)
-    const int stride = RGK_TRACE_BLOCK;
     const float eps = sc.epsilon;
     const int walk_q = (int)sc.walk_q;
     const float4* __restrict__ nodes = reinterpret_cast<const float4*>(sc.nodes);
     const float4* __restrict__ tris = reinterpret_cast<const float4*>(sc.tris);
-    const uint32_t chunk = fetch_chunk(count, gridDim.x * (RGK_TRACE_BLOCK / 64), ANY ? 4u : 16u);
-    // A wave's FIRST slice is dealt statically (wave w takes [w * chunk, (w + 1) * chunk)), the later ones through the device-wide
-    // cursor, which therefore counts from n_waves * chunk.  With the cursor alone every one of a launch's ~8000 waves started with
-    // a returning atomic on one word (~88 per microsecond chip-wide): ~90 us per launch whatever its work -- for the hundreds of
-    // short launches of a deep path loop, most of their time.  A wave whose static slice lies beyond the queue leaves at once.
-    const uint32_t n_waves = gridDim.x * (RGK_TRACE_BLOCK / 64), wave_id = blockIdx.x * (RGK_TRACE_BLOCK / 64) + (threadIdx.x >> 6);
-    uint32_t w_next = min(wave_id * chunk, count), w_end = min(w_next + chunk, count); // wave-uniform: this wave's slice of the queue
-    bool exhausted = false;         // wave-uniform: the device cursor has passed `count`
+    const uint32_t chunk = fetch_chunk(count, walk_waves(), ANY ? 4u : 16u);
+    uint32_t w_next = first_slice(chunk, count), w_end = min(w_next + chunk, count); // the wave's slice of the queue (first_slice above)
+    bool exhausted = false;
     // per-lane ray state
     bool active = false;
     uint32_t idx = 0, ignore = 0xffffffffu, slot = 0;
@@ -210,7 +318,6 @@ __device__ __forceinline__ void trace_persistent(const DevScene& sc, const float
     uint32_t jmask = 0;
     bool seg_pending = false;
 
-#define RGK_PUT(x) { if (LDSN >= STACK || sp < LDSN) stack[sp * stride] = (x); else ovf[(size_t)(sp - LDSN) * ostride] = (x); }
 // JOB: Ray(from, p, 20 eps) (src/ray.hpp:15-22) into the lane's traversal state; a ray that cannot touch the scene is visible at once
 #define RGK_JOB_RAY(from_, p_)                                                                                                         \
     {                                                                                                                                  \
@@ -221,20 +328,13 @@ __device__ __forceinline__ void trace_persistent(const DevScene& sc, const float
         best_t = __builtin_inff(); best_tri = -1;                                                                                      \
         sp = 0;                                                                                                                        \
         float t0_, t1_;                                                                                                                \
-        const bool nan_ = (o.x != o.x) | (o.y != o.y) | (o.z != o.z) | (d.x != d.x) | (d.y != d.y) | (d.z != d.z);                     \
-        if (!nan_ && clip_to_scene(sc, o, d, tn_, tf_, t0_, t1_)) {                                                                    \
+        if (!ray_has_nan(o, d) && clip_to_scene(sc, o, d, tn_, tf_, t0_, t1_)) {                                                       \
             tlo = t0_ - eps; thi = t1_ + eps;                                                                                          \
-            inv = mk3(fminf(fmaxf(1.f / d.x, -1e30f), 1e30f), fminf(fmaxf(1.f / d.y, -1e30f), 1e30f), fminf(fmaxf(1.f / d.z, -1e30f), 1e30f)); \
+            inv = ray_reciprocal(d);                                                                                                   \
             cur = 0;                                                                                                                   \
             seg_pending = false;                                                                                                       \
         } else jsum = jsum + rad;                                                                                                      \
     }
-// (The LDS part is read by an explicit ds_read_b32.  Written as a plain conditional the compiler folds the two sources into ONE
-// flat_load of a selected pointer -- also with the sides forced to values, also through a volatile pointer: then a system-coherent
-// flat load -- and every pop, nearly all of which come from LDS, takes the flat path: a vector-memory AND an LDS operation, waited
-// for as both.  The low half of a generic pointer into LDS is its LDS address.  The plain form, kept behind a switch while the
-// two were measured, is gone.)
-#define RGK_POP() ((LDSN >= STACK || sp < LDSN) ? lds_pop(stack + sp * stride) : ovf[(size_t)(sp - LDSN) * ostride])
     for (;;) {
         // ------------------------------------------------ refill idle lanes
         // (JOB: a lane whose ray is done but whose vertex has more waits like an idle lane -- `act` counts the lanes with a ray in
@@ -248,10 +348,7 @@ __device__ __forceinline__ void trace_persistent(const DevScene& sc, const float
         if (refill_now && !(exhausted && w_next >= w_end)) {
             if (COUNT) u_refill++;
             if (w_next >= w_end) {
-                uint32_t base = 0;
-                if (n_waves * chunk >= count) base = count; // (the static slices covered the queue: no cursor traffic at all)
-                else if (lane == 0) base = atomicAdd(fetch, chunk) + n_waves * chunk;
-                base = __builtin_amdgcn_readfirstlane(base);
+                const uint32_t base = next_slice(fetch, chunk, count, lane);
                 if (base >= count) exhausted = true;
                 else { w_next = base; w_end = min(base + chunk, count); }
             }
@@ -304,19 +401,9 @@ __device__ __forceinline__ void trace_persistent(const DevScene& sc, const float
                     best_t = __builtin_inff(); best_tri = -1; best_a = 0.f; best_b = 0.f;
                     float t0, t1;
                     sp = 0;
-                    // A ray with a NaN coordinate (a connection between coincident points normalises a zero vector) can never
-                    // record a hit -- every plane solve and barycentric test on it compares false -- but its NaN slab
-                    // distances drop out of the box tests, so it would walk the WHOLE tree first: on the 1 M-triangle
-                    // scene a handful of such rays kept every late-bounce shadow launch alive for 5-9 ms.  Same answer, at once.
-                    const bool nan_ray = (o.x != o.x) | (o.y != o.y) | (o.z != o.z) | (d.x != d.x) | (d.y != d.y) | (d.z != d.z);
-                    if (!nan_ray && clip_to_scene(sc, o, d, tn, tf, t0, t1)) {
+                    if (!ray_has_nan(o, d) && clip_to_scene(sc, o, d, tn, tf, t0, t1)) {
                         tlo = t0 - eps; thi = t1 + eps;
-                        // 1/d for the box tests only, clamped to +-1e30: with an infinite reciprocal (a ray lying exactly in an
-                        // axis-aligned wall: connections between two points of one wall) q*inf + (-inf) is NaN, the axis
-                        // drops out of every slab test and the ray visits every box along its way -- thousands of nodes
-                        // per ray kept the late-bounce shadow launches of the 1 M-triangle scene alive for 5-9 ms.  A huge
-                        // finite reciprocal keeps the slab test exact enough (boxes are eps-padded); results never depend on it.
-                        inv = mk3(fminf(fmaxf(1.f / d.x, -1e30f), 1e30f), fminf(fmaxf(1.f / d.y, -1e30f), 1e30f), fminf(fmaxf(1.f / d.z, -1e30f), 1e30f));
+                        inv = ray_reciprocal(d);
                         cur = 0;
                         if (ANY && pp && pp->lentry) {
                             // first-vertex shadow rays of a single-light scene start at the entry nodes of their pixel group
@@ -330,7 +417,7 @@ __device__ __forceinline__ void trace_persistent(const DevScene& sc, const float
                                 const int* e = pp->lentry + grp * RGK_ENTRY_K;
                                 cur = e[0];
 #pragma unroll
-                                for (int k = RGK_ENTRY_K - 1; k >= 1; k--) { const int r = e[k]; if (r != STACK_SENTINEL) { RGK_PUT(r) sp++; } }
+                                for (int k = RGK_ENTRY_K - 1; k >= 1; k--) { const int r = e[k]; if (r != STACK_SENTINEL) { stk.put(sp, r); sp++; } }
                             }
                         }
                         if (RAYGEN && pp->entry) {
@@ -343,7 +430,7 @@ __device__ __forceinline__ void trace_persistent(const DevScene& sc, const float
                             const int* e = pp->entry + (size_t)(pixel_j >> RGK_ENTRY_SHIFT) * RGK_ENTRY_K;
                             cur = e[0];
 #pragma unroll
-                            for (int k = RGK_ENTRY_K - 1; k >= 1; k--) { const int r = e[k]; if (r != STACK_SENTINEL) { RGK_PUT(r) sp++; } }
+                            for (int k = RGK_ENTRY_K - 1; k >= 1; k--) { const int r = e[k]; if (r != STACK_SENTINEL) { stk.put(sp, r); sp++; } }
                         }
                     } else cur = STACK_SENTINEL; // misses the scene box: reported below as a miss
                     active = true;
@@ -411,25 +498,19 @@ __device__ __forceinline__ void trace_persistent(const DevScene& sc, const float
             for (int rep_ = 0; rep_ < 2; rep_++) { asm volatile("" : "+v"(cur));
 #endif
             const float limit = ANY ? thi : fminf(thi, best_t);
-            // one 64-byte QNode: {p.xyz, sx} {child[4]} {qlo.x qlo.y qlo.z qhi.x} {qhi.y qhi.z sy sz}
-            // (the SGPR-base + 32-bit-offset load form of rgk_device.h gld_* was measured here: 23.8 vs 23.0 ms, not kept)
-            const float4 n0 = nodes[4 * cur + 0], n1 = nodes[4 * cur + 1], n2 = nodes[4 * cur + 2], n3 = nodes[4 * cur + 3];
-            const float sx = n0.w, sy = n3.z, sz = n3.w; // per-axis quantisation step (a power of two)
+            const NodeWords n = node_words(nodes, cur, ref[0], ref[1], ref[2], ref[3]);
             // plane distance along the ray: t = (p + q*s - o) / d = q * (s/d) + (p - o)/d, one fma per plane.
             // The split loses a few ulps of |(p-o)/d| to cancellation; the child boxes carry an absolute
             // pad of eps = 1e-5 * scene diagonal, two orders above float resolution at scene scale, so the
             // test stays conservative.  (Box tests only steer the walk: they never produce a result.)
-            const float kx = sx * inv.x, ky = sy * inv.y, kz = sz * inv.z;
-            const float cx = (n0.x - o.x) * inv.x, cy = (n0.y - o.y) * inv.y, cz = (n0.z - o.z) * inv.z;
+            const float kx = n.sx * inv.x, ky = n.sy * inv.y, kz = n.sz * inv.z;
+            const float cx = (n.p.x - o.x) * inv.x, cy = (n.p.y - o.y) * inv.y, cz = (n.p.z - o.z) * inv.z;
             // near / far plane words by the sign of 1/d: no per-plane min/max needed; an unused slot
             // (qlo = 255, qhi = 0) then has near > far on every axis and can never be entered
             const bool ngx = (__float_as_uint(inv.x) >> 31) != 0, ngy = (__float_as_uint(inv.y) >> 31) != 0, ngz = (__float_as_uint(inv.z) >> 31) != 0;
-            const uint32_t lx = __float_as_uint(n2.x), ly = __float_as_uint(n2.y), lz = __float_as_uint(n2.z);
-            const uint32_t hx = __float_as_uint(n2.w), hy = __float_as_uint(n3.x), hz = __float_as_uint(n3.y);
-            const uint32_t nx = ngx ? hx : lx, fx = ngx ? lx : hx;
-            const uint32_t ny = ngy ? hy : ly, fy = ngy ? ly : hy;
-            const uint32_t nz = ngz ? hz : lz, fz = ngz ? lz : hz;
-            ref[0] = __float_as_int(n1.x); ref[1] = __float_as_int(n1.y); ref[2] = __float_as_int(n1.z); ref[3] = __float_as_int(n1.w);
+            const uint32_t nx = ngx ? n.hx : n.lx, fx = ngx ? n.lx : n.hx;
+            const uint32_t ny = ngy ? n.hy : n.ly, fy = ngy ? n.ly : n.hy;
+            const uint32_t nz = ngz ? n.hz : n.lz, fz = ngz ? n.lz : n.hz;
 #pragma unroll
             for (int c = 0; c < 4; c++) {
                 // NaNs (0 * inf on an axis-parallel ray) drop out of fmax/fmin, which only widens the
@@ -447,22 +528,18 @@ __device__ __forceinline__ void trace_persistent(const DevScene& sc, const float
             asm volatile("" :: "v"(te[0]), "v"(te[1]), "v"(te[2]), "v"(te[3]), "v"(ref[0]), "v"(ref[1]), "v"(ref[2]), "v"(ref[3])); }
 #endif
             if (!ANY) {
-                // sort the four (entry distance, ref) pairs ascending: 5-comparator network
-#define RGK_CSWAP(a, b) { const bool sw = te[b] < te[a]; const float tt = sw ? te[b] : te[a], tu = sw ? te[a] : te[b]; \
-                          const int rr = sw ? ref[b] : ref[a], ru = sw ? ref[a] : ref[b]; te[a] = tt; te[b] = tu; ref[a] = rr; ref[b] = ru; }
-                RGK_CSWAP(0, 1) RGK_CSWAP(2, 3) RGK_CSWAP(0, 2) RGK_CSWAP(1, 3) RGK_CSWAP(1, 2)
-#undef RGK_CSWAP
-                // misses carry te = inf / ref = SENTINEL and sort to the back; push far -> near.
+                sort4(te[0], te[1], te[2], te[3], ref[0], ref[1], ref[2], ref[3]);
+                // misses sort to the back; push far -> near.
                 // Branch-free: always write the next free entry, advance only for a real child (the host
                 // sized STACK above the deepest push sequence the tree can produce, rgk_commit.cpp QbvhBuilder).
                 if (LDSN >= STACK || sp + 3 <= LDSN) { // all three possible entries fit the LDS part: one test instead of three
-                    stack[sp * stride] = ref[3]; sp += (ref[3] != STACK_SENTINEL);
-                    stack[sp * stride] = ref[2]; sp += (ref[2] != STACK_SENTINEL);
-                    stack[sp * stride] = ref[1]; sp += (ref[1] != STACK_SENTINEL);
+                    stk.put_lds(sp, ref[3]); sp += (ref[3] != STACK_SENTINEL);
+                    stk.put_lds(sp, ref[2]); sp += (ref[2] != STACK_SENTINEL);
+                    stk.put_lds(sp, ref[1]); sp += (ref[1] != STACK_SENTINEL);
                 } else {
-                    RGK_PUT(ref[3]) sp += (ref[3] != STACK_SENTINEL);
-                    RGK_PUT(ref[2]) sp += (ref[2] != STACK_SENTINEL);
-                    RGK_PUT(ref[1]) sp += (ref[1] != STACK_SENTINEL);
+                    stk.put(sp, ref[3]); sp += (ref[3] != STACK_SENTINEL);
+                    stk.put(sp, ref[2]); sp += (ref[2] != STACK_SENTINEL);
+                    stk.put(sp, ref[1]); sp += (ref[1] != STACK_SENTINEL);
                 }
                 cur = ref[0];
             } else {
@@ -476,9 +553,9 @@ __device__ __forceinline__ void trace_persistent(const DevScene& sc, const float
                 cur = bi == 0 ? ref[0] : (bi == 1 ? ref[1] : (bi == 2 ? ref[2] : ref[3])); // SENTINEL when no child is entered
 #pragma unroll
                 for (int c = 0; c < 4; c++)
-                    if (c != bi && ref[c] != STACK_SENTINEL && sp < STACK) { RGK_PUT(ref[c]) sp++; }
+                    if (c != bi && ref[c] != STACK_SENTINEL && sp < STACK) { stk.put(sp, ref[c]); sp++; }
             }
-            if (cur == STACK_SENTINEL && sp > 0) { sp--; cur = RGK_POP(); }
+            if (cur == STACK_SENTINEL && sp > 0) { sp--; cur = stk.pop(sp); }
         }
         // ------------------------------------------------ leaf: every triangle of it.  (One triangle per scheduled step,
         // leaving when the walkers regain the majority, was measured slower: 24.2 vs 23.3 ms.)
@@ -488,10 +565,11 @@ __device__ __forceinline__ void trace_persistent(const DevScene& sc, const float
         }
         if (active && cur < 0) {
             const uint32_t code = ~(uint32_t)cur;
-            const uint32_t first = code >> 4, cnt = (code & 15u) + 1u;
+            const uint32_t first = leaf_first(code), cnt = leaf_count(code);
             bool done = false;
             for (uint32_t k = 0; k < cnt && !done; k++) {
-                const float4 r0 = tris[3 * (first + k) + 0], r1 = tris[3 * (first + k) + 1], r2 = tris[3 * (first + k) + 2];
+                const float4* rec = tri_record(tris, first + k);
+                const float4 r0 = rec[0], r1 = rec[1], r2 = rec[2];
                 const uint32_t tid = __float_as_uint(r2.w);
                 if (tid == ignore) continue;
                 if (COUNT) n_tris++;
@@ -512,7 +590,7 @@ __device__ __forceinline__ void trace_persistent(const DevScene& sc, const float
                 }
             }
             if (ANY && done) { cur = STACK_SENTINEL; sp = 0; }
-            else if (sp > 0) { sp--; cur = RGK_POP(); }
+            else if (sp > 0) { sp--; cur = stk.pop(sp); }
             else cur = STACK_SENTINEL;
         }
         // ------------------------------------------------ retire finished rays
@@ -547,41 +625,33 @@ __device__ __forceinline__ void trace_persistent(const DevScene& sc, const float
             active = false;
         }
     }
-    if (COUNT && util && lane == 0) {
-        atomicAdd(&util[0], (unsigned long long)u_node_it); atomicAdd(&util[1], (unsigned long long)u_leaf_it);
-        atomicAdd(&util[2], (unsigned long long)u_outer_it); atomicAdd(&util[3], (unsigned long long)u_refill);
+    if (COUNT && !ANY && lane == 0) { // the closest-hit launches' lane occupancy per phase: stats[4..7]
+        atomicAdd(&stats[4], (unsigned long long)u_node_it); atomicAdd(&stats[5], (unsigned long long)u_leaf_it);
+        atomicAdd(&stats[6], (unsigned long long)u_outer_it); atomicAdd(&stats[7], (unsigned long long)u_refill);
     }
 }
 
 // ------------------------------------------------------------------ K2: closest hit
 template <bool COUNT, int STACK, int LDSN>
-__global__ __launch_bounds__(RGK_TRACE_BLOCK, (LDSN <= 16 ? RGK_TRACE_WAVES : 5)) void k_trace_closest(const DevScene sc, const float4* __restrict__ rayA,
-                                                                    const float4* __restrict__ rayB, const float2* __restrict__ nearfar,
-                                                                    float4* __restrict__ hit, const uint32_t* __restrict__ count_ptr,
-                                                                    uint32_t* __restrict__ fetch, unsigned long long* __restrict__ stats, int* __restrict__ ovf) {
+__global__ __launch_bounds__(RGK_TRACE_BLOCK, (LDSN <= 16 ? RGK_TRACE_WAVES : 5)) void k_trace_closest(
+    const DevScene sc, const float4* __restrict__ rayA, const float4* __restrict__ rayB, const float2* __restrict__ nearfar, float4* __restrict__ hit,
+    const uint32_t* __restrict__ count_ptr, uint32_t* __restrict__ fetch, unsigned long long* __restrict__ stats, int* __restrict__ ovf) {
     __shared__ int lds_stack[LDSN * RGK_TRACE_BLOCK];
     uint32_t n_nodes = 0, n_tris = 0;
-    trace_persistent<false, COUNT, STACK, LDSN>(sc, rayA, rayB, nullptr, nearfar, hit, nullptr, nullptr, 0, nullptr, *count_ptr, fetch,
-                                          lds_stack + threadIdx.x, ovf + (blockIdx.x * RGK_TRACE_BLOCK + threadIdx.x), gridDim.x * RGK_TRACE_BLOCK, n_nodes, n_tris, nullptr, nullptr, stats + 4);
-    if (COUNT) {
-        atomicAdd(&stats[0], (unsigned long long)n_nodes);
-        atomicAdd(&stats[1], (unsigned long long)n_tris);
-    }
+    trace_persistent<RayKind::Closest, COUNT, STACK, LDSN>(sc, rayA, rayB, nullptr, nearfar, hit, nullptr, nullptr, 0, nullptr, *count_ptr, fetch, lds_stack, ovf, n_nodes, n_tris, stats);
+    flush_walk_counts<COUNT>(stats, n_nodes, n_tris);
 }
 
 // K1 + K2 at bounce 0: the camera rays of a pass, generated where they are traced (no ray queue; hit[slot] out)
 template <bool COUNT, int STACK, int LDSN>
-__global__ __launch_bounds__(RGK_TRACE_BLOCK, (LDSN <= 16 ? RGK_TRACE_WAVES : 5)) void k_trace_camera(const DevScene sc, const DevCamera cam, const PassParams pp,
-                                                                    float4* __restrict__ hit, const uint32_t* __restrict__ count_ptr,
-                                                                    uint32_t* __restrict__ fetch, unsigned long long* __restrict__ stats, int* __restrict__ ovf) {
+__global__ __launch_bounds__(RGK_TRACE_BLOCK, (LDSN <= 16 ? RGK_TRACE_WAVES : 5)) void k_trace_camera(
+    const DevScene sc, const DevCamera cam, const PassParams pp, float4* __restrict__ hit, const uint32_t* __restrict__ count_ptr, uint32_t* __restrict__ fetch,
+    unsigned long long* __restrict__ stats, int* __restrict__ ovf) {
     __shared__ int lds_stack[LDSN * RGK_TRACE_BLOCK];
     uint32_t n_nodes = 0, n_tris = 0;
-    trace_persistent<false, COUNT, STACK, LDSN, true>(sc, nullptr, nullptr, nullptr, nullptr, hit, nullptr, nullptr, 0, nullptr, *count_ptr, fetch,
-                                          lds_stack + threadIdx.x, ovf + (blockIdx.x * RGK_TRACE_BLOCK + threadIdx.x), gridDim.x * RGK_TRACE_BLOCK, n_nodes, n_tris, &cam, &pp, stats + 4);
-    if (COUNT) {
-        atomicAdd(&stats[0], (unsigned long long)n_nodes);
-        atomicAdd(&stats[1], (unsigned long long)n_tris);
-    }
+    trace_persistent<RayKind::Camera, COUNT, STACK, LDSN>(sc, nullptr, nullptr, nullptr, nullptr, hit, nullptr, nullptr, 0, nullptr,
+        *count_ptr, fetch, lds_stack, ovf, n_nodes, n_tris, stats, &cam, &pp);
+    flush_walk_counts<COUNT>(stats, n_nodes, n_tris);
 }
 
 // ------------------------------------------------------------------ K1 + K2 at bounce 0, one lane per PIXEL: the beam walk
@@ -594,22 +664,23 @@ __global__ __launch_bounds__(RGK_TRACE_BLOCK, (LDSN <= 16 ? RGK_TRACE_WAVES : 5)
 // reached (the bundle reaches a superset, and a hit beyond the ray's own pruning distance loses to the nearer one anyway): the
 // same hit, bit for bit.  Node work per ray drops eight-fold; the 64 lanes of a wave are an 8 x 8 pixel block.
 // Capped entry lists (k_entry_points): rays that find nothing within the group's cap are walked again, together, from the root.
-#ifndef RGK_BEAM_WAVES
-#define RGK_BEAM_WAVES 4
-#endif
+// A lane's bundle in LDS, [entry][lane]: the 8 directions (24 floats), then the 8 nearest accepted distances.
+struct BeamRays {
+    float* ray;
+    __device__ __forceinline__ f3 d(const int k) const { return mk3(ray[(3 * k + 0) * RGK_TRACE_BLOCK], ray[(3 * k + 1) * RGK_TRACE_BLOCK], ray[(3 * k + 2) * RGK_TRACE_BLOCK]); }
+    __device__ __forceinline__ void set_d(const int k, const f3 v) const {
+        ray[(3 * k + 0) * RGK_TRACE_BLOCK] = v.x; ray[(3 * k + 1) * RGK_TRACE_BLOCK] = v.y; ray[(3 * k + 2) * RGK_TRACE_BLOCK] = v.z;
+    }
+    __device__ __forceinline__ float& best(const int k) const { return ray[(24 + k) * RGK_TRACE_BLOCK]; }
+};
 template <bool COUNT, int STACK, int LDSN>
-__global__ __launch_bounds__(RGK_TRACE_BLOCK, RGK_BEAM_WAVES) void k_trace_camera_beam(const DevScene sc, const DevCamera cam, const PassParams pp,
-                                                                    float4* hit, const uint32_t* __restrict__ count_ptr,
-                                                                    uint32_t* __restrict__ fetch, unsigned long long* __restrict__ stats, int* __restrict__ ovf_base) {
+__global__ __launch_bounds__(RGK_TRACE_BLOCK, RGK_BEAM_WAVES) void k_trace_camera_beam(
+    const DevScene sc, const DevCamera cam, const PassParams pp, float4* hit, const uint32_t* __restrict__ count_ptr, uint32_t* __restrict__ fetch,
+    unsigned long long* __restrict__ stats, int* __restrict__ ovf_base) {
     __shared__ int lds_stack[LDSN * RGK_TRACE_BLOCK];
-    __shared__ float lds_ray[32 * RGK_TRACE_BLOCK]; // per lane, [entry][lane]: the 8 directions (24 floats) and the 8 nearest accepted distances
-    int* __restrict__ stack = lds_stack + threadIdx.x;
-    float* __restrict__ ray = lds_ray + threadIdx.x;
-#define RGK_D(k_) mk3(ray[(3 * (k_) + 0) * RGK_TRACE_BLOCK], ray[(3 * (k_) + 1) * RGK_TRACE_BLOCK], ray[(3 * (k_) + 2) * RGK_TRACE_BLOCK])
-#define RGK_BEST(k_) ray[(24 + (k_)) * RGK_TRACE_BLOCK]
-    int* __restrict__ ovf = ovf_base + (blockIdx.x * RGK_TRACE_BLOCK + threadIdx.x);
-    const uint32_t ostride = gridDim.x * RGK_TRACE_BLOCK;
-    const int stride = RGK_TRACE_BLOCK;
+    __shared__ float lds_ray[32 * RGK_TRACE_BLOCK]; // BeamRays
+    const LaneStack<STACK, LDSN> stk = lane_stack<STACK, LDSN>(lds_stack, ovf_base);
+    const BeamRays rays = {lds_ray + threadIdx.x};
     const int lane = threadIdx.x & 63;
     const float eps = sc.epsilon;
     const int walk_q = (int)sc.walk_q;
@@ -617,9 +688,8 @@ __global__ __launch_bounds__(RGK_TRACE_BLOCK, RGK_BEAM_WAVES) void k_trace_camer
     const float4* __restrict__ tris = reinterpret_cast<const float4*>(sc.tris);
     const SamplerTab tb = {pp.htab, pp.multisample};
     const uint32_t count = (*count_ptr) >> 3; // bundles: 8 slots each
-    const uint32_t chunk = fetch_chunk(count, gridDim.x * (RGK_TRACE_BLOCK / 64), 16u);
-    const uint32_t n_waves = gridDim.x * (RGK_TRACE_BLOCK / 64), wave_id = blockIdx.x * (RGK_TRACE_BLOCK / 64) + (threadIdx.x >> 6);
-    uint32_t w_next = min(wave_id * chunk, count), w_end = min(w_next + chunk, count); // first slice dealt statically (see trace_persistent)
+    const uint32_t chunk = fetch_chunk(count, walk_waves(), 16u);
+    uint32_t w_next = first_slice(chunk, count), w_end = min(w_next + chunk, count);
     bool exhausted = false;
     uint32_t n_nodes = 0, n_tris = 0;
     // per-lane bundle state
@@ -638,7 +708,7 @@ __global__ __launch_bounds__(RGK_TRACE_BLOCK, RGK_BEAM_WAVES) void k_trace_camer
         f3 dmin = mk3(__builtin_inff(), __builtin_inff(), __builtin_inff()), dmax = -dmin;                                             \
         btlo = __builtin_inff();                                                                                                       \
         for (int k = 0; k < 8; k++) if (valid & (1u << k)) {                                                                          \
-            const f3 dk_ = RGK_D(k);                                                                                                   \
+            const f3 dk_ = rays.d(k);                                                                                                  \
             dmin = mk3(fminf(dmin.x, dk_.x), fminf(dmin.y, dk_.y), fminf(dmin.z, dk_.z));                                              \
             dmax = mk3(fmaxf(dmax.x, dk_.x), fmaxf(dmax.y, dk_.y), fmaxf(dmax.z, dk_.z));                                              \
             float t0_, t1_; (void)clip_to_scene(sc, o, dk_, 0.0f, 10000.0f, t0_, t1_); btlo = fminf(btlo, t0_ - eps);                  \
@@ -661,10 +731,7 @@ __global__ __launch_bounds__(RGK_TRACE_BLOCK, RGK_BEAM_WAVES) void k_trace_camer
         const int nact = __popcll(act);
         if (nact <= RGK_REFILL_BELOW && !(exhausted && w_next >= w_end)) {
             if (w_next >= w_end) {
-                uint32_t base = 0;
-                if (n_waves * chunk >= count) base = count;
-                else if (lane == 0) base = atomicAdd(fetch, chunk) + n_waves * chunk;
-                base = __builtin_amdgcn_readfirstlane(base);
+                const uint32_t base = next_slice(fetch, chunk, count, lane);
                 if (base >= count) exhausted = true;
                 else { w_next = base; w_end = min(base + chunk, count); }
             }
@@ -680,12 +747,11 @@ __global__ __launch_bounds__(RGK_TRACE_BLOCK, RGK_BEAM_WAVES) void k_trace_camer
                         const float2 jit = sample2d_t(tb, seed, pp.s0 + (sb << 3) + (uint32_t)k, 0);
                         f3 dk;
                         camera_ray(cam, (int)(pix & 0xffff), (int)(pix >> 16), (int)pp.xres, (int)pp.yres, jit, make_float2(0.f, 0.f), o, dk);
-                        ray[(3 * k + 0) * RGK_TRACE_BLOCK] = dk.x; ray[(3 * k + 1) * RGK_TRACE_BLOCK] = dk.y; ray[(3 * k + 2) * RGK_TRACE_BLOCK] = dk.z;
-                        RGK_BEST(k) = __builtin_inff();
+                        rays.set_d(k, dk);
+                        rays.best(k) = __builtin_inff();
                         hit[((size_t)idx << 3) + k] = make_float4(__builtin_inff(), 0.f, 0.f, __int_as_float(-1));
-                        const bool nan_ray = (o.x != o.x) | (o.y != o.y) | (o.z != o.z) | (dk.x != dk.x) | (dk.y != dk.y) | (dk.z != dk.z);
                         float t0, t1;
-                        if (!nan_ray && clip_to_scene(sc, o, dk, 0.0f, 10000.0f, t0, t1)) valid |= 1u << k;
+                        if (!ray_has_nan(o, dk) && clip_to_scene(sc, o, dk, 0.0f, 10000.0f, t0, t1)) valid |= 1u << k;
                     }
                     sp = 0;
                     cur = STACK_SENTINEL;
@@ -702,7 +768,7 @@ __global__ __launch_bounds__(RGK_TRACE_BLOCK, RGK_BEAM_WAVES) void k_trace_camer
                             const int* e = pp.entry + grp * RGK_ENTRY_K;
                             cur = e[0];
 #pragma unroll
-                            for (int k = RGK_ENTRY_K - 1; k >= 1; k--) { const int r = e[k]; if (r != STACK_SENTINEL) { RGK_PUT(r) sp++; } }
+                            for (int k = RGK_ENTRY_K - 1; k >= 1; k--) { const int r = e[k]; if (r != STACK_SENTINEL) { stk.put(sp, r); sp++; } }
                         }
                     }
                     active = true;
@@ -724,18 +790,15 @@ __global__ __launch_bounds__(RGK_TRACE_BLOCK, RGK_BEAM_WAVES) void k_trace_camer
             if (!walking) continue;
             if (COUNT) n_nodes++;
             const float limit = fminf(bmax, capd);
-            const float4 n0 = nodes[4 * cur + 0], n1 = nodes[4 * cur + 1], n2 = nodes[4 * cur + 2], n3 = nodes[4 * cur + 3];
-            const float sx = n0.w, sy = n3.z, sz = n3.w;
-            const float px = n0.x - o.x, py = n0.y - o.y, pz = n0.z - o.z;
-            const uint32_t mx = axis_mode & 3u, my = (axis_mode >> 2) & 3u, mz = (axis_mode >> 4) & 3u;
-            const uint32_t lx = __float_as_uint(n2.x), ly = __float_as_uint(n2.y), lz = __float_as_uint(n2.z);
-            const uint32_t hx = __float_as_uint(n2.w), hy = __float_as_uint(n3.x), hz = __float_as_uint(n3.y);
-            const uint32_t nx = mx == 1u ? hx : lx, fx = mx == 1u ? lx : hx; // near / far plane words by the bundle's direction sign
-            const uint32_t ny = my == 1u ? hy : ly, fy = my == 1u ? ly : hy;
-            const uint32_t nz = mz == 1u ? hz : lz, fz = mz == 1u ? lz : hz;
             float te[4];
             int ref[4];
-            ref[0] = __float_as_int(n1.x); ref[1] = __float_as_int(n1.y); ref[2] = __float_as_int(n1.z); ref[3] = __float_as_int(n1.w);
+            const NodeWords n = node_words(nodes, cur, ref[0], ref[1], ref[2], ref[3]);
+            const float sx = n.sx, sy = n.sy, sz = n.sz;
+            const float px = n.p.x - o.x, py = n.p.y - o.y, pz = n.p.z - o.z;
+            const uint32_t mx = axis_mode & 3u, my = (axis_mode >> 2) & 3u, mz = (axis_mode >> 4) & 3u;
+            const uint32_t nx = mx == 1u ? n.hx : n.lx, fx = mx == 1u ? n.lx : n.hx; // near / far plane words by the bundle's direction sign
+            const uint32_t ny = my == 1u ? n.hy : n.ly, fy = my == 1u ? n.ly : n.hy;
+            const uint32_t nz = mz == 1u ? n.hz : n.lz, fz = mz == 1u ? n.lz : n.hz;
 #pragma unroll
             for (int c = 0; c < 4; c++) {
                 // plane - origin, then its distance over the bundle: the interval product (plane - o) * [imin, imax]
@@ -754,27 +817,25 @@ __global__ __launch_bounds__(RGK_TRACE_BLOCK, RGK_BEAM_WAVES) void k_trace_camer
                 te[c] = h ? tn : __builtin_inff();
                 if (!h) ref[c] = STACK_SENTINEL;
             }
-#define RGK_CSWAP(a, b) { const bool sw = te[b] < te[a]; const float tt = sw ? te[b] : te[a], tu = sw ? te[a] : te[b]; \
-                          const int rr = sw ? ref[b] : ref[a], ru = sw ? ref[a] : ref[b]; te[a] = tt; te[b] = tu; ref[a] = rr; ref[b] = ru; }
-            RGK_CSWAP(0, 1) RGK_CSWAP(2, 3) RGK_CSWAP(0, 2) RGK_CSWAP(1, 3) RGK_CSWAP(1, 2)
-#undef RGK_CSWAP
-            RGK_PUT(ref[3]) sp += (ref[3] != STACK_SENTINEL);
-            RGK_PUT(ref[2]) sp += (ref[2] != STACK_SENTINEL);
-            RGK_PUT(ref[1]) sp += (ref[1] != STACK_SENTINEL);
+            sort4(te[0], te[1], te[2], te[3], ref[0], ref[1], ref[2], ref[3]);
+            stk.put(sp, ref[3]); sp += (ref[3] != STACK_SENTINEL);
+            stk.put(sp, ref[2]); sp += (ref[2] != STACK_SENTINEL);
+            stk.put(sp, ref[1]); sp += (ref[1] != STACK_SENTINEL);
             cur = ref[0];
-            if (cur == STACK_SENTINEL && sp > 0) { sp--; cur = RGK_POP(); }
+            if (cur == STACK_SENTINEL && sp > 0) { sp--; cur = stk.pop(sp); }
         }
         // ------------------------------------------------ leaf: every triangle of it against every sample of the bundle
         if (active && cur < 0) {
             const uint32_t code = ~(uint32_t)cur;
-            const uint32_t first = code >> 4, cnt = (code & 15u) + 1u;
+            const uint32_t first = leaf_first(code), cnt = leaf_count(code);
             for (uint32_t k = 0; k < cnt; k++) {
-                const float4 r0 = tris[3 * (first + k) + 0], r1 = tris[3 * (first + k) + 1], r2 = tris[3 * (first + k) + 2];
+                const float4* rec = tri_record(tris, first + k);
+                const float4 r0 = rec[0], r1 = rec[1], r2 = rec[2];
                 const int tid = (int)__float_as_uint(r2.w);
                 if (COUNT) n_tris += (uint32_t)__popc(valid);
                 for (int q = 0; q < 8; q++) {
                     if (!(valid & (1u << q))) continue;
-                    const f3 dq = RGK_D(q);
+                    const f3 dq = rays.d(q);
                     float t, al, be;
                     if (!tri_test(r0, r1, r2, o, dq, eps, t, al, be)) continue;
                     // the ray's own acceptance window: its [near, far] clipped to the scene box (and to the group's cap)
@@ -782,22 +843,22 @@ __global__ __launch_bounds__(RGK_TRACE_BLOCK, RGK_BEAM_WAVES) void k_trace_camer
                     (void)clip_to_scene(sc, o, dq, 0.0f, 10000.0f, t0, t1);
                     const float thi = capped ? fminf(t1 + eps, capd) : t1 + eps;
                     if (t < t0 - eps || t > thi) continue;
-                    const float bq = RGK_BEST(q);
+                    const float bq = rays.best(q);
                     bool take = t < bq;
                     if (t == bq) take = tid > __float_as_int(hit[((size_t)idx << 3) + q].w); // an exact tie: the higher triangle id (its own earlier write, same lane)
-                    if (take) { RGK_BEST(q) = t; hit[((size_t)idx << 3) + q] = make_float4(t, al, be, __int_as_float(tid)); }
+                    if (take) { rays.best(q) = t; hit[((size_t)idx << 3) + q] = make_float4(t, al, be, __int_as_float(tid)); }
                 }
             }
             bmax = 0.f; // nothing beyond the farthest sample's nearest hit can matter to any of them
-            for (int q = 0; q < 8; q++) if (valid & (1u << q)) bmax = fmaxf(bmax, RGK_BEST(q));
-            if (sp > 0) { sp--; cur = RGK_POP(); }
+            for (int q = 0; q < 8; q++) if (valid & (1u << q)) bmax = fmaxf(bmax, rays.best(q));
+            if (sp > 0) { sp--; cur = stk.pop(sp); }
             else cur = STACK_SENTINEL;
         }
         // ------------------------------------------------ retire: walk again from the root for samples the capped list left empty-handed
         if (active && cur == STACK_SENTINEL) {
             uint32_t again = 0;
             if (capped) {
-                for (int q = 0; q < 8; q++) if ((valid & (1u << q)) && RGK_BEST(q) == __builtin_inff()) again |= 1u << q;
+                for (int q = 0; q < 8; q++) if ((valid & (1u << q)) && rays.best(q) == __builtin_inff()) again |= 1u << q;
             }
             if (again) {
                 valid = again; capped = false; capd = __builtin_inff(); bmax = __builtin_inff();
@@ -807,96 +868,66 @@ __global__ __launch_bounds__(RGK_TRACE_BLOCK, RGK_BEAM_WAVES) void k_trace_camer
         }
     }
 #undef RGK_BEAM_BOUNDS
-#undef RGK_D
-#undef RGK_BEST
-    if (COUNT) {
-        atomicAdd(&stats[0], (unsigned long long)n_nodes);
-        atomicAdd(&stats[1], (unsigned long long)n_tris);
-    }
+    flush_walk_counts<COUNT>(stats, n_nodes, n_tris);
 }
 
 // ------------------------------------------------------------------ K5: shadow rays + accumulate
 // shA = (o.xyz, d.x)  shB = (d.y, d.z, far, slot)  shC = (radiance.rgb, near)
 template <bool COUNT, int STACK, int LDSN>
-__global__ __launch_bounds__(RGK_TRACE_BLOCK, (LDSN <= 16 ? RGK_TRACE_WAVES : 5)) void k_trace_shadow(const DevScene sc, const float4* __restrict__ shA,
-                                                                   const float4* __restrict__ shB, const float4* __restrict__ shC,
-                                                                   float4* __restrict__ tot, uint8_t* __restrict__ vis_out,
-                                                                   const int mode, float* __restrict__ splat_rgb,
-                                                                   const uint32_t* __restrict__ count_ptr, uint32_t* __restrict__ fetch,
-                                                                   unsigned long long* __restrict__ stats, int* __restrict__ ovf) {
+__global__ __launch_bounds__(RGK_TRACE_BLOCK, (LDSN <= 16 ? RGK_TRACE_WAVES : 5)) void k_trace_shadow(
+    const DevScene sc, const float4* __restrict__ shA, const float4* __restrict__ shB, const float4* __restrict__ shC, float4* __restrict__ tot,
+    uint8_t* __restrict__ vis_out, const int mode, float* __restrict__ splat_rgb, const uint32_t* __restrict__ count_ptr, uint32_t* __restrict__ fetch,
+    unsigned long long* __restrict__ stats, int* __restrict__ ovf) {
     __shared__ int lds_stack[LDSN * RGK_TRACE_BLOCK];
     uint32_t n_nodes = 0, n_tris = 0;
-    trace_persistent<true, COUNT, STACK, LDSN>(sc, shA, shB, shC, nullptr, nullptr, tot, vis_out, mode, splat_rgb, *count_ptr, fetch,
-                                         lds_stack + threadIdx.x, ovf + (blockIdx.x * RGK_TRACE_BLOCK + threadIdx.x), gridDim.x * RGK_TRACE_BLOCK, n_nodes, n_tris);
-    if (COUNT) {
-        atomicAdd(&stats[2], (unsigned long long)n_nodes);
-        atomicAdd(&stats[3], (unsigned long long)n_tris);
-    }
+    trace_persistent<RayKind::Shadow, COUNT, STACK, LDSN>(sc, shA, shB, shC, nullptr, nullptr, tot, vis_out, mode, splat_rgb, *count_ptr, fetch, lds_stack, ovf, n_nodes, n_tris, stats);
+    flush_walk_counts<COUNT>(stats + 2, n_nodes, n_tris);
 }
 // ... with the 32-byte records of the constant-light route: shA = (d.xyz, far)  shB = (radiance.rgb, slot); o = sc.cl_pos, near = 20 eps
 template <bool COUNT, int STACK, int LDSN>
-__global__ __launch_bounds__(RGK_TRACE_BLOCK, (LDSN <= 16 ? RGK_TRACE_WAVES : 5)) void k_trace_shadow_cl(const DevScene sc, const float4* __restrict__ shA,
-                                                                   const float4* __restrict__ shB, float4* __restrict__ tot,
-                                                                   const uint32_t* __restrict__ count_ptr, uint32_t* __restrict__ fetch,
-                                                                   unsigned long long* __restrict__ stats, int* __restrict__ ovf) {
+__global__ __launch_bounds__(RGK_TRACE_BLOCK, (LDSN <= 16 ? RGK_TRACE_WAVES : 5)) void k_trace_shadow_cl(
+    const DevScene sc, const float4* __restrict__ shA, const float4* __restrict__ shB, float4* __restrict__ tot, const uint32_t* __restrict__ count_ptr,
+    uint32_t* __restrict__ fetch, unsigned long long* __restrict__ stats, int* __restrict__ ovf) {
     __shared__ int lds_stack[LDSN * RGK_TRACE_BLOCK];
     uint32_t n_nodes = 0, n_tris = 0;
-    trace_persistent<true, COUNT, STACK, LDSN, false, false, true>(sc, shA, shB, nullptr, nullptr, nullptr, tot, nullptr, RGK_SHADOW_ADD, nullptr, *count_ptr, fetch,
-                                         lds_stack + threadIdx.x, ovf + (blockIdx.x * RGK_TRACE_BLOCK + threadIdx.x), gridDim.x * RGK_TRACE_BLOCK, n_nodes, n_tris);
-    if (COUNT) {
-        atomicAdd(&stats[2], (unsigned long long)n_nodes);
-        atomicAdd(&stats[3], (unsigned long long)n_tris);
-    }
+    trace_persistent<RayKind::ShadowConstLight, COUNT, STACK, LDSN>(sc, shA, shB, nullptr, nullptr, nullptr, tot, nullptr, RGK_SHADOW_ADD, nullptr,
+        *count_ptr, fetch, lds_stack, ovf, n_nodes, n_tris, stats);
+    flush_walk_counts<COUNT>(stats + 2, n_nodes, n_tris);
 }
 
 // K5 for bidirectional rounds: one queue entry per camera-path vertex (JOB above).  jobs = {vertex}{contribution, mask}{emission},
 // rads = one radiance per ray (k_connect wrote both, and counted the rays).
-#ifndef RGK_JOB_WAVES
-#define RGK_JOB_WAVES 6 // the vertex state costs ~12 VGPRs over a plain shadow ray: 8 waves per SIMD would spill 44 bytes
-#endif
 template <bool COUNT, int STACK, int LDSN>
-__global__ __launch_bounds__(RGK_TRACE_BLOCK, (LDSN <= 16 ? RGK_JOB_WAVES : 5)) void k_trace_shadow_jobs(const DevScene sc, const PassParams pp, const float4* __restrict__ jobs,
-                                                                   const float4* __restrict__ rads, float4* __restrict__ tot,
-                                                                   const uint32_t* __restrict__ count_ptr, uint32_t* __restrict__ fetch,
-                                                                   unsigned long long* __restrict__ stats, int* __restrict__ ovf) {
+__global__ __launch_bounds__(RGK_TRACE_BLOCK, (LDSN <= 16 ? RGK_JOB_WAVES : 5)) void k_trace_shadow_jobs(
+    const DevScene sc, const PassParams pp, const float4* __restrict__ jobs, const float4* __restrict__ rads, float4* __restrict__ tot,
+    const uint32_t* __restrict__ count_ptr, uint32_t* __restrict__ fetch, unsigned long long* __restrict__ stats, int* __restrict__ ovf) {
     __shared__ int lds_stack[LDSN * RGK_TRACE_BLOCK];
     uint32_t n_nodes = 0, n_tris = 0;
-    trace_persistent<true, COUNT, STACK, LDSN, false, true>(sc, jobs, rads, nullptr, nullptr, nullptr, tot, nullptr, RGK_SHADOW_ADD, nullptr, *count_ptr, fetch,
-                                         lds_stack + threadIdx.x, ovf + (blockIdx.x * RGK_TRACE_BLOCK + threadIdx.x), gridDim.x * RGK_TRACE_BLOCK, n_nodes, n_tris, nullptr, &pp);
-    if (COUNT) {
-        atomicAdd(&stats[2], (unsigned long long)n_nodes);
-        atomicAdd(&stats[3], (unsigned long long)n_tris);
-    }
+    trace_persistent<RayKind::ShadowJobs, COUNT, STACK, LDSN>(sc, jobs, rads, nullptr, nullptr, nullptr, tot, nullptr, RGK_SHADOW_ADD, nullptr,
+        *count_ptr, fetch, lds_stack, ovf, n_nodes, n_tris, stats, nullptr, &pp);
+    flush_walk_counts<COUNT>(stats + 2, n_nodes, n_tris);
 }
 
 // K5 for the first vertex of a pass in a single-light scene: the same walker, started at the pixel group's light-side entry nodes
 template <bool COUNT, int STACK, int LDSN>
-__global__ __launch_bounds__(RGK_TRACE_BLOCK, (LDSN <= 16 ? RGK_TRACE_WAVES : 5)) void k_trace_shadow_first(const DevScene sc, const PassParams pp, const float4* __restrict__ shA,
-                                                                   const float4* __restrict__ shB, const float4* __restrict__ shC,
-                                                                   float4* __restrict__ tot, const uint32_t* __restrict__ count_ptr, uint32_t* __restrict__ fetch,
-                                                                   unsigned long long* __restrict__ stats, int* __restrict__ ovf) {
+__global__ __launch_bounds__(RGK_TRACE_BLOCK, (LDSN <= 16 ? RGK_TRACE_WAVES : 5)) void k_trace_shadow_first(
+    const DevScene sc, const PassParams pp, const float4* __restrict__ shA, const float4* __restrict__ shB, const float4* __restrict__ shC, float4* __restrict__ tot,
+    const uint32_t* __restrict__ count_ptr, uint32_t* __restrict__ fetch, unsigned long long* __restrict__ stats, int* __restrict__ ovf) {
     __shared__ int lds_stack[LDSN * RGK_TRACE_BLOCK];
     uint32_t n_nodes = 0, n_tris = 0;
-    trace_persistent<true, COUNT, STACK, LDSN>(sc, shA, shB, shC, nullptr, nullptr, tot, nullptr, RGK_SHADOW_ADD, nullptr, *count_ptr, fetch,
-                                         lds_stack + threadIdx.x, ovf + (blockIdx.x * RGK_TRACE_BLOCK + threadIdx.x), gridDim.x * RGK_TRACE_BLOCK, n_nodes, n_tris, nullptr, &pp);
-    if (COUNT) {
-        atomicAdd(&stats[2], (unsigned long long)n_nodes);
-        atomicAdd(&stats[3], (unsigned long long)n_tris);
-    }
+    trace_persistent<RayKind::Shadow, COUNT, STACK, LDSN>(sc, shA, shB, shC, nullptr, nullptr, tot, nullptr, RGK_SHADOW_ADD, nullptr,
+        *count_ptr, fetch, lds_stack, ovf, n_nodes, n_tris, stats, nullptr, &pp);
+    flush_walk_counts<COUNT>(stats + 2, n_nodes, n_tris);
 }
 
 // ... with the 32-byte records of the constant-light route (k_trace_shadow_cl)
 template <bool COUNT, int STACK, int LDSN>
-__global__ __launch_bounds__(RGK_TRACE_BLOCK, (LDSN <= 16 ? RGK_TRACE_WAVES : 5)) void k_trace_shadow_first_cl(const DevScene sc, const PassParams pp, const float4* __restrict__ shA,
-                                                                   const float4* __restrict__ shB, float4* __restrict__ tot,
-                                                                   const uint32_t* __restrict__ count_ptr, uint32_t* __restrict__ fetch,
-                                                                   unsigned long long* __restrict__ stats, int* __restrict__ ovf) {
+__global__ __launch_bounds__(RGK_TRACE_BLOCK, (LDSN <= 16 ? RGK_TRACE_WAVES : 5)) void k_trace_shadow_first_cl(
+    const DevScene sc, const PassParams pp, const float4* __restrict__ shA, const float4* __restrict__ shB, float4* __restrict__ tot, const uint32_t* __restrict__ count_ptr,
+    uint32_t* __restrict__ fetch, unsigned long long* __restrict__ stats, int* __restrict__ ovf) {
     __shared__ int lds_stack[LDSN * RGK_TRACE_BLOCK];
     uint32_t n_nodes = 0, n_tris = 0;
-    trace_persistent<true, COUNT, STACK, LDSN, false, false, true>(sc, shA, shB, nullptr, nullptr, nullptr, tot, nullptr, RGK_SHADOW_ADD, nullptr, *count_ptr, fetch,
-                                         lds_stack + threadIdx.x, ovf + (blockIdx.x * RGK_TRACE_BLOCK + threadIdx.x), gridDim.x * RGK_TRACE_BLOCK, n_nodes, n_tris, nullptr, &pp);
-    if (COUNT) {
-        atomicAdd(&stats[2], (unsigned long long)n_nodes);
-        atomicAdd(&stats[3], (unsigned long long)n_tris);
-    }
+    trace_persistent<RayKind::ShadowConstLight, COUNT, STACK, LDSN>(sc, shA, shB, nullptr, nullptr, nullptr, tot, nullptr, RGK_SHADOW_ADD, nullptr,
+        *count_ptr, fetch, lds_stack, ovf, n_nodes, n_tris, stats, nullptr, &pp);
+    flush_walk_counts<COUNT>(stats + 2, n_nodes, n_tris);
 }

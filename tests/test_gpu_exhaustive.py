@@ -264,3 +264,98 @@ def test_feature_pass_equals_the_exhaustive_search_on_every_pixel(rd, oracle, na
         assert not bad.any(), (name, size, builder, int(bad.sum()), np.argwhere(bad)[:5].tolist())
         g.close()
     assert (ex["tri"] >= 0).mean() > (0.9 if name != "count65" else 0.08)
+
+
+# ----------------------------------------------------------------------- rounds under every stack variant
+ROUND_W, ROUND_H, ROUND_SPP, ROUND_DEPTH = 67, 45, 8, 5     # ragged in x and y; 8 spp: gshift = 3, the beam walker is taken when asked
+ROUND_VARIANTS = {   # scene -> the variants held to the default ("host-sah": 256/16)
+    "small": ("host-sah-stack256-lds32", "host-sah-stack32-lds32"),
+    "deep": ("host-sah-stack256-lds16", "host-sah-stack256-lds32"),     # 68 stack entries: the two that overflow into global memory
+}
+
+
+def _round_scene(name):
+    """(builder, camera): small_scene() of test_gpu_const_light.py, or trace_ref's `deep` scene lit by one point light."""
+    import test_gpu_const_light as CL
+    if name == "small":
+        return CL.small_scene(), make_camera((0, 1.5, 5.5), (0, 1.3, 0), (0, 1, 0), fov=45, xres=ROUND_W, yres=ROUND_H, focus_plane=5.0)
+    sb = T.SCENES["deep"]()
+    sb.add_point_light((0.7, 1.2, 0.9), (1.0, 0.95, 0.8), 6.0, 0.0)
+    sb.set_skybox_color((0.55, 0.7, 0.9), 0.8)
+    # looking down the progression from beyond its coarse end: the levels line up behind each other, 40 % of the pixels see a triangle
+    return sb, make_camera((1.3, 0.02, 0.05), (0, 0, 0), (0, 1, 0), fov=70, xres=ROUND_W, yres=ROUND_H)
+
+
+def _round_params(reverse=0):
+    return make_params(ROUND_W, ROUND_H, ROUND_SPP, ROUND_DEPTH, clamp=30.0, russian=0.7, bumpscale=2.0, reverse=reverse)
+
+
+def _variant_scene(rd, scene, sb, builder):
+    g = gpu_scene(rd, sb, builder)
+    depth = g.info().max_depth
+    if scene == "deep":
+        assert depth >= 11, depth          # 3 pushes per level: more than 32 stack entries possible
+    else:
+        assert depth <= 7, depth           # shallow enough for the all-LDS 32/32 walker (see CASES above)
+    return g
+
+
+def _two_rounds(g, cam, prm, tiles, **tuning):
+    """Two rounds of one frame in separate accumulators: the second runs on capped entry lists."""
+    g.set_tuning(**tuning)
+    out = [g.render_round(cam, prm, tiles) for _ in range(2)]
+    g.close()
+    return out
+
+
+ROUND_CASES = [(scene, cl, beam, 0) for scene in ("small", "deep") for cl in (0, 1) for beam in (0, 2)] + [("small", 1, 1, 3)]
+
+
+@functools.lru_cache(maxsize=None)
+def _small_scene_split(oracle):
+    """Once: the oracle's bidirectional round on the small scene, split into its terms, every ray answered by exhaustive search."""
+    sb, cam = _round_scene("small")
+    return oracle.OracleScene(sb.to_desc()).render_round_split(cam, _round_params(reverse=3), oracle.generate_task_list(ROUND_W, ROUND_H), exhaustive=True)
+
+
+@pytest.mark.parametrize("scene,const_light,beam,reverse", ROUND_CASES, ids=[f"{s}-const_light{c}-beam{b}-reverse{r}" for s, c, b, r in ROUND_CASES])
+def test_rounds_do_not_depend_on_the_stack_variant(rd, oracle, scene, const_light, beam, reverse):
+    """The walkers that only rounds reach -- k_trace_camera, k_trace_camera_beam (beam = 2: in both rounds), k_trace_shadow_first,
+    the two constant-light kernels and, with reverse = 3, k_trace_shadow_jobs and the splat mode of k_trace_shadow -- under the
+    <STACK, LDSN> variants that the tests above reach through k_trace_closest and k_trace_shadow alone.  Two rounds of one frame
+    per variant, the second on capped entry lists.  (32/32 has no overflow area and never takes the beam walker, rgk_plan.h
+    rgk_beam_taken: its camera rays go through k_trace_camera under either switch value.)
+
+    reverse = 0: accumulator, sample counts and the path / ray counters of both rounds are the default variant's, bit for bit.
+
+    reverse = 3 (small scene, every variant, the default included): splat order is not repeatable, so two GPU runs are not
+    compared bit for bit; each round is held per pixel to the oracle's terms (tests/bdpt_ref.py check_round, as
+    test_gpu_bdpt.check_case does): no pixel outside the summation-order bound, the bit-exact classes exact, sample counts,
+    paths and path_rays the oracle's, shadow_rays at most the oracle's, and all three counters equal between the variants.  The
+    oracle's rays are answered by exhaustive search, the rule the walkers are pinned to: on this scene's bump-mapped surfaces the
+    kd-tree oracle decides some in-surface connection rays inside its epsilon band
+    (test_gpu_const_light.test_bidirectional_round_on_an_eligible_scene), which says nothing about a stack."""
+    import bdpt_ref as B
+    sb, cam = _round_scene(scene)
+    prm, tiles = _round_params(reverse), rd.generate_task_list(ROUND_W, ROUND_H)
+    runs = {}
+    for builder in ("host-sah",) + ROUND_VARIANTS[scene]:
+        g = _variant_scene(rd, scene, sb, builder)
+        assert g.info().const_light == 1
+        runs[builder] = _two_rounds(g, cam, prm, tiles, const_light=const_light, beam=beam)
+    base = runs["host-sah"]
+    assert base[0][2].path_rays > ROUND_W * ROUND_H * ROUND_SPP and base[0][2].shadow_rays > 1000 and float(base[0][0].max()) > 0.0
+    tag = f"gpu_exhaustive[rounds {scene} const_light{const_light} beam{beam} reverse{reverse}"
+    for builder, rounds in runs.items():
+        for r, ((a0, c0, k0), (a1, c1, k1)) in enumerate(zip(base, rounds)):
+            assert (k0.paths, k0.path_rays, k0.shadow_rays) == (k1.paths, k1.path_rays, k1.shadow_rays), (builder, r)
+            if reverse:
+                split = _small_scene_split(oracle)
+                planes, s = B.check_split(a1, c1, split)
+                record_parity(f"{tag} {builder} round {r}]", **B.record_fields(s), path_rays_delta=int(k1.path_rays) - int(split.counters.path_rays))
+                assert split.n_splats > 0 and s["counts_equal"] and s["bad_values"] == 0 and s["outside"] == 0 and s["exact_n0"] == s["exact_n1"] == 1.0, (builder, r, s)
+                assert k1.path_rays == split.counters.path_rays and k1.paths == split.counters.paths and k1.shadow_rays <= split.counters.shadow_rays, (builder, r)
+            elif builder != "host-sah":
+                differ = int((a0.view(np.uint32) != a1.view(np.uint32)).any(axis=2).sum())
+                record_parity(f"{tag} {builder} round {r}]", pixels=ROUND_W * ROUND_H, differing=differ)
+                assert differ == 0 and np.array_equal(c0, c1), (builder, r, differ)
