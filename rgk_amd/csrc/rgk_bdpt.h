@@ -8,7 +8,7 @@
 //   k_raygen_light -> [k_trace_closest -> k_list_hits -> k_shade_light -> k_trace_shadow(splat)] x reverse
 //   [k_trace_camera | k_trace_closest -> k_shade<BDPT> -> k_connect -> k_trace_shadow(add) + k_trace_shadow_jobs] x depth
 // Light vertices live per slot in pp.lv, which of them exist in pp.lvmask.  The camera path is the unidirectional pipeline
-// (rgk_kernels.hip k_shade: no ray-generation kernel, camera rays made where they are traced and shaded) -- a vertex whose
+// (rgk_shade.h k_shade: no ray-generation kernel, camera rays made where they are traced and shaded) -- a vertex whose
 // slot has no light vertex, and that does not emit, IS a unidirectional vertex: its NEE ray goes to the plain shadow queue.
 // The others leave a record; k_connect evaluates their connections and queues ONE entry per vertex (the vertex, its
 // contribution, one radiance per ray: the 1 + reverse shadow rays all end at the vertex and start at points the slot already
@@ -20,26 +20,7 @@
 // so the light-vertex shading runs over full waves (it had 8 % of its lanes busy).
 #pragma once
 #include <hip/hip_runtime.h>
-#include "rgk_device.h"
-#include "rgk_kernels.h"
-
-// Workgroup-level append: returns this lane's position in the queue behind `counter` (valid only
-// when flag).  Two barriers; every thread of the workgroup must call it the same number of times.
-__device__ __forceinline__ uint32_t block_append(bool flag, uint32_t* counter, uint32_t* s_cnt, uint32_t* s_base) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const unsigned long long m = __ballot(flag);
-    if (lane == 0) s_cnt[w] = __popcll(m);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t t = 0;
-        for (int k = 0; k < RGK_LIGHT_BLOCK / 64; k++) { uint32_t a = s_cnt[k]; s_cnt[k] = t; t += a; }
-        *s_base = t ? atomicAdd(counter, t) : 0u;
-    }
-    __syncthreads();
-    const uint32_t p = *s_base + s_cnt[w] + __popcll(m & ((1ull << lane) - 1ull));
-    __syncthreads();
-    return p;
-}
+#include "rgk_shade.h" // block_append, path_step
 
 __device__ __forceinline__ float4* lv_ptr(const PassParams& pp, uint32_t k, uint32_t c, uint32_t slot) {
     return pp.lv + ((size_t)(k * RGK_LV_FLOAT4 + c) * pp.batch + slot);
@@ -68,9 +49,8 @@ __global__ __launch_bounds__(RGK_LIGHT_BLOCK) void k_raygen_light(const DevScene
         bool queue = false;
         float4 a = make_float4(0, 0, 0, 0), b = a, li = a, ls = a;
         if (slot < n) {
-            uint32_t srel, j; slot_decode(pp, slot, j, srel);
-            const uint32_t seed = pp.pix_seed[pp.j0 + j], s = pp.s0 + srel;
-            const uint32_t base2d = (cam.lens_size != 0.0f) ? 2u : 1u;
+            const PathSampler ps = path_sampler(pp, cam, slot);
+            const uint32_t seed = ps.seed, s = ps.s, base2d = ps.base2d;
             const float2 areal_s = sample2d_t(tb, seed, s, base2d), lightdir_s = sample2d_t(tb, seed, s, base2d + 1u);
             f3 lpos;
             const uint32_t lcode = light_code(sc, sample2d_t(tb, seed, s, base2d + 2u), sample1d_t(tb, seed, s, 0u), areal_s, lpos);
@@ -90,8 +70,8 @@ __global__ __launch_bounds__(RGK_LIGHT_BLOCK) void k_raygen_light(const DevScene
             const float k = (L.type < 0) ? 0.0f : L.intensity * light_dir_factor(L, ldir);
             const f3 start = L.color * mk3(k, k, k);
             ls = make_float4(start.x, start.y, start.z, 0.f);
-            a = make_float4(o.x, o.y, o.z, d.x);
-            b = make_float4(d.y, d.z, __uint_as_float(0xffffffffu), __uint_as_float(slot));
+            a = ray_rec_a(o, d);
+            b = ray_rec_b(d, __uint_as_float(0xffffffffu), slot);
             pp.lvmask[slot] = 0u; // no light vertex yet
             float t0, t1;
             queue = !ray_has_nan(o, d) && clip_to_scene(sc, o, d, 0.0f, 10000.0f, t0, t1); // Ray::near / Ray::far defaults, src/ray.hpp:25-26
@@ -103,7 +83,7 @@ __global__ __launch_bounds__(RGK_LIGHT_BLOCK) void k_raygen_light(const DevScene
 #pragma unroll
         for (int k = 0; k < RGK_LIGHT_BLOCK / 64; k++) { const uint32_t c = s_cnt[k]; before += k < w ? c : 0u; total += c; }
         if (queue) {
-            const uint32_t at = fill + before + __popcll(m & ((1ull << lane) - 1ull));
+            const uint32_t at = fill + before + lane_rank(m, lane);
             st_a[at] = a; st_b[at] = b;
             pp.light[slot] = li; pp.lstart[slot] = ls;
             thr[slot] = make_float4(1.f, 1.f, 1.f, __uint_as_float(1u << 16));
@@ -125,43 +105,6 @@ __global__ __launch_bounds__(RGK_LIGHT_BLOCK) void k_raygen_light(const DevScene
         const uint32_t q0 = s_base;
         for (uint32_t k = threadIdx.x; k < fill; k += RGK_LIGHT_BLOCK) { rayA[q0 + k] = st_a[k]; rayB[q0 + k] = st_b[k]; }
     }
-}
-
-// The sampling half of a GeneratePath iteration (path_tracer.cpp:239-300) shared by both sub-paths.
-struct Step {
-    bool go;
-    f3 cum, no, nd;
-};
-template <bool GENERIC>
-__device__ __forceinline__ void path_step(const DevScene& sc, const SamplerTab& tb, const Vertex& v, const MatPrep& mp, uint32_t seed, uint32_t s,
-                                 uint32_t dim2d, uint32_t n, uint32_t depth, float russian, f3 cum, uint32_t& c1, Step& st) {
-    st.go = false; st.cum = cum; st.no = st.nd = mk3(0.f, 0.f, 0.f);
-    if (!(n < depth)) return; // last vertex: nothing sampled here can be observed
-    const quatf l2g = qinverse(v.g2l);
-    float2 u = sample2d_t(tb, seed, s, dim2d);
-    f3 dirL, weight; bool may_leak;
-    mat_sample<GENERIC>(sc, (int)v.mat_id, v.mat, mp, v.VrL, v.uv, u, dirL, weight, may_leak);
-    const bool inside = dirL.z < 0;
-    const f3 dir = qrot(l2g, dirL);
-    uint32_t n_eff = n;
-    if (!(dot3(dir, v.faceN) * dot3(v.Vr, v.faceN) > 0) && !may_leak) n_eff += 10000u;
-    const bool no_russian = (v.mat.flags & RGK_MAT_NO_RUSSIAN) != 0;
-    const float rc = (!no_russian && russian > 0.0f && n_eff > 1u) ? 1.0f / russian : 1.0f;
-    cum = cum * rc;
-    cum = cum * weight;
-    st.cum = cum;
-    bool go = !(max3c(cum) < 0.001f);
-    if (go && !no_russian && russian >= 0.0f) {
-        float r = sample1d_t(tb, seed, s, c1);
-        c1++;
-        if (r > russian) go = false;
-    }
-    if (go && !(n_eff < depth)) go = false;
-    if (go) {
-        st.no = v.pos + v.faceN * sc.epsilon * 10.0f * (inside ? -1.0f : 1.0f);
-        st.nd = norm3(norm3(dir));
-    }
-    st.go = go;
 }
 
 // Queue indices of the rays that hit something, in queue order inside a workgroup's chunk (the order only decides which lanes
@@ -201,8 +144,8 @@ __global__ __launch_bounds__(RGK_LIGHT_BLOCK, 4) void k_shade_light(const DevSce
         float4 nA = make_float4(0, 0, 0, 0), nB = nA, sA = nA, sB = nA, sC = nA;
         if (valid) {
             const float4 a = rayA[i], b = rayB[i], h = hit[i];
-            const uint32_t slot = __float_as_uint(b.w);
-            const f3 o = mk3(a.x, a.y, a.z), d = mk3(a.w, b.x, b.y);
+            const uint32_t slot = ray_rec_slot(b);
+            const f3 o = ray_rec_o(a), d = ray_rec_d(a, b);
             const float4 st4 = thr[slot];
             f3 cum = mk3(st4.x, st4.y, st4.z);
             const uint32_t n = k + 1u;
@@ -212,9 +155,8 @@ __global__ __launch_bounds__(RGK_LIGHT_BLOCK, 4) void k_shade_light(const DevSce
                 surface_point(sc, pp.bumpmap_scale, o, d, h, v);
                 defer = !GENERIC && v.ok && !mat_is_fast(v.mat.kind);
                 if (v.ok && !defer) {
-                    uint32_t srel, j; slot_decode(pp, slot, j, srel);
-                    const uint32_t seed = pp.pix_seed[pp.j0 + j], s = pp.s0 + srel;
-                    const uint32_t base2d = (cam.lens_size != 0.0f) ? 2u : 1u;
+                    const PathSampler ps = path_sampler(pp, cam, slot);
+                    const uint32_t seed = ps.seed, s = ps.s, base2d = ps.base2d;
                     MatPrep mp;
                     mat_prepare(sc, v.mat, v.uv, v.VrL, n < pp.reverse, mp);
                     const f3 contribution = cum;
@@ -247,17 +189,17 @@ __global__ __launch_bounds__(RGK_LIGHT_BLOCK, 4) void k_shade_light(const DevSce
                             const f3 diff = campos - v.pos; // Ray(p.pos, camerapos, 20 eps)
                             const f3 sd = norm3(diff);
                             splat = true;
-                            sA = make_float4(v.pos.x, v.pos.y, v.pos.z, sd.x);
-                            sB = make_float4(sd.y, sd.z, len3(diff) - eps * 20.0f, __uint_as_float((uint32_t)y2 * pp.xres + (uint32_t)x2));
-                            sC = make_float4(q.x, q.y, q.z, 0.0f + eps * 20.0f);
+                            sA = shadow_rec_a(v.pos, sd);
+                            sB = shadow_rec_b(sd, len3(diff) - eps * 20.0f, (uint32_t)y2 * pp.xres + (uint32_t)x2);
+                            sC = shadow_rec_c(q, 0.0f + eps * 20.0f);
                         }
                     }
                     Step st;
                     path_step<GENERIC>(sc, tb, v, mp, seed, s, base2d + 3u + pp.depth + (n - 1u), n, pp.reverse, -1.0f, cum, c1, st);
                     if (st.go) {
                         cont = true;
-                        nA = make_float4(st.no.x, st.no.y, st.no.z, st.nd.x);
-                        nB = make_float4(st.nd.y, st.nd.z, h.w, __uint_as_float(slot));
+                        nA = ray_rec_a(st.no, st.nd);
+                        nB = ray_rec_b(st.nd, h.w, slot);
                         thr[slot] = make_float4(st.cum.x, st.cum.y, st.cum.z, st4.w);
                     }
                 }

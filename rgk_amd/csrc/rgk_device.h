@@ -832,10 +832,13 @@ __device__ __forceinline__ f3 skybox(const DevScene& sc, f3 direction) {
     return c * mk3(sc.sky_intensity, sc.sky_intensity, sc.sky_intensity);
 }
 
-// ------------------------------------------------------------------ path vertex (shared by the BDPT kernels)
+// ------------------------------------------------------------------ path vertex (k_shade_light, rgk_bdpt.h; k_aov_gather, rgk_post.hip)
 // The geometric half of one GeneratePath iteration, reference src/path_tracer.cpp:152-235: hit point,
 // interpolated + normalised face normal (with the NaN fallbacks), uv, bump-tilted shading normal and
 // the global->local frame.  `ok == false` is the reference's `return path` (vertex dropped, path ends).
+// THERE ARE TWO COPIES: k_shade (rgk_shade.h) has the same steps inline, between its own tests (`defer`, `ends`), and shares
+// face_normal() alone -- uv, the bump tilt and the frame behind a function change its code (profiles/shade_pieces_device_code.txt).
+// A change to one copy belongs in the other.
 struct Vertex {
     bool ok;
     f3 pos, faceN, lightN, Vr, VrL;
@@ -845,6 +848,19 @@ struct Vertex {
     quatf g2l;
 };
 __device__ __forceinline__ f3 clamp3(f3 v, float c) { return mk3(v.x > c ? c : v.x, v.y > c ? c : v.y, v.z > c ? c : v.z); }
+
+// Interpolated face normal, not yet normalised, with the NaN fallbacks (path_tracer.cpp:157-171) and the zero test (:175): for
+// surface_point() below and for k_shade.  (`ok` by reference: returned in a struct with the normal, k_shade_light changes.)
+__device__ __forceinline__ f3 face_normal(float ia, float ib, float ic, f3 nA_, f3 nB_, f3 nC_, bool& ok) {
+    f3 faceN = ia * nA_ + ib * nB_ + ic * nC_;
+    ok = true;
+    if (faceN.x != faceN.x) {
+        faceN = nA_;
+        if (faceN.x != faceN.x) { faceN = nB_; if (faceN.x != faceN.x) { faceN = nC_; if (faceN.x != faceN.x) ok = false; } }
+    }
+    if (ok && len3(faceN) <= 0.0f) ok = false;
+    return faceN;
+}
 
 __device__ __forceinline__ void surface_point(const DevScene& sc, float bumpmap_scale, f3 o, f3 d, float4 h, Vertex& v) {
     const int tri = __float_as_int(h.w);
@@ -857,13 +873,7 @@ __device__ __forceinline__ void surface_point(const DevScene& sc, float bumpmap_
     v.Vr = -d;
     v.pos = o + h.x * d;
     f3 nA_ = mk3(g0.x, g0.y, g0.z), nB_ = mk3(g1.x, g1.y, g1.z), nC_ = mk3(g2.x, g2.y, g2.z);
-    f3 faceN = ia * nA_ + ib * nB_ + ic * nC_;
-    v.ok = true;
-    if (faceN.x != faceN.x) { // NaN fallbacks, path_tracer.cpp:157-171
-        faceN = nA_;
-        if (faceN.x != faceN.x) { faceN = nB_; if (faceN.x != faceN.x) { faceN = nC_; if (faceN.x != faceN.x) v.ok = false; } }
-    }
-    if (v.ok && len3(faceN) <= 0.0f) v.ok = false; // path_tracer.cpp:175
+    f3 faceN = face_normal(ia, ib, ic, nA_, nB_, nC_, v.ok);
     v.uv = make_float2(0.f, 0.f);
     v.faceN = v.lightN = faceN;
     if (!v.ok) return;

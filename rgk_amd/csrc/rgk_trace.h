@@ -872,7 +872,7 @@ __global__ __launch_bounds__(RGK_TRACE_BLOCK, RGK_BEAM_WAVES) void k_trace_camer
 }
 
 // ------------------------------------------------------------------ K5: shadow rays + accumulate
-// shA = (o.xyz, d.x)  shB = (d.y, d.z, far, slot)  shC = (radiance.rgb, near)
+// shA = (o.xyz, d.x)  shB = (d.y, d.z, far, slot)  shC = (radiance.rgb, near)  (the queue records: described once in rgk_shade.h, where they are packed)
 template <bool COUNT, int STACK, int LDSN>
 __global__ __launch_bounds__(RGK_TRACE_BLOCK, (LDSN <= 16 ? RGK_TRACE_WAVES : 5)) void k_trace_shadow(
     const DevScene sc, const float4* __restrict__ shA, const float4* __restrict__ shB, const float4* __restrict__ shC, float4* __restrict__ tot,
@@ -883,7 +883,7 @@ __global__ __launch_bounds__(RGK_TRACE_BLOCK, (LDSN <= 16 ? RGK_TRACE_WAVES : 5)
     trace_persistent<RayKind::Shadow, COUNT, STACK, LDSN>(sc, shA, shB, shC, nullptr, nullptr, tot, vis_out, mode, splat_rgb, *count_ptr, fetch, lds_stack, ovf, n_nodes, n_tris, stats);
     flush_walk_counts<COUNT>(stats + 2, n_nodes, n_tris);
 }
-// ... with the 32-byte records of the constant-light route: shA = (d.xyz, far)  shB = (radiance.rgb, slot); o = sc.cl_pos, near = 20 eps
+// ... with the 32-byte records of the constant-light route: shA = (d.xyz, far)  shB = (radiance.rgb, slot); o = sc.cl_pos, near = 20 eps (rgk_shade.h)
 template <bool COUNT, int STACK, int LDSN>
 __global__ __launch_bounds__(RGK_TRACE_BLOCK, (LDSN <= 16 ? RGK_TRACE_WAVES : 5)) void k_trace_shadow_cl(
     const DevScene sc, const float4* __restrict__ shA, const float4* __restrict__ shB, float4* __restrict__ tot, const uint32_t* __restrict__ count_ptr,

@@ -28,5 +28,11 @@ def test_device_code_diff_of_the_tree_against_itself():
     for name in ("k_trace_closest", "k_trace_camera", "k_trace_shadow", "k_trace_shadow_first", "k_trace_shadow_cl", "k_trace_shadow_first_cl", "k_trace_shadow_jobs"):
         assert sum(ln.strip().startswith(name + "<") for ln in kernels) == 6, name
     assert sum(ln.strip().startswith("k_trace_camera_beam<") for ln in kernels) == 2 and "k_raygen_light" in shown
+    # the shading kernels in every variant rgk_launch_shade / rgk_launch_shade_light can pick, and the plain kernels of the headers
+    # rgk_kernels.hip includes: a split that loses an instantiation or a header fails here
+    assert sum(ln.strip().startswith("k_shade<") for ln in kernels) == 12
+    assert sum(ln.strip().startswith("k_shade_light<") for ln in kernels) == 2
+    for name in ("k_connect", "k_resolve", "k_resolve_tiled", "k_entry_points", "k_entry_points_light"):
+        assert name in shown, name
     # a call it cannot serve ends with status 2, never with 0
     assert subprocess.run([os.path.join(ROOT, "tools", "device_code_diff.sh"), ROOT], capture_output=True).returncode == 2
