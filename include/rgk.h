@@ -145,8 +145,10 @@ typedef struct rgk_scene_desc {
 #define RGK_BUILD_KEEP_FLOAT_TEXTURES 2u /* store every RGK_TEX_RGB32F texture as float4 texels, even one with <= 256 distinct channel
                                             values (by default such a texture is stored as bytes + the table of its values: the same
                                             texel values, a quarter of the traffic)                                                */
-#define RGK_BUILD_DEVICE 1u   /* LBVH on the GPU (Morton sort, Karras hierarchy, refit with tree rotations, collapse + quantisation: all on
-                                 the device): a tenth of the host's build time, traversal within a few per cent of it        */
+#define RGK_BUILD_DEVICE 1u   /* tree built on the GPU (Morton sort, bottom-up clustering of the sorted references by surface, refit,
+                                 collapse + quantisation: all on the device; no rotation pass.  RGK_LBVH_PLOC=0 in the environment:
+                                 the Karras prefix hierarchy instead, then refit with tree rotations): a tenth of the host's build
+                                 time, traversal within a few per cent of it                                                  */
 
 /* ---- Camera as RenderRound(const Camera&) receives it (src/render_driver.cpp:146): the public data members
  *      of the reference's Camera, src/camera.hpp:27-41, under their own names (`lookat` is not read on the path).

@@ -148,18 +148,6 @@ int commit_bounds(const float* vertices, const uint32_t* tri_indices, uint32_t n
 
 namespace {
 
-struct Box {
-    float mn[3], mx[3];
-    void reset() { for (int i = 0; i < 3; i++) { mn[i] = std::numeric_limits<float>::infinity(); mx[i] = -mn[i]; } }
-    void grow(const float* a, const float* b) { for (int i = 0; i < 3; i++) { mn[i] = std::min(mn[i], a[i]); mx[i] = std::max(mx[i], b[i]); } }
-    void grow(const Box& o) { grow(o.mn, o.mx); }
-    float area() const {
-        float dx = mx[0] - mn[0], dy = mx[1] - mn[1], dz = mx[2] - mn[2];
-        if (dx < 0 || dy < 0 || dz < 0) return 0.f;
-        return 2.f * (dx * dy + dy * dz + dz * dx);
-    }
-};
-
 // Early split clipping of large triangles (reference-splitting before the build): a triangle whose box is longer
 // than `lmax` on some axis enters the build as several references, one per piece of the triangle clipped at the
 // box midpoint, each with the tight box of its piece.  The pieces tile the triangle, so every hit point lies in
@@ -251,28 +239,11 @@ void commit_triangles(const float* vertices, const uint32_t* tri_indices, uint32
     splitter.out = &prims;
     for (uint32_t i = 0; i < n_triangles; i++) {
         V3 v0 = vert(tri_indices[3 * i]), v1 = vert(tri_indices[3 * i + 1]), v2 = vert(tri_indices[3 * i + 2]);
-        V3 d0 = sub(v1, v0), d1 = sub(v2, v0);
-        V3 n = normv(crossv(d1, d0));
-        float dd = -dotv(n, v0);
-        TriIsect& r = recs[i];
-        r.n[0] = n.x; r.n[1] = n.y; r.n[2] = n.z; r.d = dd;
-        int i1, i2;
-        float ax = std::fabs(n.x), ay = std::fabs(n.y), az = std::fabs(n.z);
-        if (ax > ay && ax > az) { i1 = 1; i2 = 2; }
-        else if (ay > az) { i1 = 0; i2 = 2; }
-        else { i1 = 0; i2 = 1; }
-        r.v0a = comp(v0, i1); r.v0b = comp(v0, i2);
-        r.q1x = comp(v1, i1) - comp(v0, i1); r.q1y = comp(v1, i2) - comp(v0, i2);
-        r.q2x = comp(v2, i1) - comp(v0, i1); r.q2y = comp(v2, i2) - comp(v0, i2);
-        r.axes = (uint32_t)i1 | ((uint32_t)i2 << 2);
-        r.tri = i;
-        if (n.x == n.x && n.y == n.y && n.z == n.z) { // a NaN plane can never be hit (primitives.cpp:90)
+        const TriIsect& r = recs[i] = tri_isect_record(v0, v1, v2, i);
+        if (r.n[0] == r.n[0] && r.n[1] == r.n[1] && r.n[2] == r.n[2]) { // a NaN plane can never be hit (primitives.cpp:90)
             Prim p;
-            for (int a = 0; a < 3; a++) {
-                p.bmin[a] = std::min(comp(v0, a), std::min(comp(v1, a), comp(v2, a)));
-                p.bmax[a] = std::max(comp(v0, a), std::max(comp(v1, a), comp(v2, a)));
-                p.c[a] = 0.5f * (p.bmin[a] + p.bmax[a]);
-            }
+            const Box b = tri_box(v0, v1, v2);
+            for (int a = 0; a < 3; a++) { p.bmin[a] = b.mn[a]; p.bmax[a] = b.mx[a]; p.c[a] = 0.5f * (p.bmin[a] + p.bmax[a]); }
             p.tri = i;
             p.pb[0] = 0.f; p.pb[1] = 1.f; p.pb[2] = 0.f; p.pb[3] = 1.f;
             if (splitter.lmax > 0.f) {
@@ -305,8 +276,7 @@ struct BvhBuilder {
     int make_leaf(size_t b, size_t e) {
         uint32_t first = order.size();
         for (size_t i = b; i < e; i++) order.push_back(prims[i].ref);
-        uint32_t cnt = (uint32_t)(e - b);
-        return (int)~((first << 4) | (cnt - 1));
+        return leaf_code(first, (uint32_t)(e - b));
     }
     // returns the child code for prims[b,e) and its (padded) box
     int build(size_t b, size_t e, uint32_t depth, Box& box) {
@@ -375,7 +345,7 @@ struct BvhBuilder {
                 }
             }
         }
-        for (int i = 0; i < 3; i++) { box.mn[i] -= pad; box.mx[i] += pad; }
+        box.pad(pad);
         if (leaf) return make_leaf(b, e);
         int idx = (int)nodes.size();
         nodes.emplace_back();
@@ -398,7 +368,7 @@ struct BvhBuilder {
 static void optimise_bvh2(std::vector<BvhNode>& nodes, std::vector<uint32_t>& order, int rounds, float frac) {
     const int NI = (int)nodes.size();
     if (NI < 8 || rounds <= 0) return;
-    std::vector<Box> box; std::vector<int> l, r, par, leaf_code;
+    std::vector<Box> box; std::vector<int> l, r, par, leaf_codes;
     box.reserve(2 * NI + 1); l.assign(NI, -1); r.assign(NI, -1);
     box.resize(NI);
     auto side_box = [](const BvhNode& n, bool left) { Box b; for (int a = 0; a < 3; a++) { b.mn[a] = left ? n.lmin[a] : n.rmin[a]; b.mx[a] = left ? n.lmax[a] : n.rmax[a]; } return b; };
@@ -408,11 +378,11 @@ static void optimise_bvh2(std::vector<BvhNode>& nodes, std::vector<uint32_t>& or
             const Box b = side_box(nodes[i], sd == 0);
             int id;
             if (code >= 0) { id = code; box[id] = b; }
-            else { id = (int)box.size(); box.push_back(b); l.push_back(-1); r.push_back(-1); leaf_code.resize(box.size(), 0); leaf_code[id] = code; }
+            else { id = (int)box.size(); box.push_back(b); l.push_back(-1); r.push_back(-1); leaf_codes.resize(box.size(), 0); leaf_codes[id] = code; }
             (sd == 0 ? l[i] : r[i]) = id;
         }
     }
-    leaf_code.resize(box.size(), 0);
+    leaf_codes.resize(box.size(), 0);
     const int N = (int)box.size();
     par.assign(N, -1);
     for (int i = 0; i < NI; i++) { par[l[i]] = i; par[r[i]] = i; }
@@ -472,10 +442,10 @@ static void optimise_bvh2(std::vector<BvhNode>& nodes, std::vector<uint32_t>& or
     std::vector<uint32_t> new_order; new_order.reserve(order.size());
     std::function<int(int)> emit = [&](int n) -> int {
         if (l[n] < 0) {
-            const uint32_t code = ~(uint32_t)leaf_code[n], first = code >> 4, cnt = (code & 15u) + 1u;
+            const uint32_t code = ~(uint32_t)leaf_codes[n], first = leaf_first(code), cnt = leaf_count(code);
             const uint32_t nf = (uint32_t)new_order.size();
             for (uint32_t k = 0; k < cnt; k++) new_order.push_back(order[first + k]);
-            return (int)~((nf << 4) | (cnt - 1));
+            return leaf_code(nf, cnt);
         }
         const int idx = (int)out.size();
         out.emplace_back();
@@ -492,8 +462,7 @@ static void optimise_bvh2(std::vector<BvhNode>& nodes, std::vector<uint32_t>& or
 
 // ------------------------------------------------------------------ BVH2 -> quantised BVH4
 // Collapse the binary tree (always open the inner child with the largest surface until four
-// children) and quantise each child box to 8 bits per plane relative to the node's box, rounding
-// outward and re-checking the decode in float exactly as the kernel evaluates it.
+// children) and quantise each child box to 8 bits per plane relative to the node's box (quantise_axis, rgk_tree.h).
 struct QbvhBuilder {
     const std::vector<BvhNode>& bn;
     std::vector<QNode> out;
@@ -534,29 +503,11 @@ struct QbvhBuilder {
         for (auto& c : ch) nb.grow(c.box);
         QNode q;
         std::memset(&q, 0, sizeof(q));
+        Box cb[4];
+        for (size_t i = 0; i < ch.size(); i++) cb[i] = ch[i].box;
         for (int a = 0; a < 3; a++) {
             q.p[a] = nb.mn[a];
-            float ext = nb.mx[a] - nb.mn[a];
-            int e = 0;
-            if (ext > 0.f) { std::frexp(ext / 255.0f, &e); } else e = -126;
-            for (;; e++) { // find the smallest exponent whose outward-rounded codes all fit and verify
-                if (e < -126) e = -126;
-                const float scale = std::ldexp(1.0f, e);
-                bool ok = true;
-                uint8_t lo[4], hi[4];
-                for (size_t i = 0; i < ch.size() && ok; i++) {
-                    float fl = std::floor((ch[i].box.mn[a] - q.p[a]) / scale), fh = std::ceil((ch[i].box.mx[a] - q.p[a]) / scale);
-                    if (fl < 0.f) fl = 0.f;
-                    while (fl > 0.f && std::fmaf(fl, scale, q.p[a]) > ch[i].box.mn[a]) fl -= 1.f;
-                    while (fh <= 255.f && std::fmaf(fh, scale, q.p[a]) < ch[i].box.mx[a]) fh += 1.f;
-                    if (fh > 255.f || fl > 255.f) { ok = false; break; }
-                    lo[i] = (uint8_t)fl; hi[i] = (uint8_t)fh;
-                }
-                if (!ok) continue;
-                (a == 0 ? q.sx : (a == 1 ? q.sy : q.sz)) = scale;
-                for (size_t i = 0; i < 4; i++) { q.qlo[a][i] = i < ch.size() ? lo[i] : 255; q.qhi[a][i] = i < ch.size() ? hi[i] : 0; }
-                break;
-            }
+            quantise_axis(cb, (int)ch.size(), a, q.p[a], nb.mx[a] - nb.mn[a], a == 0 ? q.sx : (a == 1 ? q.sy : q.sz), q.qlo[a], q.qhi[a]);
         }
         for (size_t i = 0; i < 4; i++) q.child[i] = RGK_QNODE_EMPTY;
         out[idx] = q;

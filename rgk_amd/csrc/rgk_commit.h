@@ -17,23 +17,11 @@
 
 #include "../../include/rgk.h"
 #include "device_types.h"
+#include "rgk_tree.h" // V3, Box, leaf codes, the quantiser, tri_isect_record: shared with the device builder
 
 // Sets rgk_last_error (per thread) and returns `code`.  Every translation unit reports through this one:
 // the others through rgk_internal_fail, its extern "C" form.
 int fail(int code, const char* fmt, ...);
-
-struct V3 {
-    float x, y, z;
-};
-inline V3 sub(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-inline V3 crossv(V3 x, V3 y) { return {x.y * y.z - y.y * x.z, x.z * y.x - y.z * x.x, x.x * y.y - y.x * x.y}; }
-inline float dotv(V3 a, V3 b) {
-    float tx = a.x * b.x, ty = a.y * b.y, tz = a.z * b.z;
-    return tx + ty + tz;
-}
-inline V3 scale(V3 a, float s) { return {a.x * s, a.y * s, a.z * s}; }
-inline V3 normv(V3 v) { return scale(v, 1.0f / std::sqrt(dotv(v, v))); }
-inline float comp(V3 v, int i) { return i == 0 ? v.x : (i == 1 ? v.y : v.z); }
 
 // ------------------------------------------------------------------ build switches
 // The build-time switches of the environment (nothing here changes a result).  Read ONCE, by read_build_options at the

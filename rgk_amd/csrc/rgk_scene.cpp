@@ -95,11 +95,10 @@ int build_accel_device(rgk_scene* s, const std::vector<Prim>& prims, const std::
     DevBuf<TriIsect> d_recs;
     if ((rc = d_recs.upload(recs.data(), recs.size())) || (rc = s->nodes.alloc(prims.size())) || (rc = s->tris.alloc(prims.size())) || (rc = s->leaf_pb.alloc(prims.size()))) return rc;
     uint32_t levels = 0;
-    const char* err = "";
     acc.n_refs = (uint32_t)prims.size();
     rc = rgk_build_bvh4_device(s->stream, bp.data(), acc.n_refs, mn, mx, eps, (uint32_t)opt.max_leaf_dev, opt.lbvh_rotate, opt.lbvh_ploc, opt.lbvh_morton_bits, d_recs.p,
-                               s->nodes.p, s->tris.p, s->leaf_pb.p, &acc.n_nodes, &levels, &err);
-    if (rc) return fail(rc, "device BVH build: %s", err);
+                               s->nodes.p, s->tris.p, s->leaf_pb.p, &acc.n_nodes, &levels);
+    if (rc) return rc;
     acc.max_depth = levels;
     acc.max_stack = 3 * levels; // three pushes per level at most
     acc.on_device = true;
@@ -266,10 +265,9 @@ int rgk_scene_refit(rgk_scene* s, const float* vertices, const float* normals, c
     DevBuf<float> d_n, d_t;
     if (normals && (rc = d_n.upload(normals, 3 * (size_t)nv))) return rc;
     if (tangents && (rc = d_t.upload(tangents, 3 * (size_t)nv))) return rc;
-    const char* err = "";
     rc = rgk_refit_bvh4_device(s->stream, s->n_refs, s->n_nodes, nt, s->scratch_f.p, normals ? d_n.p : nullptr, tangents ? d_t.p : nullptr, s->d_idx.p, s->leaf_pb.p, eps,
-                               s->tris.p, s->nodes.p, s->tri_shade.p, &err);
-    if (rc) return fail(rc, "refit: %s", err);
+                               s->tris.p, s->nodes.p, s->tri_shade.p);
+    if (rc) return rc;
     // ---- areal-light tables (areas, positions, vertex-A normals change with the vertices)
     if (normals) s->h_normals.assign(normals, normals + 3 * (size_t)nv);
     std::vector<DevArealLight> als;

@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 #include "rgk_device.h"
 #include "rgk_kernels.h"
+#include "rgk_tree.h"
 
 #define STACK_SENTINEL 0x7fffffff
 #ifndef RGK_CHUNK_MAX
@@ -251,9 +252,7 @@ __device__ __forceinline__ void sort4(float& t0, float& t1, float& t2, float& t3
 }
 
 // A leaf's child code is ~code, code = first << 4 | count - 1: 1 ... 16 consecutive triangle records of three float4 (TriIsect,
-// what tri_test takes; the triangle's id is the last word).
-__device__ __forceinline__ uint32_t leaf_first(const uint32_t code) { return code >> 4; }
-__device__ __forceinline__ uint32_t leaf_count(const uint32_t code) { return (code & 15u) + 1u; }
+// what tri_test takes; the triangle's id is the last word).  leaf_first / leaf_count: rgk_tree.h, the builders' pair.
 __device__ __forceinline__ const float4* tri_record(const float4* tris, const uint32_t i) { return tris + 3 * i; }
 // COUNT: what a walker adds to the launch's statistics, nodes visited and triangles tested (closest-hit launches stats[0..1],
 // shadow launches stats[2..3])

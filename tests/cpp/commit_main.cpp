@@ -1,6 +1,6 @@
 // CPU harness of the GPU-free commit unit (rgk_amd/csrc/rgk_commit.cpp), linked with nothing else of the library and
 // run under ASan + UBSan by tests/test_commit_cpu.py:  commit_main <case> [--digest]
-//   geom-default | geom-leaf1 | geom-leaf16 | geom-nosplit | geom-noopt | geom-single | textures | small
+//   geom-default | geom-leaf1 | geom-leaf16 | geom-nosplit | geom-noopt | geom-single | refit-pieces | textures | small
 // Inputs come from a fixed LCG seed, no file is read.  Exit status 0: every condition of the case held.
 // --digest: an FNV-1a digest per output table on stdout (a refactor of the unit must leave them as they are).
 #include <cmath>
@@ -274,6 +274,52 @@ static void check_single_leaf() {
     CHECK(run_geometry(g, BuildOptions{}, o) == 0 && o.acc.qnodes.size() == 1, "%zu nodes", o.acc.qnodes.size());
 }
 
+// ------------------------------------------------------------------ the box of a moved piece
+// rgk_scene_refit re-boxes a pre-split reference with piece_box (rgk_tree.h) from the moved triangle and the piece's parameter
+// box.  For every proper piece of the 647-triangle geometry and three affine moves of its triangle -- none, a rotation with a
+// scale and a shift of order 1, and scales of 1e3 and 1e-3 with a shift of 1e4 -- every point of a 13 x 13 lattice over the
+// parameter box that lies in the triangle (b + c <= 1), evaluated in double from the moved float vertices and rounded to
+// float, is in the box: tolerance zero.
+static void check_refit_pieces() {
+    const Geometry g = make_geometry();
+    GeomOut o;
+    CHECK(run_geometry(g, BuildOptions{}, o) == 0, "%s", rgk_last_error());
+    if (g_failed) return;
+    const double rot[3][3] = {{0.36, 0.48, -0.8}, {-0.8, 0.6, 0.0}, {0.48, 0.64, 0.6}}; // orthonormal
+    const auto move = [&](int map, const float* v) {
+        double w[3] = {v[0], v[1], v[2]};
+        if (map == 1) for (int a = 0; a < 3; a++) w[a] = 1.3 * (rot[a][0] * v[0] + rot[a][1] * v[1] + rot[a][2] * v[2]) + (a == 0 ? 0.3 : (a == 1 ? -0.2 : 0.5));
+        if (map == 2) { w[0] = 1e3 * v[0] + 1e4; w[1] = v[1] + 1e4; w[2] = 1e-3 * v[2] + 1e4; }
+        return V3{(float)w[0], (float)w[1], (float)w[2]};
+    };
+    size_t pieces = 0, points = 0, outside = 0;
+    for (const Prim& p : o.prims) {
+        if (whole_triangle(p.pb[0], p.pb[1], p.pb[2], p.pb[3])) continue;
+        for (int map = 0; map < 3; map++) {
+            V3 v[3];
+            for (int k = 0; k < 3; k++) v[k] = move(map, &g.v[3 * (size_t)g.idx[3 * p.tri + k]]);
+            const Box box = piece_box(v[0], v[1], v[2], p.pb[0], p.pb[1], p.pb[2], p.pb[3]);
+            pieces++;
+            for (int bi = 0; bi <= 12; bi++)
+                for (int ci = 0; ci <= 12; ci++) {
+                    const double b = p.pb[0] + ((double)p.pb[1] - p.pb[0]) * bi / 12.0, c = p.pb[2] + ((double)p.pb[3] - p.pb[2]) * ci / 12.0;
+                    if (b + c > 1.0) continue;
+                    points++;
+                    bool in = true;
+                    for (int a = 0; a < 3; a++) {
+                        const double v0 = comp(v[0], a), v1 = comp(v[1], a), v2 = comp(v[2], a);
+                        const float x = (float)(v0 + b * (v1 - v0) + c * (v2 - v0));
+                        in = in && box.mn[a] <= x && x <= box.mx[a];
+                    }
+                    outside += !in;
+                }
+        }
+    }
+    if (g_digest) std::printf("[pieces] %zu pieces, %zu points, %zu outside\n", pieces, points, outside);
+    CHECK(pieces > 0, "the geometry has no pre-split piece");
+    CHECK(outside == 0, "%zu of %zu points outside the box of their piece (%zu pieces)", outside, points, pieces);
+}
+
 // ------------------------------------------------------------------ texture case
 static void digest_tables(const ShadingTables& t) {
     digest("tri_shade", t.tri_shade); digest("texels", t.tex.texels); digest("texels8", t.tex.texels8); digest("luts", t.tex.luts); digest("texrefs", t.tex.refs);
@@ -405,6 +451,7 @@ int main(int argc, char** argv) {
     else if (c == "geom-nosplit") { o.split = 0.f; check_geometry(make_geometry(), o, false); }
     else if (c == "geom-noopt") { o.opt_rounds = 0; check_geometry(make_geometry(), o, true); }
     else if (c == "geom-single") check_single_leaf();
+    else if (c == "refit-pieces") check_refit_pieces();
     else if (c == "textures") check_textures();
     else if (c == "small") check_small();
     else { std::fprintf(stderr, "unknown case '%s'\n", c.c_str()); return 2; }

@@ -7,6 +7,9 @@ links that one translation unit and nothing else of the library, makes its input
             every point of a 13-step barycentric lattice on every triangle is found through the DECODED 8-bit boxes alone
             (tolerance zero: the boxes are epsilon-padded and rounded outward), max_depth is the walk's, two runs are
             byte-identical;
+  refit-pieces  the box rgk_scene_refit gives a pre-split reference (piece_box, rgk_tree.h -- the function the device kernel
+            calls): every proper piece of that geometry under three affine moves of its triangle, a 13 x 13 lattice over its
+            parameter box evaluated in double, every point inside the box with tolerance zero;
   textures  six textures in one descriptor: palette detection (+0.0, -0.0 and a NaN among the values), table sharing, the
             caller's table, the 257-value texture that stays float, tiled byte texels bit-equal to their sources;
   small     commit_bounds, const_light_eligible, build_areal_tables.
@@ -22,7 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CPP = os.path.join(ROOT, "tests", "cpp")
 CSRC = os.path.join(ROOT, "rgk_amd", "csrc")
 
-CASES = ["geom-default", "geom-leaf1", "geom-leaf16", "geom-nosplit", "geom-noopt", "geom-single", "textures", "small"]
+CASES = ["geom-default", "geom-leaf1", "geom-leaf16", "geom-nosplit", "geom-noopt", "geom-single", "refit-pieces", "textures", "small"]
 
 
 @pytest.fixture(scope="module")

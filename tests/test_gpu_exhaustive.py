@@ -225,6 +225,48 @@ def test_refitted_tree_equals_the_exhaustive_search_on_the_moved_mesh(rd, oracle
     g.close()
 
 
+# ----------------------------------------------------------------------- the device builder's trees, pinned
+FINGERPRINT_BUILDERS = ("device", "device-karras", "device-karras-rotate4")
+FINGERPRINT_CASES = [(s, b) for s in T.SCENES for b in FINGERPRINT_BUILDERS]
+FINGERPRINT_FILE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "device_tree_fingerprint.json")
+
+
+def tree_fingerprint(rd, scene, builder):
+    """({n_nodes, max_depth, n_leaf_refs}, {the four traversal counters}) of one build of `scene` on its fixed rays and pairs."""
+    ref = _reference(scene)
+    g = gpu_scene(rd, ref["sb"], builder)
+    i = g.info()
+    info = dict(n_nodes=int(i.n_nodes), max_depth=int(i.max_depth), n_leaf_refs=int(i.n_leaf_refs))
+    _, c = g.trace_closest(ref["rays"], count=True)
+    _, s = g.visibility(ref["a"], ref["b"], count=True)
+    g.close()
+    return info, dict(node_visits=int(c.node_visits), tri_tests=int(c.tri_tests), shadow_node_visits=int(s.shadow_node_visits),
+                      shadow_tri_tests=int(s.shadow_tri_tests))
+
+
+@functools.lru_cache(maxsize=None)
+def _fingerprints():
+    import json
+    with open(FINGERPRINT_FILE) as f:
+        return json.load(f)["cases"]
+
+
+@pytest.mark.parametrize("scene,builder", FINGERPRINT_CASES, ids=[f"{s}-{b}" for s, b in FINGERPRINT_CASES])
+def test_device_built_tree_keeps_its_fingerprint(rd, scene, builder):
+    """The trees of the device builder (rgk_build.hip), as far as the C ABI shows them: node count, depth and leaf references of
+    rgk_scene_get_info, and the node visits and triangle tests that the scene's fixed rays and pairs cost -- a different tree,
+    child box or 8-bit code changes what a ray visits.  The expected numbers (tests/golden/device_tree_fingerprint.json) were
+    recorded on the MI355X from the commit BEFORE the builder's pieces moved into rgk_tree.h, three builds per case; a refactor
+    of the builder must leave them as they are.  The device build numbers its nodes with atomics: a case whose counters were
+    not the same in all three builds has no "counters" entry (the file lists those cases under "unstable") and is held to the
+    three info numbers alone."""
+    want = _fingerprints()[f"{scene}-{builder}"]
+    info, counters = tree_fingerprint(rd, scene, builder)
+    assert info == want["info"], (info, want["info"])
+    if "counters" in want:
+        assert counters == want["counters"], (counters, want["counters"])
+
+
 # ----------------------------------------------------------------------- the feature pass: camera rays made on the device
 def _camera_case(name, W, H):
     from rgk_amd.workloads import Workload

@@ -1022,11 +1022,13 @@ def test_pinned_libm_same_bits_on_gpu_and_cpu(oracle, product_lib):
 
 # ----------------------------------------------------------------------- f2: the accelerator built on the device
 def test_device_built_bvh_gives_the_same_hits(rd, oracle):
-    """the LBVH built on the GPU (Morton sort, Karras hierarchy, refit with tree rotations, collapse + quantisation
-    on the device, rgk_build.hip) against the ORACLE's kd-tree walk (same bar as the host-built tree: same triangle except inside
+    """the tree built on the GPU (Morton sort, clustering of the sorted references by surface, refit, collapse +
+    quantisation on the device, rgk_build.hip; by default no rotation pass -- the Karras hierarchy with rotations is
+    RGK_LBVH_PLOC=0) against the ORACLE's kd-tree walk (same bar as the host-built tree: same triangle except inside
     the epsilon tie band, then t and barycentrics bit for bit) and against the host's binned-SAH tree (another tree over the same
     triangle records) -- on cube3, box6, the Sponza proxy and the 1.05 M-triangle dragon scene; images equal too.  Records build
-    time and node visits per ray of the host tree, the device tree, and the device tree without its rotation step."""
+    time and node visits per ray of the host tree, the device tree, and the device tree built again with RGK_LBVH_ROTATE=0 (what
+    the default already is: the same clustered tree, so the same hits)."""
     import time
     from rgk_amd.workloads import Workload
     cases = [("cube3", scene_fixture("cube3", scale=0.1, spp=4)), ("box6", scene_fixture("box6", scale=0.1, spp=4)),

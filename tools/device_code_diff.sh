@@ -57,7 +57,7 @@ for f in $SOURCES; do
     [ -s "$work/head/$f.k/index" ] || { echo "$0: no kernel found in $f.s" >&2; exit 2; }
     # parent's kernels in their order, then those only the head has
     { cut -f1 "$work/parent/$f.k/index"; cut -f1 "$work/head/$f.k/index"; } | awk '!seen[$0]++' | while read -r sym; do
-        shown=$(echo "$sym" | "$CXXFILT" | sed -e 's/^void //' -e 's/>(.*$/>/' -e 's/^\([A-Za-z_0-9]*\)(.*$/\1/')
+        shown=$(echo "$sym" | "$CXXFILT" | sed -e 's/(anonymous namespace):://g' -e 's/^void //' -e 's/>(.*$/>/' -e 's/^\([A-Za-z_0-9]*\)(.*$/\1/')
         rp=$(awk -F'\t' -v s="$sym" '$1 == s' "$work/parent/$f.k/index"); rh=$(awk -F'\t' -v s="$sym" '$1 == s' "$work/head/$f.k/index")
         row() { echo "$2" | awk -F'\t' -v side=$1 '{ printf "    %-6s vgprs %3d  scratch %4d  lds %6d  occupancy %d  code %6d\n", side, $3, $4, $5, $6, $7 }'; }
         if [ -n "$rp" ] && [ -n "$rh" ] && cmp -s "$(echo "$rp" | cut -f2)" "$(echo "$rh" | cut -f2)"; then
