@@ -305,9 +305,12 @@ int rgk_scene_get_progress(const rgk_scene *scene, rgk_progress *out);
  * of them share; 0: the per-path route.  The scene qualifies when it has exactly one point light and no emitting triangle, the
  * light's size is 0, no component of its position is -0.0 (pos + 0 * v must give back pos bit for bit), and GetRandomLight's
  * own two float comparisons, evaluated with its own expressions for the largest number the sampler returns, 1 - 2^-24, select
- * light 0: rounding is monotone, so every smaller sample selects it too.  Same bits either way), "time_post" (0 / 1, default 0: HIP events
+ * light 0: rounding is monotone, so every smaller sample selects it too.  Same bits either way), "last_vertex" (0 / 1, default 1:
+ * the last bounce of a unidirectional pass, whose vertices all end their paths, is shaded by a kernel of its own that neither
+ * samples nor queues a ray and evaluates the direct light of the vertices that can receive any on full waves; 0: by the kernel of
+ * the other bounces.  Same bits either way; RGK_LAST_VERTEX), "time_post" (0 / 1, default 0: HIP events
  * around the launches of the feature pass and the denoiser, read with rgk_scene_get_post_timing).  Their initial values are read from the environment
- * (RGK_ENTRY_POINTS, RGK_ENTRY_CAP, RGK_LIGHT_ENTRY, RGK_CONST_LIGHT, RGK_SAMPLE_GROUP, RGK_BATCH_PATHS, RGK_WORKSPACE_GB) ONCE, in
+ * (RGK_ENTRY_POINTS, RGK_ENTRY_CAP, RGK_LIGHT_ENTRY, RGK_CONST_LIGHT, RGK_LAST_VERTEX, RGK_SAMPLE_GROUP, RGK_BATCH_PATHS, RGK_WORKSPACE_GB) ONCE, in
  * rgk_scene_create; a round never reads the environment.  Not while a round is in flight on this scene. */
 int rgk_scene_set_tuning(rgk_scene *scene, const char *key, double value);
 

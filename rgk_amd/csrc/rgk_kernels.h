@@ -102,7 +102,8 @@ void rgk_launch_trace_shadow_jobs(hipStream_t st, const DevScene& sc, const Pass
                                   float4* tot, const RgkWalk& w, unsigned long long* stats);
 void rgk_launch_shade(hipStream_t st, const DevScene& sc, const DevCamera& cam, const PassParams& pp, uint32_t bounce, const float4* rayA,
                       const float4* rayB, const float4* hit, float4* thr, float4* tot, float4* nextA, float4* nextB, float4* shA,
-                      float4* shB, float4* shC, uint32_t* counters, uint32_t bound, bool bdpt = false, bool const_light = false);
+                      float4* shB, float4* shC, uint32_t* counters, uint32_t bound, bool bdpt = false, bool const_light = false,
+                      bool last_vertex = false); // last_vertex: at the last bounce of a unidirectional pass (rgk_plan.h rgk_last_bounce) the fast launch is k_last_vertex
 // the constant-light route (rgk.h rgk_scene_info::const_light; never with bdpt): rgk_launch_shade(const_light = true) queues shadow
 // rays as shA = {d.xyz, far}, shB = {radiance.rgb, slot} when rgk_const_light_records() says so, and rgk_launch_trace_shadow(rec32 =
 // true) traces them

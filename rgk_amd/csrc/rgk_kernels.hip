@@ -5,7 +5,8 @@
 //                        k_trace_closest K2  FindIntersectKdOtherThan  reference src/scene_intersect.cpp:211-327 + src/primitives.cpp:75-166
 //                        k_trace_shadow[_first][_cl], k_trace_shadow_jobs  K5  Scene::Visibility + accumulate  reference src/scene.cpp:670-673, src/path_tracer.cpp:431,455-457
 //   rgk_shade.h          k_shade  K3/K4/K6/K7  GeneratePath body + NEE + compaction  reference src/path_tracer.cpp:134-300,427-460,485-496;
-//                        the queue records, the compaction and the path step that k_shade_light shares with it
+//                        the queue records, the compaction and the path step that k_shade_light shares with it;
+//                        k_last_vertex  the last bounce of a unidirectional pass: k_shade's last vertex in two phases (ring: rgk_ring.h)
 //   rgk_bdpt.h           k_raygen_light, k_list_hits, k_shade_light, k_connect  K8  the bidirectional half (reverse > 0)
 //   rgk_resolve.h        k_resolve[_tiled]  K9  clamp / NaN scrub / AddPixel  reference src/path_tracer.cpp:502-507, src/tracer.cpp:18, src/texture.cpp:342-347
 //                        k_build_pixel_list, k_build_halton_table, k_init_counters  Tracer::Render pixel order + seeds; halton_raw per round
@@ -13,7 +14,7 @@
 //                        k_libm_eval: the unit-level entries of rgk_probe.cpp; no round launches them
 //   rgk_entry.h          k_entry_points, k_group_trange_wave, k_entry_points_light  where a pixel group's camera rays / first shadow rays
 //                        start in the tree (no reference counterpart: work shared by the rays of a group)
-//   here                 k_stage_mark, beside its launcher
+//   here                 k_stage_mark, beside its launcher; at the end of the file the launcher that instantiates k_last_vertex
 // The order of the includes, and of the launchers that instantiate kernel templates, is the order of the kernels in the assembly:
 // a kernel's labels carry its number in the file, so a reordering changes the text of every kernel behind it
 // (tools/device_code_diff.sh, profiles/shade_pieces_device_code.txt).
@@ -97,14 +98,20 @@ void rgk_launch_trace_shadow(hipStream_t st, const DevScene& sc, const RgkTraceC
 }
 
 // ------------------------------------------------------------------ rgk_shade.h
+// (k_last_vertex is instantiated at the end of this file -- its place in the assembly, behind every kernel that was there before it)
+static void launch_last_vertex(hipStream_t st, const DevScene& sc, const PassParams& pp, uint32_t bounce, const float4* rayA, const float4* rayB, const float4* hit,
+                               const float4* thr, float4* tot, float4* shA, float4* shB, float4* shC, uint32_t* counters, uint32_t bound, bool const_light);
 void rgk_launch_shade(hipStream_t st, const DevScene& sc, const DevCamera& cam, const PassParams& pp, uint32_t bounce, const float4* rayA,
                       const float4* rayB, const float4* hit, float4* thr, float4* tot, float4* nextA, float4* nextB, float4* shA,
-                      float4* shB, float4* shC, uint32_t* counters, uint32_t bound, bool bdpt, bool const_light) {
+                      float4* shB, float4* shC, uint32_t* counters, uint32_t bound, bool bdpt, bool const_light, bool last_vertex) {
     const RgkGridPair g = rgk_shade_grids(bounce, bound);
+    // every vertex of the launch is its path's last: the fast launch is k_last_vertex, the GENERIC one k_shade on the list it fills
+    const bool lv = last_vertex && rgk_last_bounce(bounce, pp.depth, bdpt);
     // the second launch shades the vertices the first one listed (materials on the generic BxDF route); it returns at once when there are none
     auto pair = [&](auto first, auto bd, auto cl) {
         constexpr bool FIRST = decltype(first)::value, BDPT = decltype(bd)::value, CL = decltype(cl)::value;
-        k_shade<false, FIRST, BDPT, CL><<<g.fast, g.block, RGK_LDS_SHADE_BYTES, st>>>(sc, cam, pp, bounce, rayA, rayB, hit, thr, tot, nextA, nextB, shA, shB, shC, counters);
+        if (!lv) k_shade<false, FIRST, BDPT, CL><<<g.fast, g.block, RGK_LDS_SHADE_BYTES, st>>>(sc, cam, pp, bounce, rayA, rayB, hit, thr, tot, nextA, nextB, shA, shB, shC, counters);
+        else launch_last_vertex(st, sc, pp, bounce, rayA, rayB, hit, thr, tot, shA, shB, shC, counters, bound, CL);
         k_shade<true, FIRST, BDPT, CL><<<g.generic, g.block, RGK_LDS_SHADE_BYTES, st>>>(sc, cam, pp, bounce, rayA, rayB, hit, thr, tot, nextA, nextB, shA, shB, shC, counters);
     };
     constexpr std::true_type T{}; constexpr std::false_type F{};
@@ -201,4 +208,12 @@ void rgk_launch_group_trange(hipStream_t st, const PassParams& pp, const float4*
 void rgk_launch_light_entry_points(hipStream_t st, const DevScene& sc, const DevCamera& cam, const PassParams& pp, uint32_t n_pixels_round, const uint32_t* trange, int* entries, float4* lbox) {
     const RgkGroupRange g = rgk_group_range(pp.j0, pp.npix);
     k_entry_points_light<<<(g.count() + 63u) / 64u, 64, 0, st>>>(sc, cam, pp.xres, pp.yres, pp.pix_xy, n_pixels_round, g.first, g.count(), trange, entries, lbox);
+}
+
+// ------------------------------------------------------------------ rgk_shade.h, k_last_vertex (declared above rgk_launch_shade)
+static void launch_last_vertex(hipStream_t st, const DevScene& sc, const PassParams& pp, uint32_t bounce, const float4* rayA, const float4* rayB, const float4* hit,
+                               const float4* thr, float4* tot, float4* shA, float4* shB, float4* shC, uint32_t* counters, uint32_t bound, bool const_light) {
+    const int grid = rgk_last_vertex_grid(bound);
+    if (const_light) k_last_vertex<true><<<grid, RGK_SHADE_BLOCK_LATER, RGK_LDS_SHADE_BYTES, st>>>(sc, pp, bounce, rayA, rayB, hit, thr, tot, shA, shB, shC, counters);
+    else k_last_vertex<false><<<grid, RGK_SHADE_BLOCK_LATER, RGK_LDS_SHADE_BYTES, st>>>(sc, pp, bounce, rayA, rayB, hit, thr, tot, shA, shB, shC, counters);
 }

@@ -96,6 +96,16 @@ inline RgkGridPair rgk_pair_grids(int block, uint32_t bound) {
     return {rgk_bounded_grid(RGK_CUS * 4 * 512 / block, bound, (uint32_t)block), rgk_bounded_grid(RGK_CUS * 2 * 512 / block, bound, (uint32_t)block), block};
 }
 inline RgkGridPair rgk_shade_grids(uint32_t bounce, uint32_t bound) { return rgk_pair_grids(bounce == 0 ? RGK_SHADE_BLOCK : RGK_SHADE_BLOCK_LATER, bound); }
+// The bounce whose vertices are all their paths' last (k_last_vertex, rgk_shade.h): bounce b's queue holds the vertices with
+// n == b + 1.  Bounce 0 keeps k_shade<FIRST> (it samples the path's light and starts the slot sums), bidirectional rounds k_shade<BDPT>.
+inline bool rgk_last_bounce(uint32_t bounce, uint32_t depth, bool bdpt) { return bounce >= 1 && bounce + 1 == depth && !bdpt; }
+// ... and its grid: the record ring (rgk_ring.h) leaves room for three workgroups of 256 per CU, the grid is two rounds of them.
+// (Measured on the headline, ms of the launch per step at 3 / 6 / 12 / 24 workgroups per CU: 17.18 / 17.14 / 17.03 / 17.00 -- within
+// the launch's own spread, profiles/last_vertex_kernel.txt.)
+#ifndef RGK_LAST_VERTEX_WGS
+#define RGK_LAST_VERTEX_WGS 6
+#endif
+inline int rgk_last_vertex_grid(uint32_t bound) { return rgk_bounded_grid(RGK_CUS * RGK_LAST_VERTEX_WGS, bound, RGK_SHADE_BLOCK_LATER); }
 // the light sub-path: k_shade_light's pair; k_raygen_light and k_list_hits take the pair's first grid
 inline RgkGridPair rgk_light_grids(uint32_t bound) { return rgk_pair_grids(RGK_LIGHT_BLOCK, bound); }
 constexpr int RGK_CONNECT_BLOCK = 256;

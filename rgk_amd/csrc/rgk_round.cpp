@@ -242,7 +242,7 @@ int queue_pass(rgk_scene* s, KernelLog& kl, const DevCamera& cam, PassParams& pp
         else
             rc = kl.run(RGK_K_TRACE_CLOSEST, [&] { rgk_launch_trace_closest(st, s->dev, tc, count_stats, rayA[q], rayB[q], nullptr, hit, wq, s->stats.p); });
         if (rc || (b == 0 && (rc = queue_first_hit_lists(s, kl, cam, pp, (uint32_t)P, cap_entries, light_entry)))) return rc;
-        if ((rc = kl.run(b == 0 ? RGK_K_SHADE_FIRST : RGK_K_SHADE, [&] { rgk_launch_shade(st, s->dev, cam, pp, b, rayA[q], rayB[q], hit, thr, tot, rayA[q ^ 1], rayB[q ^ 1], shA, shB, shC, cn, ub, R > 0, const_light); })) ||
+        if ((rc = kl.run(b == 0 ? RGK_K_SHADE_FIRST : RGK_K_SHADE, [&] { rgk_launch_shade(st, s->dev, cam, pp, b, rayA[q], rayB[q], hit, thr, tot, rayA[q ^ 1], rayB[q ^ 1], shA, shB, shC, cn, ub, R > 0, const_light, s->tune.last_vertex); })) ||
             (R > 0 && (rc = kl.run(RGK_K_CONNECT, [&] { rgk_launch_connect(st, s->dev, pp, b, s->jobs.p, s->rads.p, cn, ub); }))))
             return rc;
         // (the constant-light route: the shading launches above left 32-byte records, shA = {d, far}, shB = {radiance, slot})

@@ -57,6 +57,7 @@ RgkTuning read_tuning() {
     RgkTuning t;
     t.entry_points = !off("RGK_ENTRY_POINTS"); t.entry_cap = !off("RGK_ENTRY_CAP"); t.light_entry = !off("RGK_LIGHT_ENTRY");
     t.const_light = !off("RGK_CONST_LIGHT");
+    t.last_vertex = !off("RGK_LAST_VERTEX");
     if (const char* e = std::getenv("RGK_SAMPLE_GROUP")) t.sample_group = std::min(6, std::max(0, std::atoi(e)));
     if (const char* e = std::getenv("RGK_BATCH_PATHS")) t.batch_paths = std::max<size_t>(1024, strtoull(e, nullptr, 10));
     if (const char* e = std::getenv("RGK_WORKSPACE_GB")) t.workspace_gb = atof(e);
@@ -311,6 +312,7 @@ int rgk_scene_set_tuning(rgk_scene* s, const char* key, double value) {
     else if (k == "entry_cap") t.entry_cap = value != 0;
     else if (k == "light_entry") t.light_entry = value != 0;
     else if (k == "const_light") t.const_light = value != 0;
+    else if (k == "last_vertex") t.last_vertex = value != 0;
     else if (k == "sample_group") t.sample_group = value < 0 ? -1 : (int)std::min(6.0, value);
     else if (k == "batch_paths") t.batch_paths = value <= 0 ? 0 : std::max<size_t>(1024, (size_t)value);
     else if (k == "workspace_gb") t.workspace_gb = value <= 0 ? 0.0 : value;

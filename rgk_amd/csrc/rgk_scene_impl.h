@@ -73,7 +73,7 @@ int down(T* dst, const DevBuf<T>& b, size_t count) {
 }
 
 // Tuning switches of one scene (nothing here changes a result).  Filled ONCE, by read_tuning in rgk_scene_create, from the
-// environment (RGK_ENTRY_POINTS, RGK_ENTRY_CAP, RGK_LIGHT_ENTRY, RGK_CONST_LIGHT, RGK_SAMPLE_GROUP, RGK_BATCH_PATHS, RGK_WORKSPACE_GB,
+// environment (RGK_ENTRY_POINTS, RGK_ENTRY_CAP, RGK_LIGHT_ENTRY, RGK_CONST_LIGHT, RGK_LAST_VERTEX, RGK_SAMPLE_GROUP, RGK_BATCH_PATHS, RGK_WORKSPACE_GB,
 // RGK_BEAM, RGK_DEBUG_BVH, RGK_DEBUG_UTIL); afterwards only rgk_scene_set_tuning changes them -- a round never reads the environment
 // (round 2 did, per round: process-global state under a host that may render from two threads).  The build switches are read
 // at the same moment, by read_build_options (rgk_commit.h).
@@ -82,6 +82,7 @@ struct RgkTuning {
     bool entry_cap = true;    // ... capped behind the group's first hits from a frame's second round on
     bool light_entry = true;  // first-vertex shadow rays of a single-light scene start at light-side entry nodes
     bool const_light = true;  // eligible scenes (rgk_scene_info::const_light): unidirectional rounds take the light as a launch constant
+    bool last_vertex = true;  // the last bounce of a unidirectional pass is shaded by k_last_vertex (rgk_shade.h); false: by k_shade
     int sample_group = -1;    // log2 of the samples of a pixel side by side in the slot order; -1: the compiled default
     size_t batch_paths = 0;   // paths per pass; 0: sized from the memory that is free
     double workspace_gb = 0;  // ... or from this many GB; 0: 96 (160 for bidirectional rounds), at most 60 % of what is free

@@ -1,11 +1,12 @@
 // Shading: k_shade (K3 / K4 / K6 / K7) and the pieces the shading kernels of both sub-paths use (k_shade here, k_shade_light and
 // k_raygen_light in rgk_bdpt.h): the queue records, the path's sampler coordinates, the workgroup compaction and the sampling half
 // of a path vertex.  The geometric half -- Vertex, surface_point(), clamp3 -- is in rgk_device.h: the feature pass (rgk_post.hip)
-// and the walkers (rgk_trace.h) use it too.
+// and the walkers (rgk_trace.h) use it too.  At the end of the file: k_last_vertex, the last bounce of a unidirectional pass.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "rgk_device.h"
 #include "rgk_kernels.h"
+#include "rgk_ring.h"
 #include "rgk_trace.h" // camera_ray_of_slot, slot_decode
 
 #ifndef RGK_SKIP_DEAD_NEE
@@ -408,5 +409,256 @@ __global__ __launch_bounds__((FIRST ? RGK_SHADE_BLOCK : RGK_SHADE_BLOCK_LATER), 
             }
             __syncthreads(); // s_cnt / s_base are rewritten by the next iteration
         }
+    }
+}
+
+// ------------------------------------------------------------------ the last bounce of a unidirectional pass: k_last_vertex
+// At bounce b the queue holds the vertices with n == b + 1, so at b + 1 == depth EVERY vertex of the launch is its path's last
+// (k_shade's `ends`, there a per-lane test): nothing is sampled, no ray follows, thr[slot] is read and never written.  What is
+// left of k_shade<false, false, false, CL> is two halves, and they are the two functions below -- k_shade's expressions in
+// k_shade's order (-ffp-contract=off: the same operations on the same operands are the same bits):
+//   last_vertex_geometry   hit, ray and path state -> a sky vertex's addition, or the vertex from its triangle record to the
+//                          `nee_dead` test, the deferral test (the GENERIC launch that follows is k_shade<true, false, false, CL>
+//                          on the list this kernel fills) and the emission's addition; a LIVE vertex -- one whose light is above
+//                          both horizons -- leaves a LastVertex;
+//   last_vertex_nee        LastVertex -> texels, LTC entry, BxDF value, G, the clamp, A - B: the shadow record, if any.
+// Bounce rays scatter, so the 64 vertices of a wave are unrelated and under half of them are live (Sponza: 45 % live, 48 % dead,
+// 7 % sky): run back to back per lane -- as k_shade does, and as a one-phase build of this kernel did, which measured no faster than
+// k_shade -- the second half has most lanes of every wave masked off.  k_last_vertex runs the halves as two phases of
+// the workgroup with a record ring in LDS between them (rgk_ring.h): phase A, a thread per queue entry, appends the live vertices;
+// phase B, a thread per record, runs on full waves whenever a workgroup's worth is pending, and once behind the loop.
+struct LastVertex {
+    f3 pos, lightN, VrL, contribution;
+    quatf g2l;
+    float2 uv;
+    uint32_t slot, matf; // matf: material id | the vertex faces the viewer (bit 31: e_front is the material's emission)
+    float4 li;           // the path's light {pos, code} (CL: not read, the launch constant)
+};
+#define RGK_LV_FRONT 0x80000000u
+template <bool CL>
+__device__ __forceinline__ DLight last_vertex_light(const DevScene& sc, float4 li) {
+    return CL ? light_constant(sc) : light_from_code(sc, mk3(li.x, li.y, li.z), __float_as_uint(li.w));
+}
+// returns: live.  defer: the vertex goes on the GENERIC list.
+template <bool CL>
+__device__ __forceinline__ bool last_vertex_geometry(const DevScene& sc, const PassParams& pp, uint32_t i, const float4* __restrict__ rayA, const float4* __restrict__ rayB,
+                                                     const float4* __restrict__ hit, const float4* __restrict__ thr, float4* __restrict__ tot, bool& defer, LastVertex& v) {
+    const float4 h = hit[i];
+    const float4 a = rayA[i], b = rayB[i];
+    const uint32_t slot = ray_rec_slot(b);
+    const f3 o = ray_rec_o(a), d = ray_rec_d(a, b);
+    const float4 st = thr[slot];
+    const float4 li = CL ? make_float4(sc.cl_pos[0], sc.cl_pos[1], sc.cl_pos[2], __uint_as_float(0u)) : pp.light[slot];
+    const f3 tot0 = mk3(0.f, 0.f, 0.f);
+    const f3 cum = mk3(st.x, st.y, st.z);
+    const int tri = __float_as_int(h.w);
+    const f3 Vr = -d;
+    defer = false;
+    if (tri < 0) {
+        f3 sky = skybox(sc, Vr);
+        f3 add = cum * sky;
+        slot_add<false>(tot, slot, tot0, add);
+        return false;
+    }
+    const uint32_t tsr = (uint32_t)tri * (uint32_t)sizeof(TriShade);
+    const float4 g0 = gld_f4(sc.tri_shade, tsr), g1 = gld_f4(sc.tri_shade, tsr + 16u), g2 = gld_f4(sc.tri_shade, tsr + 32u);
+    const uint32_t mat_id = gld_u32(sc.tri_shade, tsr + 96u);
+    const DevMaterial mat = mat_load(sc, mat_id);
+    defer = !mat_is_fast(mat.kind);
+    if (defer) return false;
+    const float al = h.y, be = h.z;
+    const float ia = 1.0f - al - be, ib = al, ic = be;
+    f3 pos = o + h.x * d;
+    f3 nA_ = mk3(g0.x, g0.y, g0.z), nB_ = mk3(g1.x, g1.y, g1.z), nC_ = mk3(g2.x, g2.y, g2.z);
+    bool ok;
+    f3 faceN = face_normal(ia, ib, ic, nA_, nB_, nC_, ok);
+    if (!ok) return false;
+    faceN = norm3(faceN);
+    const float4 g3 = gld_f4(sc.tri_shade, tsr + 48u), g4 = gld_f4(sc.tri_shade, tsr + 64u), g5 = gld_f4(sc.tri_shade, tsr + 80u);
+    float2 uv = make_float2(0.f, 0.f);
+    if (sc.has_texcoords) {
+        uv.x = ia * g0.w + ib * g2.w + ic * g4.w;
+        uv.y = ia * g1.w + ib * g3.w + ic * g5.w;
+    }
+    const bool bumped = tex_kind(mat.t_bump) != RGK_TEXREF_NONE;
+    f3 lightN = faceN;
+    if (bumped) {
+        float right, bottom;
+        tex_slopes(sc, mat.t_bump, uv, right, bottom);
+        f3 tangent = ia * mk3(g3.x, g3.y, g3.z) + ib * mk3(g4.x, g4.y, g4.z) + ic * mk3(g5.x, g5.y, g5.z);
+        if (!(tangent.x * tangent.x + tangent.y * tangent.y + tangent.z * tangent.z < 0.001f)) {
+            tangent = norm3(tangent);
+            f3 bitangent = norm3(cross3(faceN, tangent));
+            f3 tangent2 = cross3(bitangent, faceN);
+            lightN = norm3(faceN + (tangent2 * right + bitangent * bottom) * pp.bumpmap_scale);
+            if (lightN.x != lightN.x) lightN = faceN;
+        }
+    }
+    const quatf g2l = rotation_between(lightN, mk3(0.f, 0.f, 1.f));
+    const f3 VrL = qrot(g2l, Vr);
+    const DLight L = last_vertex_light<CL>(sc, li);
+    bool nee_dead = false;
+    if (RGK_SKIP_DEAD_NEE) {
+        if (L.type < 0) nee_dead = true;
+        else {
+            const f3 df = pos - L.pos;
+            nee_dead = dot3(df, df) > 0.f && (qrot(g2l, norm3(L.pos - pos)).z <= 0.f || VrL.z <= 0.f);
+        }
+    }
+    const f3 contribution = cum;
+    const bool front = dot3(faceN, Vr) > 0;
+    f3 e_front = mk3(0.f, 0.f, 0.f);
+    if (front) e_front = mk3(mat.emission[0], mat.emission[1], mat.emission[2]);
+    const bool has_e = (e_front.x != 0.f) || (e_front.y != 0.f) || (e_front.z != 0.f);
+    if (has_e) {
+        f3 B = clamp3(mk3(0.f, 0.f, 0.f) + e_front, pp.clamp) * contribution;
+        slot_add<false>(tot, slot, tot0, B);
+    }
+    v.pos = pos; v.lightN = lightN; v.VrL = VrL; v.contribution = contribution; v.g2l = g2l; v.uv = uv;
+    v.slot = slot; v.matf = mat_id | (front ? RGK_LV_FRONT : 0u); v.li = li;
+    return L.type >= 0 && !nee_dead;
+}
+// returns: the vertex leaves a shadow ray, sA / sB (/ sC) its record
+template <bool CL>
+__device__ __forceinline__ bool last_vertex_nee(const DevScene& sc, const PassParams& pp, const LastVertex& v, float4& sA, float4& sB, float4& sC) {
+    const float eps = sc.epsilon;
+    const uint32_t mat_id = v.matf & ~RGK_LV_FRONT;
+    const DevMaterial mat = mat_load(sc, mat_id);
+    const DLight L = last_vertex_light<CL>(sc, v.li);
+    MatPrep mp;
+    mat_prepare(sc, mat, v.uv, v.VrL, false, mp);
+    const f3 pos = v.pos, contribution = v.contribution;
+    f3 e_front = mk3(0.f, 0.f, 0.f);
+    if (v.matf & RGK_LV_FRONT) e_front = mk3(mat.emission[0], mat.emission[1], mat.emission[2]);
+    const bool has_e = (e_front.x != 0.f) || (e_front.y != 0.f) || (e_front.z != 0.f);
+    f3 B = mk3(0.f, 0.f, 0.f);
+    if (has_e) B = clamp3(mk3(0.f, 0.f, 0.f) + e_front, pp.clamp) * contribution;
+    const f3 diff = pos - L.pos;
+    const f3 sd = norm3(diff);
+    const float slen = len3(diff);
+    const f3 Vi = norm3(L.pos - pos);
+    const f3 f = mat_value<false>(sc, (int)mat_id, mat, mp, qrot(v.g2l, Vi), v.VrL, v.uv);
+    const float G = fabsf(dot3(v.lightN, Vi)) / dot3(diff, diff);
+    const float k = L.intensity * light_dir_factor(L, -Vi);
+    const f3 inc = L.color * mk3(k, k, k);
+    const f3 out = inc * (f * G);
+    f3 A = clamp3((mk3(0.f, 0.f, 0.f) + out) + e_front, pp.clamp) * contribution;
+    f3 rad = has_e ? A - B : A;
+    if (!(rad.x != 0.f || rad.y != 0.f || rad.z != 0.f)) return false;
+    if (CL && RGK_CL_REC32) {
+        sA = cl_rec_a(sd, slen - eps * 20.0f);
+        sB = cl_rec_b(rad, v.slot);
+    } else {
+        sA = shadow_rec_a(L.pos, sd);
+        sB = shadow_rec_b(sd, slen - eps * 20.0f, v.slot);
+        sC = shadow_rec_c(rad, 0.0f + eps * 20.0f);
+    }
+    return true;
+}
+
+// A LastVertex in the ring, SoA by field: ring[field * capacity + position], 20 dwords.  The path's light is not among them: off
+// the constant-light route phase B reads pp.light[slot] again.  (With the light's four dwords the ring is 48 KB, two workgroups per
+// CU instead of three, and the launch measured SLOWER than k_shade on the headline with the route switched off: 21.9 against 20.5 ms.)
+constexpr uint32_t RGK_LV_FIELDS = 20;
+__device__ __forceinline__ void last_vertex_put(float* ring, uint32_t cap, uint32_t p, const LastVertex& v) {
+    const float f[RGK_LV_FIELDS] = {v.pos.x, v.pos.y, v.pos.z, v.lightN.x, v.lightN.y, v.lightN.z, v.VrL.x, v.VrL.y, v.VrL.z,
+                                    v.contribution.x, v.contribution.y, v.contribution.z, v.g2l.x, v.g2l.y, v.g2l.z, v.g2l.w, v.uv.x, v.uv.y,
+                                    __uint_as_float(v.slot), __uint_as_float(v.matf)};
+#pragma unroll
+    for (uint32_t k = 0; k < RGK_LV_FIELDS; k++) ring[k * cap + p] = f[k];
+}
+template <bool CL>
+__device__ __forceinline__ void last_vertex_get(const PassParams& pp, const float* ring, uint32_t cap, uint32_t p, LastVertex& v) {
+    float f[RGK_LV_FIELDS];
+#pragma unroll
+    for (uint32_t k = 0; k < RGK_LV_FIELDS; k++) f[k] = ring[k * cap + p];
+    v.pos = mk3(f[0], f[1], f[2]); v.lightN = mk3(f[3], f[4], f[5]); v.VrL = mk3(f[6], f[7], f[8]);
+    v.contribution = mk3(f[9], f[10], f[11]);
+    v.g2l.x = f[12]; v.g2l.y = f[13]; v.g2l.z = f[14]; v.g2l.w = f[15];
+    v.uv = make_float2(f[16], f[17]);
+    v.slot = __float_as_uint(f[18]); v.matf = __float_as_uint(f[19]);
+    v.li = CL ? make_float4(0.f, 0.f, 0.f, 0.f) : pp.light[v.slot];
+}
+
+// Three waves per SIMD: the ring (40 KB) beside the 8 KB of tables leaves room for three workgroups per CU.  (shading
+// at 3 and at 4 waves per SIMD measured equal.)
+template <bool CL>
+__global__ __launch_bounds__(RGK_SHADE_BLOCK_LATER, 3) void k_last_vertex(const DevScene sc, const PassParams pp, const uint32_t bounce,
+                                                            const float4* __restrict__ rayA, const float4* __restrict__ rayB,
+                                                            const float4* __restrict__ hit, const float4* __restrict__ thr, float4* __restrict__ tot,
+                                                            float4* __restrict__ shA, float4* __restrict__ shB, float4* __restrict__ shC,
+                                                            uint32_t* __restrict__ counters) {
+    constexpr uint32_t BLK = RGK_SHADE_BLOCK_LATER, NW = BLK / 64, CAP = rgk_ring_capacity(BLK);
+    static_assert((BLK & (BLK - 1)) == 0, "the ring wraps with a mask");
+    const uint32_t count = counters[RGK_CNT_QUEUE + bounce];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    // per-wave counts of an append, in two sets that alternate (parity): a set is rewritten two appends later, behind the next
+    // append's barrier, which every thread reaches only after it has read this one
+    __shared__ uint32_t s_live[2][NW], s_defer[2][NW], s_shadow[2][NW];
+    __shared__ uint32_t s_gbase[2], s_sbase[2];
+    __shared__ float s_ring[RGK_LV_FIELDS * CAP];
+    lut_lds_fill(sc);
+    uint32_t head = 0, pending = 0, par = 0, parB = 0; // workgroup-uniform: every thread derives them from the same counts
+    // workgroup-uniform trip count, and one more trip behind the queue's end (`final`), which only takes what is left in the ring
+    for (uint32_t base = blockIdx.x * BLK;; base += gridDim.x * BLK) {
+        const bool final = !(base < count);
+        if (!final) {
+            // ---- phase A: a thread per queue entry
+            const bool valid = base + threadIdx.x < count;
+            const uint32_t i = valid ? base + threadIdx.x : 0u;
+            bool defer = false, live = false;
+            LastVertex v;
+            if (valid) live = last_vertex_geometry<CL>(sc, pp, i, rayA, rayB, hit, thr, tot, defer, v);
+            // append: deferred vertices to the GENERIC list (one atomic per workgroup), live ones to the ring
+            const unsigned long long ml = __ballot(live), md = __ballot(defer);
+            if (lane == 0) { s_live[par][w] = __popcll(ml); s_defer[par][w] = __popcll(md); }
+            __syncthreads();
+            uint32_t lbefore = 0, ltotal = 0, dbefore = 0, dtotal = 0;
+#pragma unroll
+            for (uint32_t k = 0; k < NW; k++) {
+                const uint32_t c = s_defer[par][k], l = s_live[par][k];
+                if (k < (uint32_t)w) { dbefore += c; lbefore += l; }
+                dtotal += c; ltotal += l;
+            }
+            if (dtotal) { // (workgroup-uniform)
+                if (threadIdx.x == 0) s_gbase[par] = atomicAdd(&counters[RGK_CNT_GENERIC + bounce], dtotal);
+                __syncthreads();
+                if (defer) pp.generic[s_gbase[par] + dbefore + lane_rank(md, lane)] = i;
+            }
+            par ^= 1u;
+            if (live) last_vertex_put(s_ring, CAP, rgk_ring_append_at(head, pending, lbefore + lane_rank(ml, lane), BLK), v);
+            pending += ltotal;
+        }
+        // ---- phase B: a thread per record, for a workgroup's worth of them (behind the queue's end: for what is left)
+        const uint32_t n = rgk_ring_take(pending, BLK, final);
+        if (n) { // (workgroup-uniform)
+            __syncthreads(); // the records are written
+            float4 sA = make_float4(0, 0, 0, 0), sB = sA, sC = sA;
+            bool shadow = false;
+            if (threadIdx.x < n) {
+                LastVertex v;
+                last_vertex_get<CL>(pp, s_ring, CAP, rgk_ring_read_at(head, threadIdx.x, BLK), v);
+                shadow = last_vertex_nee<CL>(sc, pp, v, sA, sB, sC);
+            }
+            // the workgroup's range of the shadow queue: one atomic
+            const unsigned long long ms = __ballot(shadow);
+            if (lane == 0) s_shadow[parB][w] = __popcll(ms);
+            __syncthreads();
+            uint32_t before = 0, total = 0;
+#pragma unroll
+            for (uint32_t k = 0; k < NW; k++) { const uint32_t c = s_shadow[parB][k]; if (k < (uint32_t)w) before += c; total += c; }
+            if (total) { // (workgroup-uniform)
+                if (threadIdx.x == 0) s_sbase[parB] = atomicAdd(&counters[RGK_CNT_SHADOW + bounce], total);
+                __syncthreads();
+                if (shadow) {
+                    const uint32_t p = s_sbase[parB] + before + lane_rank(ms, lane);
+                    shA[p] = sA; shB[p] = sB;
+                    if (!(CL && RGK_CL_REC32)) shC[p] = sC;
+                }
+            }
+            parB ^= 1u;
+            head = rgk_ring_wrap(head + n, BLK); pending -= n;
+        }
+        if (final) break;
     }
 }

@@ -78,7 +78,9 @@ class Scene:
 
     def set_tuning(self, **kw):
         """rgk_scene_set_tuning: per-scene tuning switches (entry_points, entry_cap, light_entry, sample_group, batch_paths,
-        workspace_gb, beam, const_light); none changes a result.
+        workspace_gb, beam, const_light, last_vertex); none changes a result.
+
+        last_vertex (default 1): the last bounce of a unidirectional pass is shaded by k_last_vertex; 0: by k_shade.
 
         const_light (default 1): where info().const_light == 1 -- one point light of size 0, nothing else that emits, no -0.0 in
         its position, and the light pick's own float comparisons select it for the largest sample 1 - 2^-24 -- unidirectional
