@@ -454,7 +454,9 @@ int rgk_denoise_device(rgk_scene *scene, uint32_t xres, uint32_t yres, const flo
  * call (which = 1: preparation, one per iteration, finish), variance-guided denoise call (which = 2: preparation, prefilter, one
  * per iteration, finish [, variance copy]), noise estimate (which = 3: the tile sums) or round fold (which = 4: the copy of the tile
  * list and the fold) on this scene, in ms; recorded only while
- * the tuning key "time_post" is 1. *n: in, room in ms; out, entries the call had (those that fit are written). */
+ * the tuning key "time_post" is 1. *n: in, room in ms; out, entries the call had (those that fit are written).
+ * which = 5: the temporal pair -- {the last rgk_temporal_reproject_device, the last rgk_temporal_blend_device}, one launch each;
+ * two entries once either has run with "time_post" on, 0 ms for the one that has not. */
 int rgk_scene_get_post_timing(const rgk_scene *scene, uint32_t which, double *ms, uint32_t *n);
 
 /* ---- noise estimate from two half-buffers and the variance-guided filter (DESIGN.md "Half-buffer noise estimate") ----
@@ -531,6 +533,59 @@ int rgk_adapt_select(const rgk_noise_tile *tiles, const uint32_t *visits, uint32
 int rgk_round_fold_device(rgk_scene *scene, uint32_t xres, uint32_t yres, const rgk_tile *tiles, uint32_t n_tiles,
                           const uint8_t *to_half /* n_tiles */, float *d_round_rgb, uint32_t *d_round_count, float *d_total_rgb,
                           uint32_t *d_total_count, float *d_half_rgb, uint32_t *d_half_count);
+
+/* ---- temporal reuse for a moving camera over static geometry (DESIGN.md "Temporal reuse") ----
+ *
+ * A history image {h.rgb, L} -- the demodulated colour a pixel has gathered over the frames before this one and the number of frames
+ * in it, a float -- is carried from the previous frame's pixels to the current frame's (reproject) and the current frame's samples
+ * are blended into it (blend).  Both entries: all pointers DEVICE pointers on the scene's GPU, planes row-major from the top row,
+ * P = xres * yres; whole frame; one launch on the scene's stream; blocking.  No output may be one of the inputs (or another output).
+ * Arguments are checked before the scene or the device is touched; not while a round is in flight on this scene.  They use no
+ * buffer, list or counter a round reads or writes, and no workspace of the scene at all.  Everything below is float32, only
+ * + - * / max min sqrt floor, no contraction, in the order written; a . b = (a.x * b.x + a.y * b.y) + a.z * b.z, len(a) = sqrt(a . a);
+ * sums over taps start at 0 and add the counted taps in tap order. */
+typedef struct rgk_temporal_params {
+    float plane_tol;     /* >= 0: a tap's surface plane may be this far from the pixel's point, as a share of its distance */
+    float normal_cos;    /* in [-1, 1]: the smallest n_p . n_q a tap may have */
+    float alpha_min;     /* in (0, 1]: the smallest weight the current frame gets */
+    float max_len;       /* >= 1: where the history length stops growing */
+    uint32_t demodulate; /* blend only */
+    float albedo_floor;  /* >= 0, blend only: rgk_denoise_var_params' floor on the divisor */
+} rgk_temporal_params;
+/* Per pixel p = (x, y) of the current frame.  The lens of both cameras is ignored, as by rgk_render_aov_device, whose depth /
+ * normal / tri planes for the two cameras the six feature planes are.
+ *   (o, d) = the ray rgk_render_aov_device traces for p through cam_cur;  hit = tri_cur[p] >= 0
+ *   x_p = o + d * z_p;  v = hit ? x_p - o_prev : d         (a miss is a point at infinity: sky is reprojected by direction)
+ * No history -- hist_len = 0, hist_rgb = 0 -- for
+ *   a hit whose triangle's top-level material is mirror, dielectric or transparent (its radiance depends on the view; a triangle
+ *   id that is not the scene's gets none either), a hit whose normal is zero, and !(q > 0) with N = cam_prev->direction, q = v . N.
+ * Else into the previous frame, vs / vx / vy = cam_prev's viewscreen, viewscreen_x, viewscreen_y:
+ *   s = ((vs - o_prev) . N) / q;   w = (o_prev + v * s) - vs;   a = (w . vx) / (vx . vx);   b = (w . vy) / (vy . vy)
+ *   fx = a * xres - 0.5f;  fy = b * yres - 0.5f;   no history unless fx > -1 && fx < xres && fy > -1 && fy < yres
+ *   ix = (int)floor(fx), tx = fx - ix, likewise y; taps (ix, iy), (ix+1, iy), (ix, iy+1), (ix+1, iy+1) with the weights
+ *   (1-tx)*(1-ty), tx*(1-ty), (1-tx)*ty, tx*ty
+ * A tap q counts when it is inside the frame, hist_len_prev[q] > 0, and
+ *   miss:  tri_prev[q] < 0
+ *   hit:   tri_prev[q] >= 0,  n_p . n_q >= normal_cos,  |(x_p - (o_prev + d_q * z_q)) . n_q| <= plane_tol * len(v)
+ *          (d_q: cam_prev's ray through the centre of q -- the distance to the previous surface's plane)
+ *   hist_rgb = sum(w * c_q) / sum(w),  hist_len = sum(w * len_q) / sum(w);  sum(w) == 0: no history.
+ * Every member of params is checked by both entries (the ranges beside the members, all finite), whichever of them it reads. */
+int rgk_temporal_reproject_device(rgk_scene *scene, uint32_t xres, uint32_t yres, const rgk_camera *cam_cur, const rgk_camera *cam_prev,
+                                  const float *d_depth_cur /*P*/, const float *d_normal_cur /*3P*/, const int32_t *d_tri_cur /*P*/,
+                                  const float *d_depth_prev, const float *d_normal_prev, const int32_t *d_tri_prev,
+                                  const float *d_hist_rgb_prev /*3P*/, const float *d_hist_len_prev /*P floats*/,
+                                  const rgk_temporal_params *params, float *d_hist_rgb /*3P out*/, float *d_hist_len /*P out*/);
+/* Per pixel: c = accum_rgb / accum_count (0 where the count is 0); per channel div = demodulate ? (albedo > 0 ? max(albedo,
+ * albedo_floor) : 1) : 1;  m = c / div;  h = hist_rgb, L = hist_len.
+ *   L > 0:  alpha = max(1 / (L + 1), alpha_min);  m' = (m - h) * alpha + h;  L' = min(L + 1, max_len)
+ *   else:   m' = m;  L' = 1
+ *   a pixel whose count is 0 keeps its history unblended: m' = h, L' = L
+ *   out_hist_rgb = m' (demodulated: the next frame's history), out_hist_len = L', out_rgb = m' * div (the image to filter or write)
+ * d_albedo may be NULL when demodulate == 0. */
+int rgk_temporal_blend_device(rgk_scene *scene, uint32_t xres, uint32_t yres, const float *d_accum_rgb, const uint32_t *d_accum_count,
+                              const float *d_albedo, const float *d_hist_rgb, const float *d_hist_len,
+                              const rgk_temporal_params *params, float *d_out_hist_rgb /*3P*/, float *d_out_hist_len /*P*/,
+                              float *d_out_rgb /*3P*/);
 
 /* The pinned transcendental functions of the path (include/rgk_libm.h) evaluated on the device, for the test that the GPU
  * and the CPU produce the same bits: fn 0 sin, 1 cos, 2 acos, 3 asin, 4 atan2(a[i], b[i]) (b may be NULL otherwise). */

@@ -27,6 +27,11 @@
   --adaptive [N]    needs --until-noise: from the second round on a round renders only the 32 x 32 tiles whose own noise is still above
                     their share of the target; every tile is rendered at least N times (default 4, at least 2).  Not with
                     bidirectional rounds ("reverse" > 0)
+  --temporal        needs --denoise; for camera animations (-r) over static geometry: after a frame's last round the `denoised` image
+                    is written once more from the frame blended into the history the frames before it left -- reprojected through
+                    the two cameras, tested against depth, normal and triangle planes -- and then filtered; the blend becomes the
+                    next frame's history.  A frame skipped by --no-overwrite or resumed from a checkpoint starts the chain again
+                    (the history is not checkpointed).  Not with --noise, --until-noise or --adaptive.  Every other file is unchanged
 FILE is a .json or .rtc scene config.  One process drives one GPU; several GPUs: python -m torch.distributed.run ... bench.py.
 """
 import argparse
@@ -89,12 +94,16 @@ def main(argv=None):
     ap.add_argument("--noise", action="store_true")
     ap.add_argument("--until-noise", type=float, default=None, metavar="X")
     ap.add_argument("--adaptive", type=int, nargs="?", const=4, default=None, metavar="MIN_VISITS")
+    ap.add_argument("--temporal", action="store_true")
     ap.add_argument("--frames", type=int, default=None, help="with -r: stop after this many frames (default: all 501)")
     args = ap.parse_args(argv)
     verbosity = max(0, 2 + args.v - args.q)
     say = lambda lvl, *a: print(*a) if verbosity >= lvl else None
     if args.adaptive is not None and (args.until_noise is None or args.adaptive < 2):
         print("ERROR: --adaptive needs --until-noise." if args.until_noise is None else "ERROR: Invalid argument for --adaptive (at least 2).")
+        return 1
+    if args.temporal and (not args.denoise or args.noise or args.until_noise is not None or args.adaptive is not None):
+        print("ERROR: --temporal needs --denoise." if not args.denoise else "ERROR: --temporal cannot be combined with --noise, --until-noise or --adaptive.")
         return 1
     try:
         cfg = load_config(args.file)
@@ -138,11 +147,14 @@ def main(argv=None):
     no_overwrite = args.no_overwrite or args.rotate
     fps, time_length = 50.0, (10.0 if args.rotate else 0.0)
     n_frames = int(time_length * fps) + 1
+    history = rd.TemporalHistory() if args.temporal else None  # one chain across the frames of -r
     for frame_no in range(n_frames if args.frames is None else min(n_frames, args.frames)):
         t = frame_no / fps
         out = insert_file_suffix(output_file, format_int5(frame_no)) if args.rotate else output_file
         if no_overwrite and os.path.exists(out):
             say(1, f"File `{out}` exists, not overwriting.")
+            if history is not None:
+                history.reset()  # its frame is not rendered here: the chain starts again
             continue
         if args.rotate:
             open(out, "ab").close()  # claim the frame before rendering it (processes sharing the directory skip it)
@@ -150,7 +162,7 @@ def main(argv=None):
         camera = cfg.get_camera(t / time_length if args.rotate else 0.0)
         try:
             drv = rd.RenderDriver(scene, cfg, camera, device=device, track_noise=track_noise,
-                                  adaptive=capi.AdaptParams(args.until_noise, args.adaptive) if args.adaptive is not None else None)
+                                  adaptive=capi.AdaptParams(args.until_noise, args.adaptive) if args.adaptive is not None else None, history=history)
         except ValueError as e:
             print(f"ERROR: {e}")
             return 1
@@ -181,12 +193,14 @@ def main(argv=None):
                 print(f"ERROR: cannot resume from `{ckpt}`: {e}")
                 return 1
             say(2, f"Resumed from `{ckpt}`: {drv.rounds_done} rounds done.")
+            if history is not None:
+                history.reset()  # the history is not checkpointed: a resumed frame starts its chain again
         say(2, f"Writing to file {out}")
         timed = cfg.render_minutes is not None
         with FrameMonitor(scene, timed, cfg.render_rounds, cfg.render_minutes or 0, cfg.xres * cfg.yres, verbosity=verbosity) as mon:
             drv.render_frame(rounds=max(0, cfg.render_rounds - drv.rounds_done) if not timed else None, output_file=out, checkpoint=ckpt,
                              aov_files={k: insert_file_suffix(out, k) for k in ("albedo", "normal", "depth")} if args.aov else None,
-                             denoised_file=insert_file_suffix(out, "denoised") if args.denoise else None,
+                             denoised_file=insert_file_suffix(out, "denoised") if args.denoise else None, temporal=args.temporal,
                              **(dict(until_noise=args.until_noise, noise_file=insert_file_suffix(out, "noise"),
                                      on_noise=lambda r, rel, n_live=None: say(1, f"Round {r}: " + (f"{n_live} live tiles, " if n_live is not None else "") +
                                                                                   f"relative noise {rel:.4g}")) if track_noise else {}))

@@ -157,6 +157,35 @@ class AdaptParams(C.Structure):
         super().__init__(target, min_visits)
 
 
+class TemporalParams(C.Structure):
+    """rgk_temporal_params; the defaults are the shipped ones: alpha_min is the minimum of tools/temporal_sweep.py,
+    which makes max_len idle beyond 2; the sweep is flat in the other three, which keep their starting values."""
+    _fields_ = [("plane_tol", C.c_float), ("normal_cos", C.c_float), ("alpha_min", C.c_float), ("max_len", C.c_float),
+                ("demodulate", C.c_uint32), ("albedo_floor", C.c_float)]
+
+    def __init__(self, plane_tol=0.01, normal_cos=0.9, alpha_min=0.34, max_len=10.0, demodulate=1, albedo_floor=0.02):
+        super().__init__(plane_tol, normal_cos, alpha_min, max_len, demodulate, albedo_floor)
+
+    def check(self):
+        """The ranges both entries enforce, as a ValueError before anything is launched."""
+        import math
+        vals = {k: getattr(self, k) for k in ("plane_tol", "normal_cos", "alpha_min", "max_len", "albedo_floor")}
+        for k, v in vals.items():
+            if not math.isfinite(v):
+                raise ValueError(f"temporal parameter {k} must be finite, got {v}")
+        if not vals["plane_tol"] >= 0:
+            raise ValueError("plane_tol must be >= 0")
+        if not -1 <= vals["normal_cos"] <= 1:
+            raise ValueError("normal_cos must be in [-1, 1]")
+        if not 0 < vals["alpha_min"] <= 1:
+            raise ValueError("alpha_min must be in (0, 1]")
+        if not vals["max_len"] >= 1:
+            raise ValueError("max_len must be >= 1")
+        if not vals["albedo_floor"] >= 0:
+            raise ValueError("albedo_floor must be >= 0")
+        return self
+
+
 # every symbol include/rgk.h declares (tests check the .so exports all of them)
 EXPORTS = ["rgk_last_error", "rgk_device_count", "rgk_scene_create", "rgk_scene_destroy",
            "rgk_scene_get_info", "rgk_scene_get_progress", "rgk_scene_set_tuning", "rgk_scene_refit", "rgk_generate_task_list", "rgk_camera_init", "rgk_render_round",
@@ -167,7 +196,8 @@ EXPORTS = ["rgk_last_error", "rgk_device_count", "rgk_scene_create", "rgk_scene_
            "rgk_accum_download", "rgk_accum_upload", "rgk_accum_add", "rgk_accum_set_tag", "rgk_accum_save", "rgk_accum_load",
            "rgk_shard_tiles", "rgk_comm_get_unique_id", "rgk_comm_create", "rgk_comm_destroy", "rgk_accum_reduce",
            "rgk_render_aov_device", "rgk_render_aov", "rgk_denoise_device", "rgk_scene_get_post_timing",
-           "rgk_noise_estimate_device", "rgk_denoise_variance_device", "rgk_adapt_select", "rgk_round_fold_device"]
+           "rgk_noise_estimate_device", "rgk_denoise_variance_device", "rgk_adapt_select", "rgk_round_fold_device",
+           "rgk_temporal_reproject_device", "rgk_temporal_blend_device"]
 
 _p = C.POINTER
 
@@ -232,7 +262,10 @@ def _bind(lib):
     lib.rgk_adapt_select.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, _p(AdaptParams), C.c_void_p, _p(C.c_uint32), _p(C.c_uint32)]
     lib.rgk_round_fold_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, _p(Tile), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.rgk_scene_get_post_timing.argtypes = [C.c_void_p, C.c_uint32, _p(C.c_double), _p(C.c_uint32)]
+    lib.rgk_temporal_reproject_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, _p(Camera), _p(Camera)] + [C.c_void_p] * 8 + [
+        _p(TemporalParams), C.c_void_p, C.c_void_p]
+    lib.rgk_temporal_blend_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32] + [C.c_void_p] * 5 + [_p(TemporalParams)] + [C.c_void_p] * 3
+    lib.rgk_scene_get_post_timing.argtypes =[C.c_void_p, C.c_uint32, _p(C.c_double), _p(C.c_uint32)]
     lib.rgk_float_to_half.argtypes = [C.c_float]
     lib.rgk_float_to_half.restype = C.c_uint16
     return lib

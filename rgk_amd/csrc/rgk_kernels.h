@@ -141,3 +141,9 @@ void rgk_launch_nz_finish(hipStream_t st, size_t P, const float4* col, float* ou
 // the round fold: tiles / to_half on the device, n_tiles > 0 checked tiles (rgk_adapt.h rgk_fold_check_tiles gives max_tile_height)
 void rgk_launch_round_fold(hipStream_t st, uint32_t xres, const rgk_tile* tiles, const uint8_t* to_half, uint32_t n_tiles, uint32_t max_tile_height,
                            float* round_rgb, uint32_t* round_count, float* total_rgb, uint32_t* total_count, float* half_rgb, uint32_t* half_count);
+// temporal reuse: both cameras pinhole copies; n_triangles: a triangle id from there on gets no history (never an index)
+void rgk_launch_tp_reproject(hipStream_t st, const DevScene& sc, uint32_t n_triangles, const DevCamera& cam, const DevCamera& prev, uint32_t xres, uint32_t yres,
+                             const float* depth, const float* normal, const int32_t* tri, const float* depth_prev, const float* normal_prev, const int32_t* tri_prev,
+                             const float* hist_rgb_prev, const float* hist_len_prev, float plane_tol, float normal_cos, float* hist_rgb, float* hist_len);
+void rgk_launch_tp_blend(hipStream_t st, size_t P, const float* accum_rgb, const uint32_t* accum_count, const float* albedo, const float* hist_rgb, const float* hist_len,
+                         float alpha_min, float max_len, uint32_t demodulate, float albedo_floor, float* out_hist_rgb, float* out_hist_len, float* out_rgb);

@@ -12,6 +12,9 @@
 //   k_nz_finish              the plane's 4th float -> a plane of P floats
 //   k_nz_tile_sums           accumulator + half-buffer -> per tile {sum of v, sum of |c|^2, estimable pixels} (doubles), raw v plane
 //   k_round_fold             the listed tiles of a per-round accumulator -> += into the frame's, per tile into the half-buffer, and cleared
+//   k_tp_reproject           the previous frame's history {rgb, length} -> the current frame's pixels: four taps, each tested against the
+//                            previous frame's feature planes
+//   k_tp_blend               accumulator + reprojected history -> the next frame's history and the image to filter
 // (tests/noise_ref.py's k_nz_prepare, k_nz_prefilter and k_nz_atrous are k_dn_prepare<true> and k_dn_atrous<VarianceMean / VarianceGuided>)
 //
 // The traversal between raygen and gather is the round's own k_trace_closest (rgk_launch_trace_closest): no second walker.
@@ -407,4 +410,127 @@ void rgk_launch_round_fold(hipStream_t st, uint32_t xres, const rgk_tile* tiles,
                            float* round_rgb, uint32_t* round_count, float* total_rgb, uint32_t* total_count, float* half_rgb, uint32_t* half_count) {
     const RgkGrid2 g = rgk_fold_grid(n_tiles, max_tile_height);
     k_round_fold<<<dim3(g.x, g.y), RGK_POST_BLOCK, 0, st>>>(xres, tiles, to_half, round_rgb, round_count, total_rgb, total_count, half_rgb, half_count);
+}
+
+// ------------------------------------------------------------------ temporal reuse (rgk.h rgk_temporal_reproject_device / _blend_device)
+// One pixel of the current frame per lane; every formula in rgk.h's order, float32, nothing contracted (tests/temporal_ref.py gives
+// the same bits).  Streaming gathers: a lane reads 20 B of the current planes, the 4 B of its triangle's material index and that
+// material's kind, and per tap {length 4, triangle 4, depth 4, normal 12, colour 12 B} -- the feature planes only where the length
+// lets the tap in, the colour only where the features do -- and writes 16 B.  A wave's taps are two rows of up to 65 neighbouring
+// pixels of the previous frame wherever the motion is a shift, so the gathers are coalesced like the a-trous filter's at step 1.
+// (Both are templates for one reason: the compiler emits a template's code where it is first used, here after every other kernel
+// of this file, whose assembly -- the numbers in its labels included -- then stays what it was: tools/device_code_diff.sh compares text.)
+__device__ __forceinline__ f3 ld3(const float* __restrict__ a, size_t p) { return mk3(a[3 * p], a[3 * p + 1], a[3 * p + 2]); }
+
+template <int = 0>
+__global__ __launch_bounds__(RGK_POST_BLOCK) void k_tp_reproject(const DevScene sc, uint32_t n_triangles, const DevCamera cam, const DevCamera prev, int xres, int yres,
+                                                                  const float* __restrict__ depth, const float* __restrict__ normal, const int32_t* __restrict__ tri,
+                                                                  const float* __restrict__ depth_prev, const float* __restrict__ normal_prev,
+                                                                  const int32_t* __restrict__ tri_prev, const float* __restrict__ hist_rgb_prev,
+                                                                  const float* __restrict__ hist_len_prev, float plane_tol, float normal_cos,
+                                                                  float* __restrict__ hist_rgb, float* __restrict__ hist_len) {
+    const size_t p = (size_t)blockIdx.x * RGK_POST_BLOCK + threadIdx.x;
+    if (p >= (size_t)xres * (size_t)yres) return;
+    const int y = (int)(p / (size_t)xres), x = (int)(p - (size_t)y * (size_t)xres);
+    f3 o, d; // (lens_size == 0 in both cameras: the host passes pinhole copies)
+    camera_ray(cam, x, y, xres, yres, make_float2(0.5f, 0.5f), make_float2(0.f, 0.f), o, d);
+    const int t = tri[p];
+    const bool hit = t >= 0;
+    const f3 o_prev = mk3(prev.origin[0], prev.origin[1], prev.origin[2]);
+    const f3 xp = o + d * depth[p];
+    const f3 v = hit ? xp - o_prev : d;
+    const f3 np = ld3(normal, p);
+    bool ok = true;
+    if (hit) {
+        ok = (uint32_t)t < n_triangles && !is_zero3(np);
+        if (ok) { // the tables k_aov_gather reads: the triangle's shading record names its material
+            const uint32_t mat = gld_u32(sc.tri_shade, (uint32_t)t * (uint32_t)sizeof(TriShade) + 96u);
+            const uint32_t kind = gld_u32(sc.materials, mat * (uint32_t)sizeof(DevMaterial));
+            ok = !(kind == RGK_BXDF_MIRROR || kind == RGK_BXDF_DIELECTRIC || kind == RGK_BXDF_TRANSPARENT);
+        }
+    }
+    const f3 N = mk3(prev.direction[0], prev.direction[1], prev.direction[2]);
+    const float q = dot3(v, N);
+    float sr = 0.f, sg = 0.f, sb = 0.f, sl = 0.f, sw = 0.f;
+    if (ok && q > 0.0f) {
+        const f3 vs = mk3(prev.viewscreen[0], prev.viewscreen[1], prev.viewscreen[2]);
+        const f3 vx = mk3(prev.viewscreen_x[0], prev.viewscreen_x[1], prev.viewscreen_x[2]);
+        const f3 vy = mk3(prev.viewscreen_y[0], prev.viewscreen_y[1], prev.viewscreen_y[2]);
+        const float s = dot3(vs - o_prev, N) / q;
+        const f3 w = (o_prev + v * s) - vs;
+        const float a = dot3(w, vx) / dot3(vx, vx), b = dot3(w, vy) / dot3(vy, vy);
+        const float fx = a * (float)xres - 0.5f, fy = b * (float)yres - 0.5f;
+        if (fx > -1.0f && fx < (float)xres && fy > -1.0f && fy < (float)yres) { // (false for NaN)
+            const float flx = floorf(fx), fly = floorf(fy);
+            const int ix = (int)flx, iy = (int)fly;
+            const float tx = fx - flx, ty = fy - fly;
+            const float wt[4] = {(1.0f - tx) * (1.0f - ty), tx * (1.0f - ty), (1.0f - tx) * ty, tx * ty};
+            const float tol = plane_tol * len3(v);
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const int qx = ix + (k & 1), qy = iy + (k >> 1);
+                if (qx < 0 || qx >= xres || qy < 0 || qy >= yres) continue;
+                const size_t qi = (size_t)qy * (size_t)xres + (size_t)qx;
+                const float lq = hist_len_prev[qi];
+                if (!(lq > 0.0f)) continue;
+                const bool hq = tri_prev[qi] >= 0;
+                if (hq != hit) continue;
+                if (hit) {
+                    const f3 nq = ld3(normal_prev, qi);
+                    if (!(dot3(np, nq) >= normal_cos)) continue;
+                    f3 oq, dq;
+                    camera_ray(prev, qx, qy, xres, yres, make_float2(0.5f, 0.5f), make_float2(0.f, 0.f), oq, dq);
+                    if (!(fabsf(dot3(xp - (o_prev + dq * depth_prev[qi]), nq)) <= tol)) continue;
+                }
+                const f3 c = ld3(hist_rgb_prev, qi);
+                sr = sr + wt[k] * c.x; sg = sg + wt[k] * c.y; sb = sb + wt[k] * c.z;
+                sl = sl + wt[k] * lq;
+                sw = sw + wt[k];
+            }
+        }
+    }
+    const bool have = sw > 0.0f; // (sum(w) == 0, and everything that never reached the taps: no history)
+    hist_rgb[3 * p] = have ? sr / sw : 0.0f; hist_rgb[3 * p + 1] = have ? sg / sw : 0.0f; hist_rgb[3 * p + 2] = have ? sb / sw : 0.0f;
+    hist_len[p] = have ? sl / sw : 0.0f;
+}
+
+template <int = 0>
+__global__ __launch_bounds__(RGK_POST_BLOCK) void k_tp_blend(size_t P, const float* __restrict__ accum_rgb, const uint32_t* __restrict__ accum_count,
+                                                              const float* __restrict__ albedo, const float* __restrict__ hist_rgb, const float* __restrict__ hist_len,
+                                                              float alpha_min, float max_len, uint32_t demodulate, float albedo_floor,
+                                                              float* __restrict__ out_hist_rgb, float* __restrict__ out_hist_len, float* __restrict__ out_rgb) {
+    const size_t p = (size_t)blockIdx.x * RGK_POST_BLOCK + threadIdx.x;
+    if (p >= P) return;
+    const uint32_t n = accum_count[p];
+    const f3 h = ld3(hist_rgb, p);
+    const float L = hist_len[p];
+    f3 div = mk3(1.f, 1.f, 1.f);
+    if (demodulate) div = mk3(demod_div(albedo[3 * p], albedo_floor), demod_div(albedo[3 * p + 1], albedo_floor), demod_div(albedo[3 * p + 2], albedo_floor));
+    f3 m = h;
+    float Ln = L;
+    if (n) {
+        const f3 c = ld3(accum_rgb, p) / (float)n;
+        m = mk3(c.x / div.x, c.y / div.y, c.z / div.z);
+        Ln = 1.0f;
+        if (L > 0.0f) {
+            const float alpha = fmaxf(1.0f / (L + 1.0f), alpha_min);
+            m = (m - h) * alpha + h;
+            Ln = fminf(L + 1.0f, max_len);
+        }
+    }
+    out_hist_rgb[3 * p] = m.x; out_hist_rgb[3 * p + 1] = m.y; out_hist_rgb[3 * p + 2] = m.z;
+    out_hist_len[p] = Ln;
+    out_rgb[3 * p] = m.x * div.x; out_rgb[3 * p + 1] = m.y * div.y; out_rgb[3 * p + 2] = m.z * div.z;
+}
+
+void rgk_launch_tp_reproject(hipStream_t st, const DevScene& sc, uint32_t n_triangles, const DevCamera& cam, const DevCamera& prev, uint32_t xres, uint32_t yres,
+                             const float* depth, const float* normal, const int32_t* tri, const float* depth_prev, const float* normal_prev, const int32_t* tri_prev,
+                             const float* hist_rgb_prev, const float* hist_len_prev, float plane_tol, float normal_cos, float* hist_rgb, float* hist_len) {
+    k_tp_reproject<0><<<rgk_post_pixel_grid((size_t)xres * yres), RGK_POST_BLOCK, 0, st>>>(sc, n_triangles, cam, prev, (int)xres, (int)yres, depth, normal, tri, depth_prev, normal_prev,
+                                                                                       tri_prev, hist_rgb_prev, hist_len_prev, plane_tol, normal_cos, hist_rgb, hist_len);
+}
+void rgk_launch_tp_blend(hipStream_t st, size_t P, const float* accum_rgb, const uint32_t* accum_count, const float* albedo, const float* hist_rgb, const float* hist_len,
+                         float alpha_min, float max_len, uint32_t demodulate, float albedo_floor, float* out_hist_rgb, float* out_hist_len, float* out_rgb) {
+    k_tp_blend<0><<<rgk_post_pixel_grid(P), RGK_POST_BLOCK, 0, st>>>(P, accum_rgb, accum_count, albedo, hist_rgb, hist_len, alpha_min, max_len, demodulate, albedo_floor,
+                                                                 out_hist_rgb, out_hist_len, out_rgb);
 }

@@ -1,4 +1,4 @@
-// The post-processing entries: feature buffers, both denoisers, the noise estimate, tile selection and the round fold
+// The post-processing entries: feature buffers, both denoisers, the noise estimate, tile selection, the round fold and temporal reuse
 // (kernels: rgk_post.hip).
 #include <algorithm>
 #include <cmath>
@@ -98,6 +98,47 @@ int denoise(rgk_scene* s, const char* entry, PostSlot slot, uint32_t xres, uint3
         rgk_launch_nz_finish(st, P, s->dn_col[cur].p, out_variance);
         return tm.mark();
     });
+}
+
+// ---- temporal reuse
+// (both entries check every member, whichever of them they read: a parameter set is good or bad, not good for one call)
+int check_temporal_params(const rgk_temporal_params* p) {
+    if (!p) return fail(RGK_ERR_INVALID, "null argument");
+    const float all[5] = {p->plane_tol, p->normal_cos, p->alpha_min, p->max_len, p->albedo_floor};
+    for (float v : all)
+        if (!std::isfinite(v)) return fail(RGK_ERR_INVALID, "temporal parameters must be finite");
+    if (!(p->plane_tol >= 0.0f)) return fail(RGK_ERR_INVALID, "plane_tol must be >= 0");
+    if (!(p->normal_cos >= -1.0f && p->normal_cos <= 1.0f)) return fail(RGK_ERR_INVALID, "normal_cos must be in [-1, 1]");
+    if (!(p->alpha_min > 0.0f && p->alpha_min <= 1.0f)) return fail(RGK_ERR_INVALID, "alpha_min must be in (0, 1]");
+    if (!(p->max_len >= 1.0f)) return fail(RGK_ERR_INVALID, "max_len must be >= 1");
+    if (!(p->albedo_floor >= 0.0f)) return fail(RGK_ERR_INVALID, "albedo_floor must be >= 0");
+    return RGK_OK;
+}
+// no output is an input or another output (`ins` may hold NULLs)
+int check_outputs_apart(const void* const* ins, size_t n_in, const void* const* outs, size_t n_out) {
+    for (size_t o = 0; o < n_out; o++) {
+        for (size_t i = 0; i < n_in; i++)
+            if (ins[i] && ins[i] == outs[o]) return fail(RGK_ERR_INVALID, "an output plane must not be one of the inputs");
+        for (size_t k = o + 1; k < n_out; k++)
+            if (outs[k] == outs[o]) return fail(RGK_ERR_INVALID, "the output planes must be different buffers");
+    }
+    return RGK_OK;
+}
+// One launch between two marks.  The temporal slot holds {reproject, blend}: `half`'s entry is replaced, the other one kept.
+template <class Launch>
+int temporal_call(rgk_scene* s, const char* entry, int half, Launch&& launch) {
+    std::vector<double> pair = s->post_ms[POST_TEMPORAL];
+    const int rc = post_call(s, entry, POST_TEMPORAL, true, [&](PostTimer& tm) -> int {
+        if (int rc = tm.mark()) return rc;
+        launch(s->stream);
+        return tm.mark();
+    });
+    std::vector<double>& v = s->post_ms[POST_TEMPORAL];
+    if (rc || v.empty()) return rc; // ("time_post" is off: nothing recorded)
+    pair.resize(2, 0.0);
+    pair[half] = v[0];
+    v = pair;
+    return RGK_OK;
 }
 } // namespace
 
@@ -226,6 +267,48 @@ int rgk_round_fold_device(rgk_scene* s, uint32_t xres, uint32_t yres, const rgk_
         rgk_launch_round_fold(st, xres, reinterpret_cast<const rgk_tile*>(s->fold_buf.p), d_flags, n_tiles, max_height, d_round_rgb, d_round_count, d_total_rgb,
                               d_total_count, d_half_rgb, d_half_count);
         return tm.mark();
+    });
+}
+
+int rgk_temporal_reproject_device(rgk_scene* s, uint32_t xres, uint32_t yres, const rgk_camera* cam_cur, const rgk_camera* cam_prev, const float* d_depth_cur,
+                                  const float* d_normal_cur, const int32_t* d_tri_cur, const float* d_depth_prev, const float* d_normal_prev,
+                                  const int32_t* d_tri_prev, const float* d_hist_rgb_prev, const float* d_hist_len_prev, const rgk_temporal_params* tp,
+                                  float* d_hist_rgb, float* d_hist_len) {
+    // (every check before the scene or the device is touched)
+    const void* ins[8] = {d_depth_cur, d_normal_cur, d_tri_cur, d_depth_prev, d_normal_prev, d_tri_prev, d_hist_rgb_prev, d_hist_len_prev};
+    const void* outs[2] = {d_hist_rgb, d_hist_len};
+    if (!s || !cam_cur || !cam_prev || !d_hist_rgb || !d_hist_len) return fail(RGK_ERR_INVALID, "null argument");
+    for (const void* in : ins)
+        if (!in) return fail(RGK_ERR_INVALID, "null argument");
+    int rc;
+    if ((rc = check_temporal_params(tp)) || (rc = check_frame_size(xres, yres)) || (rc = check_outputs_apart(ins, 8, outs, 2))) return rc;
+    DevCamera cur, prev;
+    make_camera(cam_cur, cur);
+    make_camera(cam_prev, prev);
+    cur.lens_size = prev.lens_size = 0.0f; // the feature planes' rays: from the cameras' origins
+    const rgk_temporal_params p = *tp;
+    return temporal_call(s, "rgk_temporal_reproject_device", 0, [&](hipStream_t st) {
+        rgk_launch_tp_reproject(st, s->dev, s->n_triangles, cur, prev, xres, yres, d_depth_cur, d_normal_cur, d_tri_cur, d_depth_prev, d_normal_prev, d_tri_prev,
+                                d_hist_rgb_prev, d_hist_len_prev, p.plane_tol, p.normal_cos, d_hist_rgb, d_hist_len);
+    });
+}
+
+int rgk_temporal_blend_device(rgk_scene* s, uint32_t xres, uint32_t yres, const float* d_accum_rgb, const uint32_t* d_accum_count, const float* d_albedo,
+                              const float* d_hist_rgb, const float* d_hist_len, const rgk_temporal_params* tp, float* d_out_hist_rgb, float* d_out_hist_len,
+                              float* d_out_rgb) {
+    // (every check before the scene or the device is touched)
+    if (!s || !d_accum_rgb || !d_accum_count || !d_hist_rgb || !d_hist_len || !d_out_hist_rgb || !d_out_hist_len || !d_out_rgb)
+        return fail(RGK_ERR_INVALID, "null argument");
+    int rc;
+    if ((rc = check_temporal_params(tp))) return rc;
+    if (tp->demodulate && !d_albedo) return fail(RGK_ERR_INVALID, "demodulate without an albedo plane");
+    const void* ins[5] = {d_accum_rgb, d_accum_count, d_albedo, d_hist_rgb, d_hist_len};
+    const void* outs[3] = {d_out_hist_rgb, d_out_hist_len, d_out_rgb};
+    if ((rc = check_frame_size(xres, yres)) || (rc = check_outputs_apart(ins, 5, outs, 3))) return rc;
+    const rgk_temporal_params p = *tp;
+    return temporal_call(s, "rgk_temporal_blend_device", 1, [&](hipStream_t st) {
+        rgk_launch_tp_blend(st, (size_t)xres * yres, d_accum_rgb, d_accum_count, d_albedo, d_hist_rgb, d_hist_len, p.alpha_min, p.max_len, p.demodulate ? 1u : 0u,
+                            p.albedo_floor, d_out_hist_rgb, d_out_hist_len, d_out_rgb);
     });
 }
 

@@ -176,9 +176,27 @@ class Scene:
         capi.check(self.lib, self.lib.rgk_round_fold_device(self.h, xres, yres, tiles, len(tiles), flags.ctypes.data, d_round_rgb, d_round_count,
                                                             d_total_rgb, d_total_count, d_half_rgb, d_half_count))
 
+    def temporal_reproject_device(self, xres, yres, cam_cur, cam_prev, d_depth_cur, d_normal_cur, d_tri_cur, d_depth_prev, d_normal_prev, d_tri_prev,
+                                  d_hist_rgb_prev, d_hist_len_prev, params, d_hist_rgb, d_hist_len):
+        """rgk_temporal_reproject_device: the previous frame's history carried to the current frame's pixels; DEVICE pointers (ints)
+        on the scene's GPU, params a capi.TemporalParams (its ranges are checked here first: ValueError)."""
+        params.check()
+        capi.check(self.lib, self.lib.rgk_temporal_reproject_device(self.h, xres, yres, C.byref(cam_cur), C.byref(cam_prev), d_depth_cur, d_normal_cur,
+                                                                    d_tri_cur, d_depth_prev, d_normal_prev, d_tri_prev, d_hist_rgb_prev, d_hist_len_prev,
+                                                                    C.byref(params), d_hist_rgb, d_hist_len))
+
+    def temporal_blend_device(self, xres, yres, d_accum_rgb, d_accum_count, d_albedo, d_hist_rgb, d_hist_len, params, d_out_hist_rgb, d_out_hist_len,
+                              d_out_rgb):
+        """rgk_temporal_blend_device: the accumulator's image blended into the reprojected history -> the next frame's history
+        (demodulated) and the image to filter; DEVICE pointers (ints), d_albedo may be None without demodulation."""
+        params.check()
+        capi.check(self.lib, self.lib.rgk_temporal_blend_device(self.h, xres, yres, d_accum_rgb, d_accum_count, d_albedo, d_hist_rgb, d_hist_len,
+                                                                C.byref(params), d_out_hist_rgb, d_out_hist_len, d_out_rgb))
+
     def post_timing(self, which):
         """HIP-event times (ms) of the launches of the last feature pass (0) / denoise call (1) / variance-guided denoise call (2) /
-        noise estimate (3) / round fold (4: the copy of its tile list, the fold); set_tuning(time_post=1) first."""
+        noise estimate (3) / round fold (4: the copy of its tile list, the fold) / temporal pair (5: reproject, blend);
+        set_tuning(time_post=1) first."""
         ms, n = (C.c_double * 32)(), C.c_uint32(32)
         capi.check(self.lib, self.lib.rgk_scene_get_post_timing(self.h, which, ms, C.byref(n)))
         return list(ms[:min(n.value, 32)])
@@ -327,12 +345,45 @@ def missing_half_message(path):
             "cannot be continued from it (render without --noise, or start the frame again)")
 
 
+class TemporalHistory:
+    """What one frame of a camera animation hands to the next (static geometry, moving camera): the frame's camera, its depth /
+    normal / tri feature planes, and the history image -- demodulated colour (y, x, 3) and length (y, x), float32 tensors on the
+    device -- with the capi.TemporalParams both kernels run with.  One object serves a sequence of RenderDrivers, one per frame;
+    each commits once (RenderDriver.denoise_temporal).  Lives on the device only: not checkpointed."""
+
+    def __init__(self, params=None):
+        self.params = (params or capi.TemporalParams()).check()
+        self.reset()
+
+    def reset(self):
+        """Forget the chain: the next frame starts with every length 0."""
+        self.camera = self.depth = self.normal = self.tri = self.rgb = self.length = None
+        self.share = None  # of the last frame's pixels, those that found history (None: that frame started the chain)
+
+    @property
+    def empty(self):
+        return self.camera is None
+
+    def commit(self, camera, aov, rgb, length):
+        self.camera = capi.Camera.from_buffer_copy(camera)
+        self.depth, self.normal, self.tri = aov["depth"], aov["normal"], aov["tri"]
+        self.rgb, self.length = rgb, length
+
+
 class RenderDriver:
     """RenderDriver::RenderFrame / RenderRound for one process per GPU."""
 
     def __init__(self, scene, cfg, camera, rank=0, world_size=1, device=None, sampler=capi.SAMPLER_HALTON, flags=0,
-                 host_reduce=False, track_noise=False, adaptive=None):
+                 host_reduce=False, track_noise=False, adaptive=None, history=None):
         import torch
+        # history (a TemporalHistory shared by the drivers of an animation's frames): denoise_temporal() reprojects the previous
+        # frame's history into this frame, blends this frame's samples in and commits the result for the next frame.  Nothing else
+        # reads it: rounds, accumulator and denoise() are the same with and without one.
+        if history is not None and track_noise:
+            raise ValueError("temporal reuse cannot be combined with track_noise: the variance-guided filter needs the two halves of "
+                             "one frame and stays a per-frame tool")
+        self.history = history
+        self._reprojected = None  # the history as this frame received it: (rgb, length), made by the first denoise_temporal()
         self.scene, self.cfg, self.camera = scene, cfg, camera
         self.rank, self.world_size = rank, world_size
         self.device = device if device is not None else torch.device("cuda", scene.device)
@@ -516,6 +567,50 @@ class RenderDriver:
                                   a["albedo"].data_ptr(), a["normal"].data_ptr(), a["depth"].data_ptr(), params, out.data_ptr())
         return out
 
+    def denoise_temporal(self, params=None):
+        """The current accumulator's image blended into the history the previous frame left (rgk_temporal_reproject_device,
+        rgk_temporal_blend_device, parameters: the history's), through the guided a-trous filter with sample counts of 1
+        (rgk_denoise_device; params: a capi.DenoiseParams, default the shipped ones with sigma_color from the blended image), and
+        the blend committed as the next frame's history: a (y, x, 3) float32 tensor on the device.  The accumulator is not changed.
+        On the first frame of a chain every history length is 0 and the blend is the frame itself.  The history is reprojected
+        once per driver: a second call -- after more rounds, say -- blends the accumulator into what this frame RECEIVED, never
+        into its own earlier blend, and commits again in place of the first.  Root rank only."""
+        import torch
+        if self.rank != 0:
+            return None
+        if self.history is None:
+            raise ValueError("denoise_temporal needs a driver made with history=TemporalHistory()")
+        hist, tp = self.history, self.history.params
+        a = self.render_aov()
+        y, x = self.cfg.yres, self.cfg.xres
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.device)
+        if self._reprojected is None:
+            rgb, length = torch.zeros((y, x, 3), dtype=torch.float32, device=self.device), torch.zeros((y, x), dtype=torch.float32, device=self.device)
+            share = None
+            if not hist.empty and tuple(hist.length.shape) == (y, x) and hist.length.device == rgb.device:
+                torch.cuda.current_stream(self.device).synchronize()
+                self.scene.temporal_reproject_device(x, y, self.camera, hist.camera, a["depth"].data_ptr(), a["normal"].data_ptr(), a["tri"].data_ptr(),
+                                                     hist.depth.data_ptr(), hist.normal.data_ptr(), hist.tri.data_ptr(), hist.rgb.data_ptr(),
+                                                     hist.length.data_ptr(), tp, rgb.data_ptr(), length.data_ptr())
+                share = float((length > 0).double().mean())
+            self._reprojected = (rgb, length, share)
+        rgb, length, share = self._reprojected
+        out_hist, out_len, out = new(y, x, 3), new(y, x), new(y, x, 3)
+        torch.cuda.current_stream(self.device).synchronize()
+        self.scene.temporal_blend_device(x, y, self.total_ob.data.data_ptr(), self.total_ob.count.data_ptr(), a["albedo"].data_ptr(), rgb.data_ptr(),
+                                         length.data_ptr(), tp, out_hist.data_ptr(), out_len.data_ptr(), out.data_ptr())
+        if params is None:
+            level = float(out.max(dim=-1).values.double().mean())
+            params = capi.DenoiseParams(sigma_color=DENOISE_SIGMA_K * level if level > 0 else 1.0)
+        ones = torch.ones((y, x), dtype=torch.int32, device=self.device)
+        filtered = torch.empty_like(out)
+        torch.cuda.current_stream(self.device).synchronize()
+        self.scene.denoise_device(x, y, out.data_ptr(), ones.data_ptr(), a["albedo"].data_ptr(), a["normal"].data_ptr(), a["depth"].data_ptr(), params,
+                                  filtered.data_ptr())
+        hist.commit(self.camera, a, out_hist, out_len)
+        hist.share = share
+        return filtered
+
     def save_checkpoint(self, path):
         """Raw-accumulator checkpoint (rgk_accum_save): accumulator + rounds done + the running task counter.  With track_noise the
         half-buffer goes beside it as `<path>.half`, same format, same tag."""
@@ -574,7 +669,7 @@ class RenderDriver:
         return yes
 
     def render_frame(self, rounds=None, minutes=None, output_file=None, checkpoint=None, aov_files=None, denoised_file=None,
-                     until_noise=None, noise_file=None, on_noise=None):
+                     until_noise=None, noise_file=None, on_noise=None, temporal=False):
         """RenderFrame: Rounds mode (render_driver.cpp:229-235) or Timed mode (:237-247); with `output_file` the
         normalised image is rewritten after every round, as the reference does (rank 0 only).
         aov_files: {"albedo" / "normal" / "depth": path} -- the feature planes, written once (depth replicated to R, G, B).
@@ -585,7 +680,12 @@ class RenderDriver:
         on_noise(rounds_done, rel) is called on rank 0 after every round that has an estimate.
         With an adaptive driver and until_noise: after every round from the second on rgk_adapt_select (target = until_noise) says
         whether the frame is done and which tiles the next round renders; on_noise(rounds_done, rel, n_live) also gets their number.
-        The rule keeps no state, so a frame resumed from a checkpoint goes on with the tiles the interrupted one would have rendered."""
+        The rule keeps no state, so a frame resumed from a checkpoint goes on with the tiles the interrupted one would have rendered.
+        temporal (needs a driver with a history, and denoised_file): after the frame's LAST round denoised_file is rewritten once more,
+        from denoise_temporal(), which also commits the history for the next frame; the rewrites after earlier rounds are the
+        single-frame filter's as without it."""
+        if temporal and (self.history is None or not denoised_file):
+            raise ValueError("temporal=True needs a driver made with history=TemporalHistory() and a denoised_file")
         if (until_noise is not None or noise_file or on_noise) and not self.track_noise:
             raise ValueError("until_noise, noise_file and on_noise need track_noise=True")
         rounds = self.cfg.render_rounds if rounds is None else rounds
@@ -593,6 +693,7 @@ class RenderDriver:
         t0 = self.clock()
         adapting = self.adaptive is not None and until_noise is not None
         live = None  # the next round's tiles (None: all)
+        val = None   # the scale the last rewrite of output_file used
         if aov_files and self.rank == 0:
             a = self.render_aov()
             for name, path in aov_files.items():
@@ -631,4 +732,6 @@ class RenderDriver:
                 done = until_noise is not None and self._root_decides(nz is not None and nz["rel"] <= until_noise)
             if done:
                 break
+        if temporal and val is not None and self.rank == 0:
+            write_exr(denoised_file, (self.denoise_temporal() * val).cpu().numpy())
         return self.total_ob
