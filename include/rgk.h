@@ -425,6 +425,44 @@ int rgk_render_aov_device(rgk_scene *scene, const rgk_camera *camera, const rgk_
 int rgk_render_aov(rgk_scene *scene, const rgk_camera *camera, const rgk_params *params, const rgk_tile *tiles, uint32_t n_tiles,
                    float *albedo, float *normal, float *depth, int32_t *tri);
 
+/* ---- feature planes that follow mirrors and glass to the first non-specular surface ----
+ *
+ * The planes of rgk_render_aov_device, but a pixel whose centre ray meets a mirror, a dielectric or a transparent surface follows
+ * the chain of delta interactions the integrator's path takes and reports the first surface behind it.  Per pixel, float32,
+ * contraction off, in this order.  Let U = (0x1.fffffep-1f, 0), T_0 = (1, 1, 1) and L_0 = 0.  ray_0 is the centre ray of
+ * rgk_render_aov_device (pinhole copy of the camera, near 0, far 10000, no ignored triangle).  For hop k = 0, 1, ...:
+ *   1. Trace ray_k with the round's own closest-hit walker.
+ *        Miss: tri = -1, depth = 0, normal = albedo = 0, hops = k.  End.
+ *   2. v = the integrator's vertex at the hit (position, face normal, uv, bump-tilted shading normal, local frame g2l) and
+ *      L_{k+1} = L_k + t_k.
+ *        A vertex the integrator drops (NaN / zero face normal): tri = tri_k, depth = L_{k+1}, normal = albedo = 0, hops = k.  End.
+ *   3. TERMINAL means: tri = tri_k, depth = L_{k+1}, normal = v.lightN (world space), albedo = T_k * albedo(v.mat, v.uv) -- the
+ *      albedo of rgk_render_aov_device, one multiply per channel -- hops = k.  End.
+ *        The vertex is terminal when its TOP-LEVEL material kind is not mirror, dielectric or transparent (a mix ends the chain and
+ *        reports its mixed albedo), and when k == max_hops.
+ *   4. Otherwise (dirL, weight, may_leak) = the integrator's own BxDF sample of that kind at u = U, in the local frame:
+ *        mirror: the reflection; transparent: straight through; dielectric: the refraction unless decide_and_rescale(U.x, R) picks
+ *        the reflection (in effect: total internal reflection).
+ *      dir = qrot(qinverse(v.g2l), dirL).  The integrator's leak rule: if !(dot(dir, faceN) * dot(Vr, faceN) > 0) && !may_leak its
+ *      path would end here, and the vertex is terminal.
+ *   5. T_{k+1} = T_k * weight.  ray_{k+1} is the ray the integrator continues with: origin v.pos + v.faceN * epsilon * 10 *
+ *      (dirL.z < 0 ? -1 : 1), direction norm3(norm3(dir)), ignored triangle tri_k, near 0, far 10000.
+ *      A continuation ray with a non-finite component is queued and traced like every other, as in a round: the walker records no
+ *      hit for a ray with a NaN component, so the pixel ends at step 1 of hop k + 1 as a miss.
+ * No roulette, no clamp, no throughput cut-off: only geometric ends.  max_hops == 0 gives the planes of rgk_render_aov_device
+ * bit for bit and hops = 0 everywhere.  Queue order may vary from run to run, the planes do not.
+ * Conventions of rgk_render_aov_device: any output may be NULL; pixels outside the tiles are not written; DEVICE buffers on the
+ * scene's GPU; blocking; not while a round is in flight on this scene; a call between two rounds of a frame changes nothing those
+ * rounds compute.  Arguments are checked before the scene or the device is touched; max_hops > RGK_AOV_MAX_HOPS is RGK_ERR_INVALID. */
+#define RGK_AOV_MAX_HOPS 8
+int rgk_render_aov_chain_device(rgk_scene *scene, const rgk_camera *camera, const rgk_params *params, const rgk_tile *tiles,
+                                uint32_t n_tiles, uint32_t max_hops, float *d_albedo /*3P*/, float *d_normal /*3P*/,
+                                float *d_depth /*P*/, int32_t *d_tri /*P*/, uint8_t *d_hops /*P*/);
+/* Same with HOST buffers (their contents are kept outside the tiles). */
+int rgk_render_aov_chain(rgk_scene *scene, const rgk_camera *camera, const rgk_params *params, const rgk_tile *tiles,
+                         uint32_t n_tiles, uint32_t max_hops, float *albedo, float *normal, float *depth, int32_t *tri,
+                         uint8_t *hops);
+
 /* Edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) of the accumulator's image, guided by the feature planes.
  * c = accum_rgb / accum_count (0 where the count is 0); with `demodulate`, c is divided per channel by (albedo > 0 ? albedo : 1)
  * before the filter and multiplied back after it.  Iteration i = 0 .. iterations - 1, step s = 2^i: 5 x 5 taps q = p + s * (dx, dy)
@@ -456,7 +494,8 @@ int rgk_denoise_device(rgk_scene *scene, uint32_t xres, uint32_t yres, const flo
  * list and the fold) on this scene, in ms; recorded only while
  * the tuning key "time_post" is 1. *n: in, room in ms; out, entries the call had (those that fit are written).
  * which = 5: the temporal pair -- {the last rgk_temporal_reproject_device, the last rgk_temporal_blend_device}, one launch each;
- * two entries once either has run with "time_post" on, 0 ms for the one that has not. */
+ * two entries once either has run with "time_post" on, 0 ms for the one that has not.
+ * which = 6: the last rgk_render_aov_chain[_device] -- pixel list + ray generation, then {walker, k_aov_hop} per hop 0 .. max_hops. */
 int rgk_scene_get_post_timing(const rgk_scene *scene, uint32_t which, double *ms, uint32_t *n);
 
 /* ---- noise estimate from two half-buffers and the variance-guided filter (DESIGN.md "Half-buffer noise estimate") ----

@@ -32,6 +32,11 @@
                     the two cameras, tested against depth, normal and triangle planes -- and then filtered; the blend becomes the
                     next frame's history.  A frame skipped by --no-overwrite or resumed from a checkpoint starts the chain again
                     (the history is not checkpointed).  Not with --noise, --until-noise or --adaptive.  Every other file is unchanged
+  --aov-hops K      needs --aov or --denoise; K = 0 .. 8 (default 0: off).  The feature planes follow up to K mirror, glass and
+                    transparent surfaces along the path the integrator takes and describe the first other surface seen through
+                    them (depth: the length of the whole chain; albedo: times the surfaces' colours): --aov writes those planes
+                    and, beside them, the suffix `hops` (the surfaces passed, in R, G and B), --denoise filters with them.  Not
+                    with --temporal.  The plain output is unchanged
 FILE is a .json or .rtc scene config.  One process drives one GPU; several GPUs: python -m torch.distributed.run ... bench.py.
 """
 import argparse
@@ -96,6 +101,7 @@ def main(argv=None):
     ap.add_argument("--adaptive", type=int, nargs="?", const=4, default=None, metavar="MIN_VISITS")
     ap.add_argument("--temporal", action="store_true")
     ap.add_argument("--frames", type=int, default=None, help="with -r: stop after this many frames (default: all 501)")
+    ap.add_argument("--aov-hops", type=int, default=None, metavar="K")
     args = ap.parse_args(argv)
     verbosity = max(0, 2 + args.v - args.q)
     say = lambda lvl, *a: print(*a) if verbosity >= lvl else None
@@ -105,6 +111,17 @@ def main(argv=None):
     if args.temporal and (not args.denoise or args.noise or args.until_noise is not None or args.adaptive is not None):
         print("ERROR: --temporal needs --denoise." if not args.denoise else "ERROR: --temporal cannot be combined with --noise, --until-noise or --adaptive.")
         return 1
+    if args.aov_hops is not None:
+        if not 0 <= args.aov_hops <= capi.AOV_MAX_HOPS:
+            print(f"ERROR: Invalid argument for --aov-hops (0 to {capi.AOV_MAX_HOPS}).")
+            return 1
+        if not (args.aov or args.denoise):
+            print("ERROR: --aov-hops needs --aov or --denoise.")
+            return 1
+        if args.temporal:
+            print("ERROR: --aov-hops cannot be combined with --temporal.")
+            return 1
+    aov_hops = args.aov_hops or 0
     try:
         cfg = load_config(args.file)
     except ConfigFileException as e:
@@ -162,7 +179,8 @@ def main(argv=None):
         camera = cfg.get_camera(t / time_length if args.rotate else 0.0)
         try:
             drv = rd.RenderDriver(scene, cfg, camera, device=device, track_noise=track_noise,
-                                  adaptive=capi.AdaptParams(args.until_noise, args.adaptive) if args.adaptive is not None else None, history=history)
+                                  adaptive=capi.AdaptParams(args.until_noise, args.adaptive) if args.adaptive is not None else None, history=history,
+                                  aov_hops=aov_hops)
         except ValueError as e:
             print(f"ERROR: {e}")
             return 1
@@ -199,7 +217,7 @@ def main(argv=None):
         timed = cfg.render_minutes is not None
         with FrameMonitor(scene, timed, cfg.render_rounds, cfg.render_minutes or 0, cfg.xres * cfg.yres, verbosity=verbosity) as mon:
             drv.render_frame(rounds=max(0, cfg.render_rounds - drv.rounds_done) if not timed else None, output_file=out, checkpoint=ckpt,
-                             aov_files={k: insert_file_suffix(out, k) for k in ("albedo", "normal", "depth")} if args.aov else None,
+                             aov_files={k: insert_file_suffix(out, k) for k in ("albedo", "normal", "depth") + (("hops",) if aov_hops > 0 else ())} if args.aov else None,
                              denoised_file=insert_file_suffix(out, "denoised") if args.denoise else None, temporal=args.temporal,
                              **(dict(until_noise=args.until_noise, noise_file=insert_file_suffix(out, "noise"),
                                      on_noise=lambda r, rel, n_live=None: say(1, f"Round {r}: " + (f"{n_live} live tiles, " if n_live is not None else "") +

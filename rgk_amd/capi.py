@@ -197,7 +197,9 @@ EXPORTS = ["rgk_last_error", "rgk_device_count", "rgk_scene_create", "rgk_scene_
            "rgk_shard_tiles", "rgk_comm_get_unique_id", "rgk_comm_create", "rgk_comm_destroy", "rgk_accum_reduce",
            "rgk_render_aov_device", "rgk_render_aov", "rgk_denoise_device", "rgk_scene_get_post_timing",
            "rgk_noise_estimate_device", "rgk_denoise_variance_device", "rgk_adapt_select", "rgk_round_fold_device",
-           "rgk_temporal_reproject_device", "rgk_temporal_blend_device"]
+           "rgk_temporal_reproject_device", "rgk_temporal_blend_device",
+           "rgk_render_aov_chain_device", "rgk_render_aov_chain"]
+AOV_MAX_HOPS = 8  # RGK_AOV_MAX_HOPS
 
 _p = C.POINTER
 
@@ -253,6 +255,9 @@ def _bind(lib):
     lib.rgk_render_aov_device.argtypes = [C.c_void_p, _p(Camera), _p(Params), _p(Tile), C.c_uint32,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.rgk_render_aov.argtypes = lib.rgk_render_aov_device.argtypes
+    lib.rgk_render_aov_chain_device.argtypes = [C.c_void_p, _p(Camera), _p(Params), _p(Tile), C.c_uint32, C.c_uint32,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rgk_render_aov_chain.argtypes = lib.rgk_render_aov_chain_device.argtypes
     lib.rgk_denoise_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        _p(DenoiseParams), C.c_void_p]
     lib.rgk_noise_estimate_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

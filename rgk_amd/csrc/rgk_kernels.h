@@ -126,6 +126,11 @@ void rgk_launch_libm_eval(hipStream_t st, int fn, uint32_t n, const float* a, co
 void rgk_launch_aov_raygen(hipStream_t st, const DevCamera& cam, uint32_t xres, uint32_t yres, const uint32_t* pix_xy, uint32_t n, float4* rayA, float4* rayB);
 void rgk_launch_aov_gather(hipStream_t st, const DevScene& sc, float bumpmap_scale, uint32_t xres, const uint32_t* pix_xy, uint32_t n, const float4* rayA,
                            const float4* rayB, const float4* hit, float* albedo, float* normal, float* depth, int32_t* tri);
+// one hop of rgk_render_aov_chain_device: hop `hop`'s queue (rayA / rayB / hit, counters[RGK_CNT_QUEUE + hop] entries, at most n) ->
+// the planes, or hop + 1's queue (nextA / nextB, counters[RGK_CNT_QUEUE + hop + 1]); state: per slot {T.rgb, L}; n: the call's pixels
+void rgk_launch_aov_hop(hipStream_t st, const DevScene& sc, float bumpmap_scale, uint32_t xres, const uint32_t* pix_xy, uint32_t n, uint32_t hop, uint32_t max_hops,
+                        const float4* rayA, const float4* rayB, const float4* hit, float4* state, float4* nextA, float4* nextB, uint32_t* counters, float* albedo,
+                        float* normal, float* depth, int32_t* tri, uint8_t* hops);
 // ... both denoisers (grids: rgk_plan.h rgk_post_*).  half_rgb == NULL: no half-buffer, the plane's variance is 0.
 void rgk_launch_dn_prepare(hipStream_t st, size_t P, const float* accum_rgb, const uint32_t* accum_count, const float* half_rgb, const uint32_t* half_count,
                            const float* albedo, const float* normal, const float* depth, uint32_t demodulate, float albedo_floor, float4* col, float4* guide);

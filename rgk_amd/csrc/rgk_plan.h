@@ -110,6 +110,8 @@ inline int rgk_last_vertex_grid(uint32_t bound) { return rgk_bounded_grid(RGK_CU
 inline RgkGridPair rgk_light_grids(uint32_t bound) { return rgk_pair_grids(RGK_LIGHT_BLOCK, bound); }
 constexpr int RGK_CONNECT_BLOCK = 256;
 inline int rgk_connect_grid(uint32_t bound) { return rgk_bounded_grid(RGK_CUS * 8, bound, RGK_CONNECT_BLOCK); }
+// k_aov_hop (rgk_post.hip): workgroups of 256 over a queue of at most `bound` entries (the call's pixels)
+inline int rgk_aov_hop_grid(uint32_t bound) { return rgk_bounded_grid(RGK_CUS * 8, bound, 256u); }
 // k_resolve (gshift 0: a thread per pixel) or k_resolve_tiled (a wave per `PT` pixels, staged through `lds` bytes)
 struct RgkResolvePlan { int grid; uint32_t PT; size_t lds; };
 inline RgkResolvePlan rgk_resolve_plan(uint32_t npix, uint32_t gshift) {

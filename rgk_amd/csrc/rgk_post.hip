@@ -15,6 +15,8 @@
 //   k_tp_reproject           the previous frame's history {rgb, length} -> the current frame's pixels: four taps, each tested against the
 //                            previous frame's feature planes
 //   k_tp_blend               accumulator + reprojected history -> the next frame's history and the image to filter
+//   k_aov_hop                one hop of the feature planes that follow mirrors and glass: a terminal vertex, miss or dropped vertex
+//                            -> the planes, a delta vertex -> the continuation ray, compacted into the next hop's queue
 // (tests/noise_ref.py's k_nz_prepare, k_nz_prefilter and k_nz_atrous are k_dn_prepare<true> and k_dn_atrous<VarianceMean / VarianceGuided>)
 //
 // The traversal between raygen and gather is the round's own k_trace_closest (rgk_launch_trace_closest): no second walker.
@@ -533,4 +535,128 @@ void rgk_launch_tp_blend(hipStream_t st, size_t P, const float* accum_rgb, const
                          float alpha_min, float max_len, uint32_t demodulate, float albedo_floor, float* out_hist_rgb, float* out_hist_len, float* out_rgb) {
     k_tp_blend<0><<<rgk_post_pixel_grid(P), RGK_POST_BLOCK, 0, st>>>(P, accum_rgb, accum_count, albedo, hist_rgb, hist_len, alpha_min, max_len, demodulate, albedo_floor,
                                                                  out_hist_rgb, out_hist_len, out_rgb);
+}
+
+// ------------------------------------------------------------------ feature planes through delta chains (rgk.h rgk_render_aov_chain_device)
+// One hop of the chain: a lane per entry of hop k's queue.  The entry is the ray the walker has just traced (A / B as every ray
+// queue, the pixel's slot in B.w) and its hit; per slot {T.rgb, L} -- the product of the delta weights and the length of the chain
+// so far -- in one float4 plane, implicit {1, 1, 1 | 0} at hop 0.  A lane either writes its pixel's planes (miss, dropped vertex,
+// terminal vertex) or appends the ray the integrator would continue with to hop k + 1's queue: wave ballot + prefix, the four
+// waves add up through LDS, one atomic per workgroup on counters[RGK_CNT_QUEUE + k + 1] (written out here: the shared
+// block_append of rgk_shade.h is sized for another workgroup).  Every output is indexed by the slot, so the order of the queue
+// does not show in the planes.
+// The three delta kinds are sampled with the statements bxdf_sample (rgk_device.h) runs for them at u = U = (0x1.fffffep-1f, 0);
+// the LTC and diffuse cases are not in this kernel.  (A template for the reason k_tp_reproject is one.)
+__device__ __forceinline__ bool aov_is_delta(uint32_t kind) { return kind == RGK_BXDF_MIRROR || kind == RGK_BXDF_DIELECTRIC || kind == RGK_BXDF_TRANSPARENT; }
+__device__ __forceinline__ void aov_delta_sample(const DevScene& sc, const DevMaterial& m, f3 Vi, float2 uv, f3& dir, f3& weight, bool& may_leak) {
+    may_leak = false;
+    if (m.kind == RGK_BXDF_MIRROR) {
+        dir = mk3(-Vi.x, -Vi.y, Vi.z);
+        weight = tex_get(sc, m.t_color, uv);
+    } else if (m.kind == RGK_BXDF_DIELECTRIC) {
+        float eta = (Vi.z < 0) ? m.ior : (float)(1.0 / (double)m.ior);
+        float R, cosT;
+        fresnel_dielectric(eta, fabsf(Vi.z), R, cosT);
+        weight = tex_get(sc, m.t_color, uv);
+        float ux = 0x1.fffffep-1f;
+        if (decide_and_rescale(ux, R)) { dir = mk3(-Vi.x, -Vi.y, Vi.z); return; }
+        cosT = fabsf(cosT);
+        dir = mk3(-Vi.x * eta, -Vi.y * eta, (Vi.z > 0) ? -cosT : cosT);
+        may_leak = true;
+    } else { // RGK_BXDF_TRANSPARENT
+        dir = mk3(-Vi.x, -Vi.y, -Vi.z);
+        weight = mk3(1.f, 1.f, 1.f);
+        may_leak = true;
+    }
+}
+
+template <int = 0>
+__global__ __launch_bounds__(256) void k_aov_hop(const DevScene sc, float bumpmap_scale, uint32_t xres, const uint32_t* __restrict__ pix_xy, uint32_t n, uint32_t hop,
+                                                  uint32_t max_hops, const float4* __restrict__ rayA, const float4* __restrict__ rayB, const float4* __restrict__ hit,
+                                                  float4* __restrict__ state, float4* __restrict__ nextA, float4* __restrict__ nextB, uint32_t* __restrict__ counters,
+                                                  float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ depth, int32_t* __restrict__ tri_out,
+                                                  uint8_t* __restrict__ hops_out) {
+    __shared__ uint32_t s_cnt[4];
+    __shared__ uint32_t s_base;
+    lut_lds_fill(sc);
+    // (a queue never holds more entries than the call has pixels -- an entry leaves at most one -- and every plane here has n elements)
+    const uint32_t queued = counters[RGK_CNT_QUEUE + hop], count = queued < n ? queued : n;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    // workgroup-uniform trip count (the compaction synchronises the workgroup)
+    for (uint32_t base = blockIdx.x * 256u; base < count; base += gridDim.x * 256u) {
+        const uint32_t i = base + threadIdx.x;
+        bool cont = false;
+        float4 nA = make_float4(0, 0, 0, 0), nB = nA, nS = nA;
+        uint32_t slot = 0;
+        if (i < count) {
+            const float4 a = rayA[i], b = rayB[i], h = hit[i];
+            slot = __float_as_uint(b.w);
+            if (slot < n) { // (always: raygen numbered the slots 0 .. n - 1)
+                const uint32_t pix = pix_xy[slot];
+                const size_t p = (size_t)(pix >> 16) * xres + (pix & 0xffffu);
+                f3 T = mk3(1.f, 1.f, 1.f);
+                float L = 0.f;
+                if (hop) { const float4 s = state[slot]; T = mk3(s.x, s.y, s.z); L = s.w; }
+                const int tri = __float_as_int(h.w);
+                f3 nrm = mk3(0.f, 0.f, 0.f), alb = nrm;
+                float z = 0.f;
+                if (tri >= 0) {
+                    Vertex v;
+                    surface_point(sc, bumpmap_scale, mk3(a.x, a.y, a.z), mk3(a.w, b.x, b.y), h, v);
+                    z = L + h.x;
+                    if (v.ok) {
+                        if (aov_is_delta(v.mat.kind) && hop < max_hops) {
+                            f3 dirL, weight; bool may_leak;
+                            aov_delta_sample(sc, v.mat, v.VrL, v.uv, dirL, weight, may_leak);
+                            const f3 dir = qrot(qinverse(v.g2l), dirL);
+                            if (!(!(dot3(dir, v.faceN) * dot3(v.Vr, v.faceN) > 0) && !may_leak)) { // the integrator's leak rule (path_step, rgk_shade.h)
+                                cont = true;
+                                T = T * weight;
+                                const f3 no = v.pos + v.faceN * sc.epsilon * 10.0f * (dirL.z < 0 ? -1.0f : 1.0f);
+                                const f3 nd = norm3(norm3(dir));
+                                nA = make_float4(no.x, no.y, no.z, nd.x);
+                                nB = make_float4(nd.y, nd.z, __int_as_float(tri), __uint_as_float(slot));
+                                nS = make_float4(T.x, T.y, T.z, z);
+                            }
+                        }
+                        if (!cont) {
+                            nrm = v.lightN;
+                            alb = T * albedo_of(sc, v.mat, v.uv);
+                        }
+                    }
+                }
+                if (!cont) {
+                    if (tri_out) tri_out[p] = tri < 0 ? -1 : tri;
+                    if (depth) depth[p] = z;
+                    if (normal) { normal[3 * p] = nrm.x; normal[3 * p + 1] = nrm.y; normal[3 * p + 2] = nrm.z; }
+                    if (albedo) { albedo[3 * p] = alb.x; albedo[3 * p + 1] = alb.y; albedo[3 * p + 2] = alb.z; }
+                    if (hops_out) hops_out[p] = (uint8_t)hop;
+                }
+            }
+        }
+        const unsigned long long m = __ballot(cont);
+        if (lane == 0) s_cnt[w] = __popcll(m);
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            uint32_t t = 0;
+            for (int k = 0; k < 4; k++) { const uint32_t c = s_cnt[k]; s_cnt[k] = t; t += c; }
+            s_base = t ? atomicAdd(&counters[RGK_CNT_QUEUE + hop + 1], t) : 0u;
+        }
+        __syncthreads();
+        if (cont) {
+            const uint32_t q = s_base + s_cnt[w] + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+            if (q < n) { // (always: see `count`)
+                nextA[q] = nA; nextB[q] = nB;
+                state[slot] = nS;
+            }
+        }
+        __syncthreads(); // s_cnt / s_base are rewritten by the next trip
+    }
+}
+
+void rgk_launch_aov_hop(hipStream_t st, const DevScene& sc, float bumpmap_scale, uint32_t xres, const uint32_t* pix_xy, uint32_t n, uint32_t hop, uint32_t max_hops,
+                        const float4* rayA, const float4* rayB, const float4* hit, float4* state, float4* nextA, float4* nextB, uint32_t* counters, float* albedo,
+                        float* normal, float* depth, int32_t* tri, uint8_t* hops) {
+    k_aov_hop<0><<<rgk_aov_hop_grid(n), 256, RGK_LDS_SHADE_BYTES, st>>>(sc, bumpmap_scale, xres, pix_xy, n, hop, max_hops, rayA, rayB, hit, state, nextA, nextB, counters, albedo,
+                                                                        normal, depth, tri, hops);
 }

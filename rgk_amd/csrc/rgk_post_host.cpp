@@ -187,6 +187,64 @@ int rgk_render_aov(rgk_scene* s, const rgk_camera* camera, const rgk_params* prm
     return RGK_OK;
 }
 
+int rgk_render_aov_chain_device(rgk_scene* s, const rgk_camera* camera, const rgk_params* prm, const rgk_tile* tiles, uint32_t n_tiles, uint32_t max_hops,
+                                float* d_albedo, float* d_normal, float* d_depth, int32_t* d_tri, uint8_t* d_hops) {
+    int rc;
+    std::vector<uint32_t> toff; // (read by a queued copy: lives until the stream has been waited for)
+    if (max_hops > RGK_AOV_MAX_HOPS) return fail(RGK_ERR_INVALID, "max_hops %u: at most %d", max_hops, RGK_AOV_MAX_HOPS);
+    if ((rc = check_aov_args(s, camera, prm, tiles, n_tiles, toff))) return rc;
+    const uint32_t n = toff[n_tiles];
+    return post_call(s, "rgk_render_aov_chain_device", POST_AOV_CHAIN, n != 0, [&](PostTimer& tm) -> int {
+        // The buffers of rgk_render_aov_device, with the same argument: the round's pixel list, both pairs of ray planes (hop k reads
+        // pair k & 1 and fills the other), the hit plane, and the path-state plane for {T.rgb, L} -- every pass writes a slot's state
+        // (its first vertex) before a later vertex reads it.  The counters are the round's: every pass initialises them first.
+        // Nothing is read back between the hops: walker and hop kernel of hop k take the queue's length from the device counter.
+        if ((rc = ensure_workspace(s, n))) return rc;
+        hipStream_t st = s->stream;
+        DevCamera cam;
+        make_camera(camera, cam);
+        cam.lens_size = 0.0f; // every feature ray leaves from the camera's origin
+        if ((rc = tm.mark()) || (rc = queue_pixel_list(s, tiles, n_tiles, toff))) return rc;
+        rgk_launch_init_counters(st, s->counters.p, n);
+        rgk_launch_aov_raygen(st, cam, prm->xres, prm->yres, s->pix_xy.p, n, s->rayA[0].p, s->rayB[0].p);
+        if ((rc = tm.mark())) return rc;
+        for (uint32_t k = 0; k <= max_hops; k++) {
+            const uint32_t cur = k & 1u;
+            rgk_launch_trace_closest(st, s->dev, s->tcfg, false, s->rayA[cur].p, s->rayB[cur].p, nullptr, s->hit.p,
+                                     {n, s->counters.p + RGK_CNT_QUEUE + k, s->counters.p + RGK_CNT_FETCH_T + k}, s->stats.p);
+            if ((rc = tm.mark())) return rc;
+            rgk_launch_aov_hop(st, s->dev, prm->bumpmap_scale, prm->xres, s->pix_xy.p, n, k, max_hops, s->rayA[cur].p, s->rayB[cur].p, s->hit.p, s->thr.p,
+                               s->rayA[cur ^ 1u].p, s->rayB[cur ^ 1u].p, s->counters.p, d_albedo, d_normal, d_depth, d_tri, d_hops);
+            if ((rc = tm.mark())) return rc;
+        }
+        return 0;
+    });
+}
+
+int rgk_render_aov_chain(rgk_scene* s, const rgk_camera* camera, const rgk_params* prm, const rgk_tile* tiles, uint32_t n_tiles, uint32_t max_hops, float* albedo,
+                         float* normal, float* depth, int32_t* tri, uint8_t* hops) {
+    int rc;
+    std::vector<uint32_t> toff;
+    if (max_hops > RGK_AOV_MAX_HOPS) return fail(RGK_ERR_INVALID, "max_hops %u: at most %d", max_hops, RGK_AOV_MAX_HOPS);
+    if ((rc = check_aov_args(s, camera, prm, tiles, n_tiles, toff))) return rc;
+    HIPCHK(hipSetDevice(s->device));
+    const size_t P = (size_t)prm->xres * prm->yres;
+    DevBuf<float> d_alb, d_nrm, d_z;
+    DevBuf<int32_t> d_tri;
+    DevBuf<uint8_t> d_hops;
+    // (the planes go up first: pixels outside the tiles keep what the caller had there)
+    if ((albedo && (rc = d_alb.upload(albedo, 3 * P))) || (normal && (rc = d_nrm.upload(normal, 3 * P))) || (depth && (rc = d_z.upload(depth, P))) ||
+        (tri && (rc = d_tri.upload(tri, P))) || (hops && (rc = d_hops.upload(hops, P))))
+        return rc;
+    if ((rc = rgk_render_aov_chain_device(s, camera, prm, tiles, n_tiles, max_hops, albedo ? d_alb.p : nullptr, normal ? d_nrm.p : nullptr, depth ? d_z.p : nullptr,
+                                          tri ? d_tri.p : nullptr, hops ? d_hops.p : nullptr)))
+        return rc;
+    if ((albedo && (rc = down(albedo, d_alb, 3 * P))) || (normal && (rc = down(normal, d_nrm, 3 * P))) || (depth && (rc = down(depth, d_z, P))) ||
+        (tri && (rc = down(tri, d_tri, P))) || (hops && (rc = down(hops, d_hops, P))))
+        return rc;
+    return RGK_OK;
+}
+
 int rgk_denoise_device(rgk_scene* s, uint32_t xres, uint32_t yres, const float* d_accum_rgb, const uint32_t* d_accum_count, const float* d_albedo,
                        const float* d_normal, const float* d_depth, const rgk_denoise_params* dp, float* d_out_rgb) {
     if (!dp) return fail(RGK_ERR_INVALID, "null argument");

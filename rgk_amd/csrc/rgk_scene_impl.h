@@ -93,7 +93,7 @@ struct RgkTuning {
 };
 
 // rgk_scene_get_post_timing's `which` (rgk.h): the post-processing call whose launch times a slot holds
-enum PostSlot : uint32_t { POST_AOV = 0, POST_DENOISE = 1, POST_DENOISE_VARIANCE = 2, POST_NOISE = 3, POST_FOLD = 4, POST_TEMPORAL = 5, POST_SLOTS = 6 };
+enum PostSlot : uint32_t { POST_AOV = 0, POST_DENOISE = 1, POST_DENOISE_VARIANCE = 2, POST_NOISE = 3, POST_FOLD = 4, POST_TEMPORAL = 5, POST_AOV_CHAIN = 6, POST_SLOTS = 7 };
 constexpr uint32_t RGK_SCENE_MAGIC = 0x53474b52u; // "RKGS": what a live scene handle starts with (rgk_scene_get_post_timing)
 struct rgk_scene {
     uint32_t magic = RGK_SCENE_MAGIC;

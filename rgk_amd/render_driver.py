@@ -148,6 +148,26 @@ class Scene:
         capi.check(self.lib, self.lib.rgk_render_aov_device(self.h, C.byref(camera), C.byref(params), tiles, len(tiles),
                                                             d_albedo, d_normal, d_depth, d_tri))
 
+    def render_aov_chain(self, camera, params, tiles, max_hops, albedo=None, normal=None, depth=None, tri=None, hops=None, sentinel=None):
+        """rgk_render_aov_chain, host buffers: the planes of render_aov, followed through up to `max_hops` mirror / dielectric /
+        transparent surfaces to the first other surface, and hops (y, x) uint8, the delta surfaces passed on the way.  Planes that
+        are not passed in are created (filled with `sentinel`, default 0)."""
+        y, x = params.yres, params.xres
+        fill = 0 if sentinel is None else sentinel
+        albedo = np.full((y, x, 3), fill, np.float32) if albedo is None else albedo
+        normal = np.full((y, x, 3), fill, np.float32) if normal is None else normal
+        depth = np.full((y, x), fill, np.float32) if depth is None else depth
+        tri = np.full((y, x), fill, np.int32) if tri is None else tri
+        hops = np.full((y, x), fill, np.uint8) if hops is None else hops
+        capi.check(self.lib, self.lib.rgk_render_aov_chain(self.h, C.byref(camera), C.byref(params), tiles, len(tiles), max_hops, albedo.ctypes.data,
+                                                           normal.ctypes.data, depth.ctypes.data, tri.ctypes.data, hops.ctypes.data))
+        return albedo, normal, depth, tri, hops
+
+    def render_aov_chain_device(self, camera, params, tiles, max_hops, d_albedo=None, d_normal=None, d_depth=None, d_tri=None, d_hops=None):
+        """rgk_render_aov_chain_device: DEVICE pointers (ints) on the scene's GPU; any may be None."""
+        capi.check(self.lib, self.lib.rgk_render_aov_chain_device(self.h, C.byref(camera), C.byref(params), tiles, len(tiles), max_hops,
+                                                                  d_albedo, d_normal, d_depth, d_tri, d_hops))
+
     def denoise_device(self, xres, yres, d_accum_rgb, d_accum_count, d_albedo, d_normal, d_depth, params, d_out_rgb):
         """rgk_denoise_device: the guided a-trous filter of a whole frame, DEVICE pointers (ints) on the scene's GPU."""
         capi.check(self.lib, self.lib.rgk_denoise_device(self.h, xres, yres, d_accum_rgb, d_accum_count, d_albedo, d_normal, d_depth,
@@ -195,8 +215,8 @@ class Scene:
 
     def post_timing(self, which):
         """HIP-event times (ms) of the launches of the last feature pass (0) / denoise call (1) / variance-guided denoise call (2) /
-        noise estimate (3) / round fold (4: the copy of its tile list, the fold) / temporal pair (5: reproject, blend);
-        set_tuning(time_post=1) first."""
+        noise estimate (3) / round fold (4: the copy of its tile list, the fold) / temporal pair (5: reproject, blend) /
+        followed feature pass (6: list + ray generation, then walker and k_aov_hop per hop); set_tuning(time_post=1) first."""
         ms, n = (C.c_double * 32)(), C.c_uint32(32)
         capi.check(self.lib, self.lib.rgk_scene_get_post_timing(self.h, which, ms, C.byref(n)))
         return list(ms[:min(n.value, 32)])
@@ -374,8 +394,18 @@ class RenderDriver:
     """RenderDriver::RenderFrame / RenderRound for one process per GPU."""
 
     def __init__(self, scene, cfg, camera, rank=0, world_size=1, device=None, sampler=capi.SAMPLER_HALTON, flags=0,
-                 host_reduce=False, track_noise=False, adaptive=None, history=None):
+                 host_reduce=False, track_noise=False, adaptive=None, history=None, aov_hops=0):
         import torch
+        # aov_hops (0 .. capi.AOV_MAX_HOPS): render_aov() -- and with it denoise(), denoise_variance() and the aov_files -- takes its
+        # planes from rgk_render_aov_chain_device, which follows mirrors and glass to the first other surface; aov_hops_plane() is
+        # the number of such surfaces a pixel passed.  0: the first-hit planes, every code path the one without it.
+        aov_hops = int(aov_hops)
+        if not 0 <= aov_hops <= capi.AOV_MAX_HOPS:
+            raise ValueError(f"aov_hops must be 0 .. {capi.AOV_MAX_HOPS}")
+        if aov_hops > 0 and history is not None:
+            raise ValueError("aov_hops > 0 cannot be combined with history=: the reproject step tests the history against first-hit "
+                             "geometry, and reprojecting the virtual images behind mirrors and glass is not done")
+        self.aov_hops = aov_hops
         # history (a TemporalHistory shared by the drivers of an animation's frames): denoise_temporal() reprojects the previous
         # frame's history into this frame, blends this frame's samples in and commits the result for the next frame.  Nothing else
         # reads it: rounds, accumulator and denoise() are the same with and without one.
@@ -487,6 +517,7 @@ class RenderDriver:
     def render_aov(self):
         """First-hit feature planes of the whole frame, one ray per pixel through the pixel centre: a dict of torch tensors
         on the device -- "albedo", "normal" (y, x, 3) float32, "depth" (y, x) float32, "tri" (y, x) int32 (-1: miss).
+        On a driver with aov_hops > 0: the planes followed through mirrors and glass (rgk_render_aov_chain_device), and "hops".
         Rendered once per driver (one frame, one camera) and kept.  With several ranks the root alone renders them, the
         whole frame (it is one ray per pixel); the other ranks get None."""
         import torch
@@ -498,11 +529,26 @@ class RenderDriver:
                  "normal": torch.empty((y, x, 3), dtype=torch.float32, device=self.device),
                  "depth": torch.empty((y, x), dtype=torch.float32, device=self.device),
                  "tri": torch.empty((y, x), dtype=torch.int32, device=self.device)}
+            if self.aov_hops > 0:
+                a["hops"] = torch.empty((y, x), dtype=torch.uint8, device=self.device)
             torch.cuda.current_stream(self.device).synchronize()
-            self.scene.render_aov_device(self.camera, self.params, self.tasks, a["albedo"].data_ptr(), a["normal"].data_ptr(),
-                                         a["depth"].data_ptr(), a["tri"].data_ptr())
+            if self.aov_hops > 0:
+                self.scene.render_aov_chain_device(self.camera, self.params, self.tasks, self.aov_hops, a["albedo"].data_ptr(), a["normal"].data_ptr(),
+                                                   a["depth"].data_ptr(), a["tri"].data_ptr(), a["hops"].data_ptr())
+            else:
+                self.scene.render_aov_device(self.camera, self.params, self.tasks, a["albedo"].data_ptr(), a["normal"].data_ptr(),
+                                             a["depth"].data_ptr(), a["tri"].data_ptr())
             self.aov = a
         return self.aov
+
+    def aov_hops_plane(self):
+        """(y, x) uint8 tensor on the device: the mirror / dielectric / transparent surfaces each pixel's feature chain passed
+        before the surface render_aov() reports (all 0 on a driver made with aov_hops=0).  Root rank only."""
+        import torch
+        a = self.render_aov()
+        if a is None:
+            return None
+        return a["hops"] if "hops" in a else torch.zeros((self.cfg.yres, self.cfg.xres), dtype=torch.uint8, device=self.device)
 
     def default_denoise_params(self):
         """The shipped defaults; sigma_color = DENOISE_SIGMA_K x the mean over pixels of the largest channel of the image."""
@@ -672,7 +718,8 @@ class RenderDriver:
                      until_noise=None, noise_file=None, on_noise=None, temporal=False):
         """RenderFrame: Rounds mode (render_driver.cpp:229-235) or Timed mode (:237-247); with `output_file` the
         normalised image is rewritten after every round, as the reference does (rank 0 only).
-        aov_files: {"albedo" / "normal" / "depth": path} -- the feature planes, written once (depth replicated to R, G, B).
+        aov_files: {"albedo" / "normal" / "depth" / "hops": path} -- the feature planes, written once (depth and hops replicated to
+        R, G, B); on a driver with aov_hops > 0 they are the followed planes.
         denoised_file: rewritten after every round that rewrites output_file, normalised with the scale output_file got.
         With track_noise -- until_noise: stop once noise()["rel"] <= until_noise, checked after every round from the second on
         (`rounds` / `minutes` still bound the frame); from the second round on denoised_file comes from the variance-guided
@@ -697,7 +744,8 @@ class RenderDriver:
         if aov_files and self.rank == 0:
             a = self.render_aov()
             for name, path in aov_files.items():
-                plane = a[name] if a[name].dim() == 3 else a[name].unsqueeze(-1).expand(-1, -1, 3)
+                src = self.aov_hops_plane().float() if name == "hops" else a[name]
+                plane = src if src.dim() == 3 else src.unsqueeze(-1).expand(-1, -1, 3)
                 write_exr(path, plane.cpu().numpy())
         if adapting and self.rounds_done >= 2:  # resumed
             live, _, done = self.adapt_select(until_noise)
