@@ -1,6 +1,7 @@
 // CPU harness of the GPU-free commit unit (rgk_amd/csrc/rgk_commit.cpp), linked with nothing else of the library and
 // run under ASan + UBSan by tests/test_commit_cpu.py:  commit_main <case> [--digest]
-//   geom-default | geom-leaf1 | geom-leaf16 | geom-nosplit | geom-noopt | geom-single | refit-pieces | textures | small
+//   geom-default | geom-leaf1 | geom-leaf16 | geom-nosplit | geom-noopt | geom-single | refit-pieces | textures |
+//   pool-tables | pool-limits | pool-bits | pool-small | small
 // Inputs come from a fixed LCG seed, no file is read.  Exit status 0: every condition of the case held.
 // --digest: an FNV-1a digest per output table on stdout (a refactor of the unit must leave them as they are).
 #include <cmath>
@@ -381,6 +382,191 @@ static void check_textures() {
           "two runs on the same input differ");
 }
 
+// ------------------------------------------------------------------ texture pool cases
+// assign_palettes + pack_texels on descriptors that hold textures only: where the tables land (the kernels decode a table
+// through LDS while its offset + 256 <= RGK_LDS_LUT_FLOATS = 512, rgk_device.h), the 256 / 257 value limit, values told apart
+// by their bits, and the tiled byte layout at its smallest shapes.
+struct Pool {
+    std::vector<Palette> palettes;
+    std::vector<int> tex_palette;
+    TexturePools pools;
+};
+static int run_pool(const std::vector<rgk_texture>& tex, uint32_t flags, Pool& p) {
+    rgk_scene_desc d;
+    std::memset(&d, 0, sizeof(d));
+    d.n_textures = (uint32_t)tex.size(); d.textures = tex.data(); d.build_flags = flags;
+    assign_palettes(&d, p.palettes, p.tex_palette, p.pools);
+    return pack_texels(&d, p.palettes, p.tex_palette, p.pools);
+}
+static rgk_texture float_texture(uint32_t w, uint32_t h, const std::vector<float>& texels) {
+    rgk_texture t{};
+    t.kind = RGK_TEX_RGB32F; t.width = w; t.height = h; t.texels = texels.data();
+    return t;
+}
+static rgk_texture byte_texture(uint32_t w, uint32_t h, const std::vector<uint8_t>& bytes, const std::vector<float>& lut) {
+    rgk_texture t{};
+    t.kind = RGK_TEX_RGB8; t.width = w; t.height = h; t.texels8 = bytes.data(); t.lut = lut.data();
+    return t;
+}
+static float from_bits(uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; }
+// tex_row / tex_col of rgk_device.h for a byte texture of width w, restated
+static uint32_t row_of(uint32_t w, uint32_t y) { return (y >> 2) * (((w + 7u) >> 3) << 5) + ((y & 3u) << 3); }
+static uint32_t col_of(uint32_t x) { return ((x >> 3) << 5) + (x & 7u); }
+
+// Three caller tables (1 x 1 byte textures) and two few-valued float textures whose union fits one table: the callers' tables
+// at 0, 256, 512 in the order of their first appearance -- a repeated table takes no new place --, the shared one at 768.
+static void check_pool_tables() {
+    std::vector<float> lut[3];
+    for (int k = 0; k < 3; k++) for (int i = 0; i < 256; i++) lut[k].push_back((float)(k + 2) * (float)((i * 37 + k) & 255));
+    const std::vector<uint8_t> px[4] = {{1, 2, 3}, {4, 5, 6}, {7, 8, 9}, {10, 11, 12}};
+    std::vector<float> a, b;
+    for (int i = 0; i < 3 * 8 * 6; i++) a.push_back(1000.5f + (float)(i % 120));          // 120 values
+    for (int i = 0; i < 3 * 5 * 10; i++) b.push_back(1000.5f + (float)(60 + i % 130));     // 130 values, 60 of them a's: a union of 190
+    const std::vector<rgk_texture> tex = {byte_texture(1, 1, px[0], lut[0]), float_texture(8, 6, a), byte_texture(1, 1, px[1], lut[1]), byte_texture(1, 1, px[3], lut[0]),
+                                          byte_texture(1, 1, px[2], lut[2]), float_texture(5, 10, b)};
+    Pool p;
+    CHECK(run_pool(tex, 0u, p) == 0, "%s", rgk_last_error());
+    const std::vector<TexRef>& R = p.pools.refs;
+    CHECK(R.size() == 6 && p.pools.luts.size() == 4 * 256, "%zu refs, %zu table floats", R.size(), p.pools.luts.size());
+    if (g_failed) return;
+    CHECK(R[0].c == 0 && R[2].c == 256 && R[4].c == 512 && R[3].c == 0, "callers' tables at %u %u %u, the repeated one at %u", R[0].c, R[2].c, R[4].c, R[3].c);
+    CHECK(R[1].c == 768 && R[5].c == 768, "shared table at %u and %u", R[1].c, R[5].c);
+    CHECK(p.pools.n_float == 2 && p.pools.n_palettized == 2, "%u float, %u palettized", p.pools.n_float, p.pools.n_palettized);
+    for (int k = 0; k < 3; k++) CHECK(std::memcmp(&p.pools.luts[256 * (size_t)k], lut[k].data(), 1024) == 0, "table %d is not the caller's", k);
+    size_t bad = 0;
+    for (int i : {1, 5}) {
+        const rgk_texture& x = tex[(size_t)i];
+        CHECK(R[(size_t)i].kind == RGK_TEX_RGB8, "T%d kind %u", i, R[(size_t)i].kind);
+        for (uint32_t y = 0; y < x.height; y++)
+            for (uint32_t xx = 0; xx < x.width; xx++) {
+                const uint32_t w = p.pools.texels8[R[(size_t)i].b + row_of(x.width, y) + col_of(xx)];
+                for (int ch = 0; ch < 3; ch++) bad += bits(p.pools.luts[768 + ((w >> (8 * ch)) & 255u)]) != bits(x.texels[3 * (y * x.width + xx) + (uint32_t)ch]);
+            }
+    }
+    CHECK(bad == 0, "%zu channel values decode wrong through the shared table", bad);
+    Pool keep; // RGK_BUILD_KEEP_FLOAT_TEXTURES: the callers' tables stay where they are, no table of the scene's own
+    CHECK(run_pool(tex, RGK_BUILD_KEEP_FLOAT_TEXTURES, keep) == 0, "%s", rgk_last_error());
+    CHECK(keep.pools.luts.size() == 3 * 256 && keep.pools.n_float == 2 && keep.pools.n_palettized == 0 && keep.pools.refs[1].kind == RGK_TEX_RGB32F && keep.pools.refs[4].c == 512,
+          "keep-float: %zu table floats, %u palettized", keep.pools.luts.size(), keep.pools.n_palettized);
+}
+
+// Exactly 256 distinct values: bytes + table.  257: stays float.
+static void check_pool_limits() {
+    for (int n_vals : {256, 257}) {
+        std::vector<float> t;
+        for (int i = 0; i < 3 * 16 * 6; i++) t.push_back(-7.25f + 0.5f * (float)(i < n_vals ? i : (i * 7) % n_vals)); // 288 channel values
+        std::set<uint32_t> distinct;
+        for (float f : t) distinct.insert(bits(f));
+        CHECK((int)distinct.size() == n_vals, "%zu distinct values", distinct.size());
+        Pool p;
+        CHECK(run_pool({float_texture(16, 6, t)}, 0u, p) == 0, "%s", rgk_last_error());
+        if (g_failed) return;
+        const TexRef& r = p.pools.refs[0];
+        if (n_vals == 256) {
+            CHECK(r.kind == RGK_TEX_RGB8 && p.pools.n_palettized == 1 && p.pools.luts.size() == 256 && p.pools.texels.empty(), "256 values: kind %u, %zu table floats", r.kind, p.pools.luts.size());
+            size_t bad = 0;
+            for (uint32_t y = 0; y < 6 && r.kind == RGK_TEX_RGB8; y++)
+                for (uint32_t x = 0; x < 16; x++) {
+                    const uint32_t w = p.pools.texels8[r.b + row_of(16, y) + col_of(x)];
+                    for (int ch = 0; ch < 3; ch++) bad += bits(p.pools.luts[r.c + ((w >> (8 * ch)) & 255u)]) != bits(t[3 * (y * 16 + x) + (uint32_t)ch]);
+                }
+            CHECK(bad == 0, "%zu channel values decode wrong", bad);
+        } else {
+            CHECK(r.kind == RGK_TEX_RGB32F && p.pools.n_float == 1 && p.pools.n_palettized == 0 && p.pools.luts.empty() && p.pools.texels8.empty() && p.pools.texels.size() == 96,
+                  "257 values: kind %u, %zu table floats, %zu byte texels", r.kind, p.pools.luts.size(), p.pools.texels8.size());
+        }
+    }
+}
+
+// +0.0, -0.0 and NaNs of different payloads and signs are different values: every texel decodes to its own bits.
+static void check_pool_bits() {
+    const uint32_t special[] = {0x00000000u, 0x80000000u, 0x7fc00000u, 0x7fc12345u, 0xffc00001u, 0x7f800000u, 0xff800000u, 0x00000001u, 0x80000001u, 0x3f800000u};
+    const size_t ns = sizeof(special) / sizeof(special[0]);
+    Lcg r;
+    std::vector<float> t;
+    for (size_t i = 0; i < 3 * 9 * 5; i++) t.push_back(from_bits(special[i < ns ? i : r.next() % ns]));
+    for (size_t i = 0; i < ns; i++) CHECK(bits(t[i]) == special[i], "value %zu did not keep its bits on the way in: %08x", i, bits(t[i]));
+    Pool p;
+    CHECK(run_pool({float_texture(9, 5, t)}, 0u, p) == 0, "%s", rgk_last_error());
+    if (g_failed) return;
+    const TexRef& rr = p.pools.refs[0];
+    CHECK(rr.kind == RGK_TEX_RGB8 && p.palettes.size() == 1 && p.palettes[0].vals.size() == ns, "kind %u, %zu values in the table", rr.kind, p.palettes.empty() ? (size_t)0 : p.palettes[0].vals.size());
+    if (g_failed) return;
+    size_t bad = 0;
+    std::set<uint32_t> used;
+    for (uint32_t y = 0; y < 5; y++)
+        for (uint32_t x = 0; x < 9; x++) {
+            const uint32_t w = p.pools.texels8[rr.b + row_of(9, y) + col_of(x)];
+            for (int ch = 0; ch < 3; ch++) {
+                const uint32_t byte = (w >> (8 * ch)) & 255u;
+                used.insert(byte);
+                bad += bits(p.pools.luts[rr.c + byte]) != bits(t[3 * (y * 9 + x) + (uint32_t)ch]);
+            }
+        }
+    CHECK(bad == 0, "%zu channel values decode to other bits", bad);
+    CHECK(used.size() == ns, "%zu table entries in use for %zu values", used.size(), ns);
+}
+
+// The smallest shapes of the tiled layout, (height, width) 1 x 1, 1 x 5, 9 x 1, 4 x 8, 5 x 9, 4 x 16, 3 x 7, each as a byte texture
+// and as a few-valued float texture, one after the other in one pool: texel (x, y) lies at tex_row(y) + tex_col(x), everything
+// else inside the texture's whole tiles is zero, and each texture starts on the 32-dword boundary where the one before ended.
+static void check_pool_small() {
+    const uint32_t sizes[7][2] = {{1, 1}, {1, 5}, {9, 1}, {4, 8}, {5, 9}, {4, 16}, {3, 7}};
+    Lcg r;
+    std::vector<float> lut(256), fvals;
+    for (int i = 0; i < 256; i++) lut[(size_t)i] = 0.25f * (float)i - 3.0f;
+    for (int i = 0; i < 100; i++) fvals.push_back(50.0625f + 0.125f * (float)i); // none of them in `lut`: a table of the scene's own
+    std::vector<std::vector<uint8_t>> bytes(7);
+    std::vector<std::vector<float>> floats(7);
+    std::vector<rgk_texture> tex;
+    for (int s = 0; s < 7; s++) {
+        const uint32_t h = sizes[s][0], w = sizes[s][1];
+        for (uint32_t k = 0; k < 3 * w * h; k++) { bytes[(size_t)s].push_back((uint8_t)(1u + r.next() % 255u)); floats[(size_t)s].push_back(fvals[1 + r.next() % 99]); } // no zero word: padding shows
+        floats[(size_t)s][0] = fvals[0];
+    }
+    for (int s = 0; s < 7; s++) {
+        tex.push_back(byte_texture(sizes[s][1], sizes[s][0], bytes[(size_t)s], lut));
+        tex.push_back(float_texture(sizes[s][1], sizes[s][0], floats[(size_t)s]));
+    }
+    Pool p;
+    CHECK(run_pool(tex, 0u, p) == 0, "%s", rgk_last_error());
+    if (g_failed) return;
+    CHECK(p.pools.n_float == 7 && p.pools.n_palettized == 7 && p.pools.luts.size() == 512 && p.pools.texels.empty(), "%u float, %u palettized, %zu table floats", p.pools.n_float,
+          p.pools.n_palettized, p.pools.luts.size());
+    size_t at = 0;
+    for (size_t i = 0; i < tex.size(); i++) {
+        const rgk_texture& x = tex[i];
+        const TexRef& rr = p.pools.refs[i];
+        const size_t span = ((x.width + 7) / 8) * ((x.height + 3) / 4) * 32;
+        CHECK(rr.kind == RGK_TEX_RGB8 && rr.a == (x.width | (x.height << 16)) && rr.c == (x.kind == RGK_TEX_RGB8 ? 0u : 256u), "T%zu: kind %u size %08x table %u", i, rr.kind, rr.a, rr.c);
+        CHECK(rr.b == at && rr.b % 32 == 0, "T%zu (%u x %u) starts at %u, the one before ended at %zu", i, x.height, x.width, rr.b, at);
+        CHECK(rr.b + span <= p.pools.texels8.size(), "T%zu: outside the pool", i);
+        if (g_failed) return;
+        std::vector<uint8_t> texel(span, 0);
+        size_t bad = 0, twice = 0, pad_nonzero = 0;
+        for (uint32_t y = 0; y < x.height; y++)
+            for (uint32_t xx = 0; xx < x.width; xx++) {
+                const uint32_t k = row_of(x.width, y) + col_of(xx);
+                CHECK(k < span, "T%zu: texel (%u, %u) at %u of %zu", i, xx, y, k, span);
+                if (k >= span) return;
+                twice += texel[k]++;
+                const uint32_t w = p.pools.texels8[rr.b + k];
+                bad += (w >> 24) != 0;
+                for (int ch = 0; ch < 3; ch++) {
+                    const size_t src = 3 * ((size_t)y * x.width + xx) + (size_t)ch;
+                    const uint32_t byte = (w >> (8 * ch)) & 255u;
+                    if (x.kind == RGK_TEX_RGB8) bad += byte != x.texels8[src] || bits(p.pools.luts[rr.c + byte]) != bits(lut[x.texels8[src]]);
+                    else bad += bits(p.pools.luts[rr.c + byte]) != bits(x.texels[src]);
+                }
+            }
+        for (size_t k = 0; k < span; k++) pad_nonzero += !texel[k] && p.pools.texels8[rr.b + k] != 0u;
+        CHECK(bad == 0 && twice == 0 && pad_nonzero == 0, "T%zu (%u x %u): %zu texels wrong, %zu places used twice, %zu padding words not zero", i, x.height, x.width, bad, twice, pad_nonzero);
+        at += span;
+    }
+    CHECK(at == p.pools.texels8.size(), "pool of %zu dwords, textures cover %zu", p.pools.texels8.size(), at);
+    CHECK(p.pools.refs[13].b == p.pools.refs[12].b + 32 && p.pools.refs[12].b % 32 == 0, "the texture after the 3 x 7 one starts at %u, the 3 x 7 one at %u", p.pools.refs[13].b, p.pools.refs[12].b);
+}
+
 // ------------------------------------------------------------------ small cases
 static uint32_t eligible(const std::vector<rgk_pointlight>& lights, float areal_power) {
     rgk_scene_desc d;
@@ -453,6 +639,10 @@ int main(int argc, char** argv) {
     else if (c == "geom-single") check_single_leaf();
     else if (c == "refit-pieces") check_refit_pieces();
     else if (c == "textures") check_textures();
+    else if (c == "pool-tables") check_pool_tables();
+    else if (c == "pool-limits") check_pool_limits();
+    else if (c == "pool-bits") check_pool_bits();
+    else if (c == "pool-small") check_pool_small();
     else if (c == "small") check_small();
     else { std::fprintf(stderr, "unknown case '%s'\n", c.c_str()); return 2; }
     if (g_failed) std::fprintf(stderr, "%d condition(s) failed in case %s\n", g_failed, c.c_str());

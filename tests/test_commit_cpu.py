@@ -12,6 +12,14 @@ links that one translation unit and nothing else of the library, makes its input
             parameter box evaluated in double, every point inside the box with tolerance zero;
   textures  six textures in one descriptor: palette detection (+0.0, -0.0 and a NaN among the values), table sharing, the
             caller's table, the 257-value texture that stays float, tiled byte texels bit-equal to their sources;
+  pool-*    assign_palettes + pack_texels on textures alone.  tables: three caller tables at offsets 0, 256, 512 in the order of
+            their first appearance (the kernels decode a table through LDS while offset + 256 <= 512, by global loads beyond:
+            tests/test_gpu_thresholds.py) and two few-valued float textures sharing one table at 768; limits: 256 distinct
+            values become bytes + table, 257 stay float; bits: +0.0, -0.0, NaNs of different payloads and signs, infinities and
+            denormals are different values, every texel decodes to its own bits; small: (height, width) 1 x 1, 1 x 5, 9 x 1,
+            4 x 8, 5 x 9, 4 x 16, 3 x 7 as byte and as few-valued float textures -- texel (x, y) at tex_row(y) + tex_col(x)
+            (rgk_device.h, restated in the harness), padding zero, every texture on the 32-dword boundary where the one
+            before ended;
   small     commit_bounds, const_light_eligible, build_areal_tables.
 
 Exit status 0 = every condition held and neither sanitizer spoke.  That the harness links at all, without the HIP runtime,
@@ -25,7 +33,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CPP = os.path.join(ROOT, "tests", "cpp")
 CSRC = os.path.join(ROOT, "rgk_amd", "csrc")
 
-CASES = ["geom-default", "geom-leaf1", "geom-leaf16", "geom-nosplit", "geom-noopt", "geom-single", "refit-pieces", "textures", "small"]
+CASES = ["geom-default", "geom-leaf1", "geom-leaf16", "geom-nosplit", "geom-noopt", "geom-single", "refit-pieces", "textures", "pool-tables", "pool-limits",
+         "pool-bits", "pool-small", "small"]
 
 
 @pytest.fixture(scope="module")

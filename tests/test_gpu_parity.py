@@ -965,8 +965,10 @@ def test_bxdf_value_and_sample_unit_level(rd, oracle, product_lib):
 
 def test_texture_lookup_unit_level(rd, oracle, product_lib):
     """GetPixelInterpolated / GetSlopeRight / GetSlopeBottom (src/texture.cpp:35-102): solid, empty, float and 8-bit textures
-    (the PNG of rubiks-bump and one of the shipped Sponza JPGs as decoded bytes), uv inside, outside (repeat), on texel
-    centres and on the wrap seam: integer / float arithmetic only, so HIP and oracle must agree bit for bit."""
+    (the bump-map PNG of rubiks-bump, 598 x 897 -- no multiple of the 8 x 4 byte tile either way --, from
+    tests/golden/scene_rubiks-bump.npz, and one of the shipped Sponza JPGs as decoded bytes), uv inside, outside (repeat), on
+    texel centres and on the wrap seam: integer / float arithmetic only, so HIP and oracle must agree bit for bit.  1500 uv per
+    texture.  (Scenes with more than two byte tables and the smallest tiled shapes: tests/test_gpu_thresholds.py.)"""
     from rgk_amd.proxy import shipped_sponza_textures
     sb = SceneBuilder()
     rng = np.random.default_rng(22)
@@ -976,12 +978,16 @@ def test_texture_lookup_unit_level(rd, oracle, product_lib):
     jpg = shipped_sponza_textures().get("KAMEN.JPG")
     if jpg is not None:
         ids.append(sb.add_image_texture8("kamen", np.ascontiguousarray(jpg[::-1])))
+    rubiks = SceneBuilder.load_npz(os.path.join(ROOT, "tests", "golden", "scene_rubiks-bump.npz"))
+    bump = rubiks.textures[next(m["tex_bump"] for m in rubiks.materials if m["tex_bump"] >= 0)]
+    assert bump["kind"] == capi.TEX_RGB8 and bump["data"].shape == (598, 897, 3)
+    ids.append(sb.add_image_texture8("rubiks-bump", bump["data"], lut=bump["lut"]))
     m = sb.new_material("m", capi.BXDF_DIFFUSE); m["tex_diffuse"] = ids[0]; sb.register_material(m)
     sb.add_primitive("cube", np.eye(4, dtype=np.float32), "m")
     desc = sb.to_desc()
     g, o = rd.Scene(desc), oracle.OracleScene(desc)
     L = oracle.lib()
-    n = 6000
+    n = 1500 * len(ids)     # (6000 over four or five textures before the rubiks-bump PNG joined them)
     tex = np.array([ids[i % len(ids)] for i in range(n)], dtype=np.int32)
     uv = rng.uniform(-2, 3, (n, 2)).astype(np.float32)
     uv[::7] = np.round(uv[::7] * 8) / 8                      # seams and exact fractions
