@@ -278,6 +278,10 @@ typedef struct rgk_scene rgk_scene;
 
 const char *rgk_last_error(void);
 int rgk_device_count(void);
+/* Debugging aid.  With RGK_POISON set in the environment (read once per process) every fresh device allocation of the library --
+ * a scene's buffers and the device builder's scratch -- is filled with 0xFF bytes, so that a read of memory nothing wrote shows
+ * in the results.  This is the number of bytes filled so far in this process; 0 when the switch is off. */
+uint64_t rgk_debug_poisoned_bytes(void);
 
 /* Scene::Commit() outputs (src/scene.cpp:294-400) + accelerator build + upload. */
 int rgk_scene_create(const rgk_scene_desc *desc, int device, rgk_scene **out);

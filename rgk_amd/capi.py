@@ -198,7 +198,7 @@ EXPORTS = ["rgk_last_error", "rgk_device_count", "rgk_scene_create", "rgk_scene_
            "rgk_render_aov_device", "rgk_render_aov", "rgk_denoise_device", "rgk_scene_get_post_timing",
            "rgk_noise_estimate_device", "rgk_denoise_variance_device", "rgk_adapt_select", "rgk_round_fold_device",
            "rgk_temporal_reproject_device", "rgk_temporal_blend_device",
-           "rgk_render_aov_chain_device", "rgk_render_aov_chain"]
+           "rgk_render_aov_chain_device", "rgk_render_aov_chain", "rgk_debug_poisoned_bytes"]
 AOV_MAX_HOPS = 8  # RGK_AOV_MAX_HOPS
 
 _p = C.POINTER
@@ -207,6 +207,8 @@ _p = C.POINTER
 def _bind(lib):
     lib.rgk_last_error.restype = C.c_char_p
     lib.rgk_device_count.restype = C.c_int
+    lib.rgk_debug_poisoned_bytes.argtypes = []
+    lib.rgk_debug_poisoned_bytes.restype = C.c_uint64
     lib.rgk_scene_create.argtypes = [_p(SceneDesc), C.c_int, _p(C.c_void_p)]
     lib.rgk_scene_destroy.argtypes = [C.c_void_p]
     lib.rgk_scene_destroy.restype = None

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/rgk.h"
+#include "rgk_poison.h"
 
 extern "C" int rgk_internal_fail(int code, const char* msg);
 
@@ -56,6 +57,8 @@ int rgk_accum_create(uint32_t xres, uint32_t yres, int device, rgk_accum** out) 
     a->xres = xres; a->yres = yres; a->device = device;
     if ((e = hipMalloc((void**)&a->rgb, a->pixels() * 3 * sizeof(float))) != hipSuccess) { delete a; return hip_fail("hipMalloc", e); }
     if ((e = hipMalloc((void**)&a->count, a->pixels() * sizeof(uint32_t))) != hipSuccess) { (void)hipFree(a->rgb); delete a; return hip_fail("hipMalloc", e); }
+    rgk_poison_fill(a->rgb, a->pixels() * 3 * sizeof(float)); // RGK_POISON=1 (rgk_poison.h): the clear below is what makes the accumulator start at zero
+    rgk_poison_fill(a->count, a->pixels() * sizeof(uint32_t));
     const int rc = rgk_accum_clear(a);
     if (rc) { rgk_accum_destroy(a); return rc; }
     *out = a;

@@ -30,6 +30,7 @@
 
 #include "rgk_build.h"
 #include "rgk_commit.h" // fail()
+#include "rgk_poison.h"
 #include "rgk_tree.h"
 
 namespace {
@@ -422,7 +423,12 @@ __global__ void k_qbvh_refit(QNode* __restrict__ nodes, uint32_t n_nodes, const 
 template <typename T>
 struct Tmp { // device scratch freed on scope exit
     T* p = nullptr;
-    hipError_t alloc(size_t n) { return hipMalloc((void**)&p, (n ? n : 1) * sizeof(T)); }
+    hipError_t alloc(size_t n) {
+        const size_t bytes = (n ? n : 1) * sizeof(T);
+        const hipError_t e = hipMalloc((void**)&p, bytes);
+        if (e == hipSuccess) rgk_poison_fill(p, bytes); // RGK_POISON=1: 0xFF bytes (rgk_poison.h); hipcub's storage is a Tmp too
+        return e;
+    }
     ~Tmp() { if (p) (void)hipFree(p); }
 };
 

@@ -208,6 +208,8 @@ int rgk_device_count(void) {
     return n;
 }
 
+uint64_t rgk_debug_poisoned_bytes(void) { return rgk_poison_total().load(std::memory_order_relaxed); }
+
 int rgk_scene_create(const rgk_scene_desc* d, int device, rgk_scene** out) {
     if (!out) return fail(RGK_ERR_INVALID, "null output pointer");
     *out = nullptr;

@@ -16,6 +16,7 @@
 #include "device_types.h"
 #include "rgk_commit.h" // fail
 #include "rgk_kernels.h"
+#include "rgk_poison.h"
 #include "rgk_round_plan.h"
 
 #pragma GCC visibility push(hidden) // shared between the host files, not exports of the library (popped at the end)
@@ -45,13 +46,7 @@ struct DevBuf {
         hipError_t e = hipMalloc((void**)&p, count * sizeof(T));
         if (e != hipSuccess) return fail(RGK_ERR_OOM, "hipMalloc(%zu bytes): %s", count * sizeof(T), hipGetErrorString(e));
         n = count;
-        // RGK_POISON=1: every fresh device buffer is filled with 0xFF bytes (NaN as float, huge as index), so that any read of
-        // memory the pipeline did not write first shows in the results instead of hiding behind zero-filled fresh pages
-        static const bool poison = std::getenv("RGK_POISON") != nullptr;
-        if (poison) { // (the fill runs on the null stream, the scene's stream is non-blocking: wait for it, or it lands on top of real data)
-            (void)hipMemset(p, 0xFF, count * sizeof(T));
-            (void)hipDeviceSynchronize();
-        }
+        rgk_poison_fill(p, count * sizeof(T)); // RGK_POISON=1: 0xFF bytes (rgk_poison.h)
         return 0;
     }
     int upload(const T* src, size_t count) {

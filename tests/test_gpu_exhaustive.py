@@ -259,7 +259,9 @@ def test_device_built_tree_keeps_its_fingerprint(rd, scene, builder):
     recorded on the MI355X from the commit BEFORE the builder's pieces moved into rgk_tree.h, three builds per case; a refactor
     of the builder must leave them as they are.  The device build numbers its nodes with atomics: a case whose counters were
     not the same in all three builds has no "counters" entry (the file lists those cases under "unstable") and is held to the
-    three info numbers alone."""
+    three info numbers alone.  (Atomics, not a read of something unwritten: every scratch array of the build is written before
+    it is read -- DESIGN.md 16, "Written before read" -- and with the builder's scratch filled with 0xFF bytes the same three
+    builders give the info numbers and, for every ray, the answers they give on fresh memory: tests/test_gpu_memstate.py.)"""
     want = _fingerprints()[f"{scene}-{builder}"]
     info, counters = tree_fingerprint(rd, scene, builder)
     assert info == want["info"], (info, want["info"])

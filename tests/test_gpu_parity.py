@@ -404,9 +404,8 @@ def test_deep_tree_stack_overflow_variant(rd, oracle):
     check_visibility_disagreements(vg, vo, o, oo[:50000], oo[50000:100000], "test_deep_tree_stack_overflow_variant:visibility")
 
 
-def test_envmap_sky_float_texture(rd, oracle):
-    """Scene::GetSkyboxRay in envmap mode (scene.cpp:748-763): lat-long lookup with rotation into a float (HDR-style)
-    texture -- the kind BASELINE configs[3] names but the reference checkout does not ship (SURVEY F5)."""
+def envmap_sky_scene():
+    """A plane and a cube under a float (HDR-style) lat-long environment map with a few bright spots, rotated by 37 degrees."""
     rng = np.random.default_rng(11)
     sb = SceneBuilder()
     m = sb.new_material("grey", capi.BXDF_LTC_GGX_DIFFUSE)
@@ -419,6 +418,13 @@ def test_envmap_sky_float_texture(rd, oracle):
     hdr[20:24, 30:36] = (40.0, 35.0, 30.0)
     tex = sb.add_image_texture("sky", hdr)
     sb.sky.update(mode=capi.SKY_ENVMAP, tex=tex, intensity=0.9, rotate=37.0)
+    return sb
+
+
+def test_envmap_sky_float_texture(rd, oracle):
+    """Scene::GetSkyboxRay in envmap mode (scene.cpp:748-763): lat-long lookup with rotation into a float (HDR-style)
+    texture -- the kind BASELINE configs[3] names but the reference checkout does not ship (SURVEY F5)."""
+    sb = envmap_sky_scene()
     W, H = 160, 120
     cam = make_camera((2.5, 1.8, 3.0), (0, 0.4, 0), (0, 1, 0), fov=50, xres=W, yres=H)
     prm = make_params(W, H, 16, 4, clamp=50.0, russian=0.8)

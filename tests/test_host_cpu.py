@@ -25,6 +25,17 @@ def test_library_exports_every_symbol_the_header_declares(product_lib):
         assert getattr(product_lib, name) is not None
 
 
+def test_poisoned_byte_total_is_exported_and_zero_without_the_switch(product_lib):
+    """rgk_debug_poisoned_bytes: declared as uint64_t (void), in the export list, bound with a 64-bit result, and 0 in a process
+    without RGK_POISON (the call touches no device)."""
+    hdr = open(os.path.join(ROOT, "include", "rgk.h")).read()
+    assert re.search(r"uint64_t\s+rgk_debug_poisoned_bytes\s*\(\s*void\s*\)\s*;", hdr)
+    assert "rgk_debug_poisoned_bytes" in capi.EXPORTS
+    assert product_lib.rgk_debug_poisoned_bytes.restype is C.c_uint64 and product_lib.rgk_debug_poisoned_bytes.argtypes == []
+    if "RGK_POISON" not in os.environ:
+        assert product_lib.rgk_debug_poisoned_bytes() == 0
+
+
 def test_struct_layouts_match_the_header(tmp_path):
     """sizeof() of every struct, C compiler vs ctypes mirror."""
     src = tmp_path / "sz.c"
