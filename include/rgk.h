@@ -499,7 +499,8 @@ int rgk_denoise_device(rgk_scene *scene, uint32_t xres, uint32_t yres, const flo
  * the tuning key "time_post" is 1. *n: in, room in ms; out, entries the call had (those that fit are written).
  * which = 5: the temporal pair -- {the last rgk_temporal_reproject_device, the last rgk_temporal_blend_device}, one launch each;
  * two entries once either has run with "time_post" on, 0 ms for the one that has not.
- * which = 6: the last rgk_render_aov_chain[_device] -- pixel list + ray generation, then {walker, k_aov_hop} per hop 0 .. max_hops. */
+ * which = 6: the last rgk_render_aov_chain[_device] -- pixel list + ray generation, then {walker, k_aov_hop} per hop 0 .. max_hops.
+ * which = 7: the last rgk_upsample_device -- {k_us_prepare, k_us_gather}. */
 int rgk_scene_get_post_timing(const rgk_scene *scene, uint32_t which, double *ms, uint32_t *n);
 
 /* ---- noise estimate from two half-buffers and the variance-guided filter (DESIGN.md "Half-buffer noise estimate") ----
@@ -629,6 +630,54 @@ int rgk_temporal_blend_device(rgk_scene *scene, uint32_t xres, uint32_t yres, co
                               const float *d_albedo, const float *d_hist_rgb, const float *d_hist_len,
                               const rgk_temporal_params *params, float *d_out_hist_rgb /*3P*/, float *d_out_hist_len /*P*/,
                               float *d_out_rgb /*3P*/);
+
+/* ---- guided upsampling of a low-resolution render (DESIGN.md "Guided upsampling") ----
+ *
+ * The accumulator of a render on a low grid (xl x yl, cam_low) reconstructed on a full grid (xres x yres, cam), guided by the feature
+ * planes rgk_render_aov_device makes for the two cameras and re-modulated with the full grid's albedo.  The two cameras need not
+ * have the same view rectangle.  All pointers DEVICE pointers on the scene's GPU, planes row-major from the top row, P = xres * yres,
+ * Pl = xl * yl; whole frame; two launches on the scene's stream; blocking.  No output may be one of the inputs (or the other
+ * output).  Arguments are checked before the scene or the device is touched: every member of params (the ranges beside the members,
+ * all finite), xl, yl, xres, yres in 1 .. 65535, cam->xsize == xres, cam->ysize == yres, cam_low->xsize == xl, cam_low->ysize == yl.
+ * Not while a round is in flight on this scene.  It uses record planes of its own and no buffer, list or counter a round reads or
+ * writes; no scene data is read.  d_albedo and d_low_albedo may be NULL when demodulate == 0.  The lens of both cameras is ignored.
+ * Everything below is float32, only + - * / max min sqrt floor, no contraction, in the order written;
+ * a . b = (a.x * b.x + a.y * b.y) + a.z * b.z, len(a) = sqrt(a . a); sums over taps start at 0 and add the counted taps in tap order.
+ *
+ * Per low pixel q:
+ *   c_q = S_q / n_q (0 where n_q == 0), live_q = n_q > 0
+ *   per channel div_q = demodulate ? (a_q > 0 ? max(a_q, albedo_floor) : 1) : 1,  m_q = c_q / div_q
+ *   flat_q: all three normal components == 0 (a miss or a dropped vertex)
+ *   x_q = o_low + d_q * z_q, (o_low, d_q) the ray rgk_render_aov_device traces for q through cam_low
+ * Per full pixel p = (x, y):
+ *   1. (o, d) = the ray rgk_render_aov_device traces for p through cam; flat_p as above; x_p = o + d * z_p;
+ *      v = flat_p ? d : x_p - o_low      (a flat pixel is carried by direction, like sky in the reprojection)
+ *   2. into the low grid with the formulas of rgk_temporal_reproject_device, cam_low for cam_prev: N = cam_low->direction,
+ *      qd = v . N;  s = ((vs - o_low) . N) / qd;  w = (o_low + v * s) - vs;  a = (w . vx) / (vx . vx);  b = (w . vy) / (vy . vy);
+ *      fx = a * xl - 0.5f;  fy = b * yl - 0.5f.
+ *      If !(qd > 0), or unless fx > -2 && fx < xl + 1 && fy > -2 && fy < yl + 1 (false for NaN): out = 0, support = 0, end.
+ *   3. ix = (int)floor(fx), tx = fx - ix, likewise y.  A tap q COUNTS when it is inside the low frame, live_q, flat_q == flat_p and,
+ *      for a non-flat p,  n_p . n_q >= normal_cos  and  |(x_q - x_p) . n_p| <= plane_tol * len(x_p - o).
+ *   4. ring 1: taps (ix, iy), (ix+1, iy), (ix, iy+1), (ix+1, iy+1) with the weights (1-tx)*(1-ty), tx*(1-ty), (1-tx)*ty, tx*ty;
+ *      W = sum(w), A = sum(w * m_q).  If W > 0: m = A / W, support = 1.
+ *   5. else ring 2: the 16 taps ix-1 .. ix+2 x iy-1 .. iy+2 (dy outer, dx inner), the same counting rule,
+ *      w = 1 / (1 + ((fx - qx)^2 + (fy - qy)^2)).  If W > 0: m = A / W, support = 2.
+ *   6. else nearest: q0 = (min(max((int)floor(fx + 0.5f), 0), xl - 1), likewise y), out = c_q0 (plain: 0 when not live, not
+ *      demodulated, not re-modulated), support = 0, end.
+ *   7. out = m * div_p, div_p formed from the full-resolution albedo by the rule for div_q. */
+typedef struct rgk_upsample_params {
+    float plane_tol;     /* >= 0: a tap's point may be this far from the pixel's surface plane, as a share of the pixel's distance */
+    float normal_cos;    /* in [-1, 1]: the smallest n_p . n_q a tap may have */
+    uint32_t demodulate;
+    float albedo_floor;  /* >= 0: the floor on the divisor, as in rgk_temporal_params */
+} rgk_upsample_params;
+int rgk_upsample_device(rgk_scene *scene, uint32_t xres, uint32_t yres, const rgk_camera *cam,
+                        const float *d_albedo /*3P*/, const float *d_normal /*3P*/, const float *d_depth /*P*/,
+                        uint32_t xl, uint32_t yl, const rgk_camera *cam_low,
+                        const float *d_low_accum_rgb /*3Pl*/, const uint32_t *d_low_accum_count /*Pl*/,
+                        const float *d_low_albedo, const float *d_low_normal, const float *d_low_depth,
+                        const rgk_upsample_params *params,
+                        float *d_out_rgb /*3P*/, uint8_t *d_out_support /*P, may be NULL*/);
 
 /* The pinned transcendental functions of the path (include/rgk_libm.h) evaluated on the device, for the test that the GPU
  * and the CPU produce the same bits: fn 0 sin, 1 cos, 2 acos, 3 asin, 4 atan2(a[i], b[i]) (b may be NULL otherwise). */

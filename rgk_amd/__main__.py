@@ -37,6 +37,12 @@
                     them (depth: the length of the whole chain; albedo: times the surfaces' colours): --aov writes those planes
                     and, beside them, the suffix `hops` (the surfaces passed, in R, G and B), --denoise filters with them.  Not
                     with --temporal.  The plain output is unchanged
+  --upsample        needs -p: after every round that rewrites the output, also writes the output name with the suffix `upsampled` at
+                    the configuration's FULL resolution -- the quarter-resolution accumulator reconstructed on the full grid,
+                    guided by the normal and depth planes of both grids (one extra ray per full-resolution pixel, once): a pixel
+                    takes radiance only from quarter-resolution pixels on its own surface; scaled like the plain output.  With --denoise the upsampled image
+                    is filtered at full resolution; the `denoised` file stays the quarter-resolution one.  Not with --temporal,
+                    --noise, --until-noise, --adaptive, --aov-hops or -d.  Every other file is unchanged
 FILE is a .json or .rtc scene config.  One process drives one GPU; several GPUs: python -m torch.distributed.run ... bench.py.
 """
 import argparse
@@ -102,6 +108,7 @@ def main(argv=None):
     ap.add_argument("--temporal", action="store_true")
     ap.add_argument("--frames", type=int, default=None, help="with -r: stop after this many frames (default: all 501)")
     ap.add_argument("--aov-hops", type=int, default=None, metavar="K")
+    ap.add_argument("--upsample", action="store_true")
     args = ap.parse_args(argv)
     verbosity = max(0, 2 + args.v - args.q)
     say = lambda lvl, *a: print(*a) if verbosity >= lvl else None
@@ -122,6 +129,15 @@ def main(argv=None):
             print("ERROR: --aov-hops cannot be combined with --temporal.")
             return 1
     aov_hops = args.aov_hops or 0
+    if args.upsample:
+        if not args.preview:
+            print("ERROR: --upsample needs -p (--preview).")
+            return 1
+        clash = [name for name, on in (("--temporal", args.temporal), ("--noise", args.noise), ("--until-noise", args.until_noise is not None),
+                                       ("--adaptive", args.adaptive is not None), ("--aov-hops", args.aov_hops is not None), ("-d", args.debug is not None)) if on]
+        if clash:
+            print(f"ERROR: --upsample cannot be combined with {clash[0]}.")
+            return 1
     try:
         cfg = load_config(args.file)
     except ConfigFileException as e:
@@ -146,6 +162,7 @@ def main(argv=None):
         output_file = insert_file_suffix(output_file, "preview")
     if args.compare:
         output_file = insert_file_suffix(output_file, "cmp")  # main.cpp:196 (after the preview suffix, before the frame number)
+    full_res = (cfg.xres, cfg.yres)  # --upsample: the grid the preview is reconstructed on
     if args.preview:
         cfg.xres //= PREVIEW_DIMENSIONS_RATIO
         cfg.yres //= PREVIEW_DIMENSIONS_RATIO
@@ -177,6 +194,12 @@ def main(argv=None):
             open(out, "ab").close()  # claim the frame before rendering it (processes sharing the directory skip it)
             say(1, f"Rendering frame #{frame_no} of ~{int(time_length * fps)} ({format_percent(t / time_length * 100.0)})")
         camera = cfg.get_camera(t / time_length if args.rotate else 0.0)
+        upsample_to = None
+        if args.upsample:  # the frame's camera as the configuration has it before -p divides its sizes
+            low_res = (cfg.xres, cfg.yres)
+            cfg.xres, cfg.yres = full_res
+            upsample_to = (cfg.get_camera(t / time_length if args.rotate else 0.0),) + full_res
+            cfg.xres, cfg.yres = low_res
         try:
             drv = rd.RenderDriver(scene, cfg, camera, device=device, track_noise=track_noise,
                                   adaptive=capi.AdaptParams(args.until_noise, args.adaptive) if args.adaptive is not None else None, history=history,
@@ -219,6 +242,7 @@ def main(argv=None):
             drv.render_frame(rounds=max(0, cfg.render_rounds - drv.rounds_done) if not timed else None, output_file=out, checkpoint=ckpt,
                              aov_files={k: insert_file_suffix(out, k) for k in ("albedo", "normal", "depth") + (("hops",) if aov_hops > 0 else ())} if args.aov else None,
                              denoised_file=insert_file_suffix(out, "denoised") if args.denoise else None, temporal=args.temporal,
+                             **(dict(upsampled_file=insert_file_suffix(out, "upsampled"), upsample_to=upsample_to) if args.upsample else {}),
                              **(dict(until_noise=args.until_noise, noise_file=insert_file_suffix(out, "noise"),
                                      on_noise=lambda r, rel, n_live=None: say(1, f"Round {r}: " + (f"{n_live} live tiles, " if n_live is not None else "") +
                                                                                   f"relative noise {rel:.4g}")) if track_noise else {}))

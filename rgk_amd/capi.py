@@ -186,6 +186,32 @@ class TemporalParams(C.Structure):
         return self
 
 
+class UpsampleParams(C.Structure):
+    """rgk_upsample_params; the defaults are the shipped ones, the minimum of tools/upsample_sweep.py: plane_tol,
+    normal_cos (-1: the normal test is off -- bump-mapped normals differ between neighbours of one surface) and demodulate (0: the
+    low pixel's radiance is a box average over its footprint, its albedo the centre ray's, and dividing one by the other loses
+    more than the full-resolution albedo gives back) are measured; albedo_floor is the temporal one, not read while demodulate is 0."""
+    _fields_ = [("plane_tol", C.c_float), ("normal_cos", C.c_float), ("demodulate", C.c_uint32), ("albedo_floor", C.c_float)]
+
+    def __init__(self, plane_tol=0.05, normal_cos=-1.0, demodulate=0, albedo_floor=0.02):
+        super().__init__(plane_tol, normal_cos, demodulate, albedo_floor)
+
+    def check(self):
+        """The ranges the entry enforces, as a ValueError before anything is launched."""
+        import math
+        vals = {k: getattr(self, k) for k in ("plane_tol", "normal_cos", "albedo_floor")}
+        for k, v in vals.items():
+            if not math.isfinite(v):
+                raise ValueError(f"upsample parameter {k} must be finite, got {v}")
+        if not vals["plane_tol"] >= 0:
+            raise ValueError("plane_tol must be >= 0")
+        if not -1 <= vals["normal_cos"] <= 1:
+            raise ValueError("normal_cos must be in [-1, 1]")
+        if not vals["albedo_floor"] >= 0:
+            raise ValueError("albedo_floor must be >= 0")
+        return self
+
+
 # every symbol include/rgk.h declares (tests check the .so exports all of them)
 EXPORTS = ["rgk_last_error", "rgk_device_count", "rgk_scene_create", "rgk_scene_destroy",
            "rgk_scene_get_info", "rgk_scene_get_progress", "rgk_scene_set_tuning", "rgk_scene_refit", "rgk_generate_task_list", "rgk_camera_init", "rgk_render_round",
@@ -198,7 +224,7 @@ EXPORTS = ["rgk_last_error", "rgk_device_count", "rgk_scene_create", "rgk_scene_
            "rgk_render_aov_device", "rgk_render_aov", "rgk_denoise_device", "rgk_scene_get_post_timing",
            "rgk_noise_estimate_device", "rgk_denoise_variance_device", "rgk_adapt_select", "rgk_round_fold_device",
            "rgk_temporal_reproject_device", "rgk_temporal_blend_device",
-           "rgk_render_aov_chain_device", "rgk_render_aov_chain", "rgk_debug_poisoned_bytes"]
+           "rgk_render_aov_chain_device", "rgk_render_aov_chain", "rgk_debug_poisoned_bytes", "rgk_upsample_device"]
 AOV_MAX_HOPS = 8  # RGK_AOV_MAX_HOPS
 
 _p = C.POINTER
@@ -272,6 +298,8 @@ def _bind(lib):
     lib.rgk_temporal_reproject_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, _p(Camera), _p(Camera)] + [C.c_void_p] * 8 + [
         _p(TemporalParams), C.c_void_p, C.c_void_p]
     lib.rgk_temporal_blend_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32] + [C.c_void_p] * 5 + [_p(TemporalParams)] + [C.c_void_p] * 3
+    lib.rgk_upsample_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, _p(Camera)] + [C.c_void_p] * 3 + [C.c_uint32, C.c_uint32, _p(Camera)] + [
+        C.c_void_p] * 5 + [_p(UpsampleParams), C.c_void_p, C.c_void_p]
     lib.rgk_scene_get_post_timing.argtypes =[C.c_void_p, C.c_uint32, _p(C.c_double), _p(C.c_uint32)]
     lib.rgk_float_to_half.argtypes = [C.c_float]
     lib.rgk_float_to_half.restype = C.c_uint16

@@ -152,3 +152,10 @@ void rgk_launch_tp_reproject(hipStream_t st, const DevScene& sc, uint32_t n_tria
                              const float* hist_rgb_prev, const float* hist_len_prev, float plane_tol, float normal_cos, float* hist_rgb, float* hist_len);
 void rgk_launch_tp_blend(hipStream_t st, size_t P, const float* accum_rgb, const uint32_t* accum_count, const float* albedo, const float* hist_rgb, const float* hist_len,
                          float alpha_min, float max_len, uint32_t demodulate, float albedo_floor, float* out_hist_rgb, float* out_hist_len, float* out_rgb);
+// guided upsampling: both cameras pinhole copies; rec: 3 * xl * yl records (prepare writes them, gather reads them); albedo planes may
+// be NULL without demodulation, out_support may be NULL
+void rgk_launch_us_prepare(hipStream_t st, const DevCamera& low, uint32_t xl, uint32_t yl, const float* accum_rgb, const uint32_t* accum_count, const float* albedo,
+                           const float* normal, const float* depth, uint32_t demodulate, float albedo_floor, float4* rec);
+void rgk_launch_us_gather(hipStream_t st, const DevCamera& cam, const DevCamera& low, uint32_t xres, uint32_t yres, uint32_t xl, uint32_t yl, const float* albedo,
+                          const float* normal, const float* depth, const float* low_rgb, const uint32_t* low_count, const float4* rec, float plane_tol, float normal_cos,
+                          uint32_t demodulate, float albedo_floor, float* out_rgb, uint8_t* out_support);

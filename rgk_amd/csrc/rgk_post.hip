@@ -17,6 +17,8 @@
 //   k_tp_blend               accumulator + reprojected history -> the next frame's history and the image to filter
 //   k_aov_hop                one hop of the feature planes that follow mirrors and glass: a terminal vertex, miss or dropped vertex
 //                            -> the planes, a delta vertex -> the continuation ray, compacted into the next hop's queue
+//   k_us_prepare             a low-resolution accumulator and its feature planes -> 16-byte tap records {m.rgb, flags}, {x_q}, {n_q}
+//   k_us_gather              the full grid's pixels projected into the low grid: ring 1 (bilinear), ring 2 (4 x 4), nearest
 // (tests/noise_ref.py's k_nz_prepare, k_nz_prefilter and k_nz_atrous are k_dn_prepare<true> and k_dn_atrous<VarianceMean / VarianceGuided>)
 //
 // The traversal between raygen and gather is the round's own k_trace_closest (rgk_launch_trace_closest): no second walker.
@@ -659,4 +661,140 @@ void rgk_launch_aov_hop(hipStream_t st, const DevScene& sc, float bumpmap_scale,
                         float* normal, float* depth, int32_t* tri, uint8_t* hops) {
     k_aov_hop<0><<<rgk_aov_hop_grid(n), 256, RGK_LDS_SHADE_BYTES, st>>>(sc, bumpmap_scale, xres, pix_xy, n, hop, max_hops, rayA, rayB, hit, state, nextA, nextB, counters, albedo,
                                                                         normal, depth, tri, hops);
+}
+
+// ------------------------------------------------------------------ guided upsampling (rgk.h rgk_upsample_device)
+// A low-resolution accumulator reconstructed on a finer grid, guided by the feature planes of both grids; every formula in rgk.h's
+// order, float32, nothing contracted (tests/upsample_ref.py gives the same bits).  (Templates for the reason k_tp_reproject is one.)
+//   k_us_prepare   a lane per LOW pixel: three 16-byte records in three planes of `rec` -- [q] {m.rgb, flags: 1 live, 2 flat},
+//                  [Pl + q] {x_q.xyz, 0}, [2 Pl + q] {n_q.xyz, 0} -- so a tap is up to three dwordx4 loads (the flags decide whether
+//                  the other two are needed) and x_q, its camera ray included, is formed once per low pixel instead of once per tap.
+//                  Reads 32 B (44 with the albedo), writes 48 B per low pixel.
+//   k_us_gather    a lane per FULL pixel, a workgroup per RGK_POST_BX x RGK_POST_BY tile: at ratio 4 its ring-1 taps lie in a 9 x 3
+//                  patch of the low grid, ring 2 in 11 x 5, i.e. a few cache lines per record plane.  Reads its own 16 B (28 with
+//                  the albedo), writes 12 B + 1 B.  Ring 2 is a branch: a wave none of whose lanes needs it skips it.
+constexpr uint32_t RGK_US_LIVE = 1u, RGK_US_FLAT = 2u;
+
+template <int = 0>
+__global__ __launch_bounds__(RGK_POST_BLOCK) void k_us_prepare(const DevCamera low, int xl, int yl, const float* __restrict__ accum_rgb,
+                                                                const uint32_t* __restrict__ accum_count, const float* __restrict__ albedo,
+                                                                const float* __restrict__ normal, const float* __restrict__ depth, uint32_t demodulate,
+                                                                float albedo_floor, float4* __restrict__ rec) {
+    const size_t Pl = (size_t)xl * (size_t)yl;
+    const size_t q = (size_t)blockIdx.x * RGK_POST_BLOCK + threadIdx.x;
+    if (q >= Pl) return;
+    const int y = (int)(q / (size_t)xl), x = (int)(q - (size_t)y * (size_t)xl);
+    const uint32_t n = accum_count[q];
+    f3 c = mk3(0.f, 0.f, 0.f);
+    if (n) c = ld3(accum_rgb, q) / (float)n;
+    f3 div = mk3(1.f, 1.f, 1.f);
+    if (demodulate) div = mk3(demod_div(albedo[3 * q], albedo_floor), demod_div(albedo[3 * q + 1], albedo_floor), demod_div(albedo[3 * q + 2], albedo_floor));
+    const f3 nq = ld3(normal, q);
+    f3 o, d; // (lens_size == 0: the host passes a pinhole copy)
+    camera_ray(low, x, y, xl, yl, make_float2(0.5f, 0.5f), make_float2(0.f, 0.f), o, d);
+    const f3 xq = o + d * depth[q];
+    const uint32_t flags = (n ? RGK_US_LIVE : 0u) | (is_zero3(nq) ? RGK_US_FLAT : 0u);
+    rec[q] = make_float4(c.x / div.x, c.y / div.y, c.z / div.z, __uint_as_float(flags));
+    rec[Pl + q] = make_float4(xq.x, xq.y, xq.z, 0.f);
+    rec[2 * Pl + q] = make_float4(nq.x, nq.y, nq.z, 0.f);
+}
+
+// One tap of either ring: adds w * m_q to (A, W) when q counts.
+struct UsPixel { f3 xp, np; float tol, normal_cos; bool flat; };
+__device__ __forceinline__ void us_tap(const UsPixel& px, const float4* __restrict__ rec, size_t Pl, int xl, int yl, int qx, int qy, float w, f3& A, float& W) {
+    if (qx < 0 || qx >= xl || qy < 0 || qy >= yl) return;
+    const size_t qi = (size_t)qy * (size_t)xl + (size_t)qx;
+    const float4 r0 = rec[qi];
+    const uint32_t flags = __float_as_uint(r0.w);
+    if (!(flags & RGK_US_LIVE) || ((flags & RGK_US_FLAT) != 0u) != px.flat) return;
+    if (!px.flat) {
+        const float4 rn = rec[2 * Pl + qi];
+        if (!(dot3(px.np, mk3(rn.x, rn.y, rn.z)) >= px.normal_cos)) return;
+        const float4 rx = rec[Pl + qi];
+        if (!(fabsf(dot3(mk3(rx.x, rx.y, rx.z) - px.xp, px.np)) <= px.tol)) return;
+    }
+    W = W + w;
+    A = mk3(A.x + w * r0.x, A.y + w * r0.y, A.z + w * r0.z);
+}
+
+template <int = 0>
+__global__ __launch_bounds__(RGK_POST_BX * RGK_POST_BY) void k_us_gather(const DevCamera cam, const DevCamera low, int xres, int yres, int xl, int yl,
+                                                                         const float* __restrict__ albedo, const float* __restrict__ normal,
+                                                                         const float* __restrict__ depth, const float* __restrict__ low_rgb,
+                                                                         const uint32_t* __restrict__ low_count, const float4* __restrict__ rec, float plane_tol,
+                                                                         float normal_cos, uint32_t demodulate, float albedo_floor, float* __restrict__ out_rgb,
+                                                                         uint8_t* __restrict__ out_support) {
+    const int x = (int)(blockIdx.x * RGK_POST_BX + threadIdx.x % RGK_POST_BX), y = (int)(blockIdx.y * RGK_POST_BY + threadIdx.x / RGK_POST_BX);
+    if (x >= xres || y >= yres) return;
+    const size_t p = (size_t)y * (size_t)xres + (size_t)x, Pl = (size_t)xl * (size_t)yl;
+    f3 o, d; // (lens_size == 0 in both cameras: the host passes pinhole copies)
+    camera_ray(cam, x, y, xres, yres, make_float2(0.5f, 0.5f), make_float2(0.f, 0.f), o, d);
+    UsPixel px;
+    px.np = ld3(normal, p);
+    px.flat = is_zero3(px.np);
+    px.xp = o + d * depth[p];
+    px.normal_cos = normal_cos;
+    const f3 o_low = mk3(low.origin[0], low.origin[1], low.origin[2]);
+    const f3 v = px.flat ? d : px.xp - o_low;
+    const f3 N = mk3(low.direction[0], low.direction[1], low.direction[2]);
+    const float qd = dot3(v, N);
+    f3 out = mk3(0.f, 0.f, 0.f);
+    uint32_t support = 0;
+    if (qd > 0.0f) {
+        const f3 vs = mk3(low.viewscreen[0], low.viewscreen[1], low.viewscreen[2]);
+        const f3 vx = mk3(low.viewscreen_x[0], low.viewscreen_x[1], low.viewscreen_x[2]);
+        const f3 vy = mk3(low.viewscreen_y[0], low.viewscreen_y[1], low.viewscreen_y[2]);
+        const float s = dot3(vs - o_low, N) / qd;
+        const f3 w = (o_low + v * s) - vs;
+        const float a = dot3(w, vx) / dot3(vx, vx), b = dot3(w, vy) / dot3(vy, vy);
+        const float fx = a * (float)xl - 0.5f, fy = b * (float)yl - 0.5f;
+        if (fx > -2.0f && fx < (float)(xl + 1) && fy > -2.0f && fy < (float)(yl + 1)) { // (false for NaN)
+            const float flx = floorf(fx), fly = floorf(fy);
+            const int ix = (int)flx, iy = (int)fly;
+            const float tx = fx - flx, ty = fy - fly;
+            px.tol = plane_tol * len3(px.xp - o);
+            f3 A = mk3(0.f, 0.f, 0.f);
+            float W = 0.f;
+            const float wt[4] = {(1.0f - tx) * (1.0f - ty), tx * (1.0f - ty), (1.0f - tx) * ty, tx * ty};
+#pragma unroll
+            for (int k = 0; k < 4; k++) us_tap(px, rec, Pl, xl, yl, ix + (k & 1), iy + (k >> 1), wt[k], A, W);
+            support = 1;
+            if (!(W > 0.0f)) { // ring 2: only where ring 1 found nothing
+                A = mk3(0.f, 0.f, 0.f);
+                W = 0.f;
+                for (int dy = -1; dy <= 2; dy++)
+                    for (int dx = -1; dx <= 2; dx++) {
+                        const int qx = ix + dx, qy = iy + dy;
+                        const float ex = fx - (float)qx, ey = fy - (float)qy;
+                        us_tap(px, rec, Pl, xl, yl, qx, qy, 1.0f / (1.0f + (ex * ex + ey * ey)), A, W);
+                    }
+                support = 2;
+            }
+            if (W > 0.0f) {
+                f3 div = mk3(1.f, 1.f, 1.f);
+                if (demodulate) div = mk3(demod_div(albedo[3 * p], albedo_floor), demod_div(albedo[3 * p + 1], albedo_floor), demod_div(albedo[3 * p + 2], albedo_floor));
+                out = mk3((A.x / W) * div.x, (A.y / W) * div.y, (A.z / W) * div.z);
+            } else { // nearest: the plain image of the closest low pixel
+                support = 0;
+                const int nx = min(max((int)floorf(fx + 0.5f), 0), xl - 1), ny = min(max((int)floorf(fy + 0.5f), 0), yl - 1);
+                const size_t q0 = (size_t)ny * (size_t)xl + (size_t)nx;
+                const uint32_t n0 = low_count[q0];
+                if (n0) out = ld3(low_rgb, q0) / (float)n0;
+            }
+        }
+    }
+    out_rgb[3 * p] = out.x; out_rgb[3 * p + 1] = out.y; out_rgb[3 * p + 2] = out.z;
+    if (out_support) out_support[p] = (uint8_t)support;
+}
+
+void rgk_launch_us_prepare(hipStream_t st, const DevCamera& low, uint32_t xl, uint32_t yl, const float* accum_rgb, const uint32_t* accum_count, const float* albedo,
+                           const float* normal, const float* depth, uint32_t demodulate, float albedo_floor, float4* rec) {
+    k_us_prepare<0><<<rgk_post_pixel_grid((size_t)xl * yl), RGK_POST_BLOCK, 0, st>>>(low, (int)xl, (int)yl, accum_rgb, accum_count, albedo, normal, depth, demodulate, albedo_floor, rec);
+}
+void rgk_launch_us_gather(hipStream_t st, const DevCamera& cam, const DevCamera& low, uint32_t xres, uint32_t yres, uint32_t xl, uint32_t yl, const float* albedo,
+                          const float* normal, const float* depth, const float* low_rgb, const uint32_t* low_count, const float4* rec, float plane_tol, float normal_cos,
+                          uint32_t demodulate, float albedo_floor, float* out_rgb, uint8_t* out_support) {
+    const RgkGrid2 g = rgk_post_filter_grid(xres, yres);
+    k_us_gather<0><<<dim3(g.x, g.y), RGK_POST_BX * RGK_POST_BY, 0, st>>>(cam, low, (int)xres, (int)yres, (int)xl, (int)yl, albedo, normal, depth, low_rgb, low_count, rec,
+                                                                         plane_tol, normal_cos, demodulate, albedo_floor, out_rgb, out_support);
 }

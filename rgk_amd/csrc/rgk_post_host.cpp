@@ -1,5 +1,5 @@
-// The post-processing entries: feature buffers, both denoisers, the noise estimate, tile selection, the round fold and temporal reuse
-// (kernels: rgk_post.hip).
+// The post-processing entries: feature buffers, both denoisers, the noise estimate, tile selection, the round fold, temporal reuse and
+// guided upsampling (kernels: rgk_post.hip).
 #include <algorithm>
 #include <cmath>
 
@@ -367,6 +367,43 @@ int rgk_temporal_blend_device(rgk_scene* s, uint32_t xres, uint32_t yres, const 
     return temporal_call(s, "rgk_temporal_blend_device", 1, [&](hipStream_t st) {
         rgk_launch_tp_blend(st, (size_t)xres * yres, d_accum_rgb, d_accum_count, d_albedo, d_hist_rgb, d_hist_len, p.alpha_min, p.max_len, p.demodulate ? 1u : 0u,
                             p.albedo_floor, d_out_hist_rgb, d_out_hist_len, d_out_rgb);
+    });
+}
+
+int rgk_upsample_device(rgk_scene* s, uint32_t xres, uint32_t yres, const rgk_camera* cam, const float* d_albedo, const float* d_normal, const float* d_depth,
+                        uint32_t xl, uint32_t yl, const rgk_camera* cam_low, const float* d_low_accum_rgb, const uint32_t* d_low_accum_count, const float* d_low_albedo,
+                        const float* d_low_normal, const float* d_low_depth, const rgk_upsample_params* up, float* d_out_rgb, uint8_t* d_out_support) {
+    // (every check before the scene or the device is touched)
+    if (!s || !cam || !cam_low || !d_normal || !d_depth || !d_low_accum_rgb || !d_low_accum_count || !d_low_normal || !d_low_depth || !up || !d_out_rgb)
+        return fail(RGK_ERR_INVALID, "null argument");
+    const float all[3] = {up->plane_tol, up->normal_cos, up->albedo_floor};
+    for (float v : all)
+        if (!std::isfinite(v)) return fail(RGK_ERR_INVALID, "upsample parameters must be finite");
+    if (!(up->plane_tol >= 0.0f)) return fail(RGK_ERR_INVALID, "plane_tol must be >= 0");
+    if (!(up->normal_cos >= -1.0f && up->normal_cos <= 1.0f)) return fail(RGK_ERR_INVALID, "normal_cos must be in [-1, 1]");
+    if (!(up->albedo_floor >= 0.0f)) return fail(RGK_ERR_INVALID, "albedo_floor must be >= 0");
+    if (up->demodulate && (!d_albedo || !d_low_albedo)) return fail(RGK_ERR_INVALID, "demodulate without both albedo planes");
+    int rc;
+    if ((rc = check_frame_size(xres, yres)) || (rc = check_frame_size(xl, yl))) return rc;
+    if (cam->xsize != (int32_t)xres || cam->ysize != (int32_t)yres || cam_low->xsize != (int32_t)xl || cam_low->ysize != (int32_t)yl)
+        return fail(RGK_ERR_INVALID, "a camera's xsize / ysize is not its grid's resolution");
+    const void* ins[8] = {d_albedo, d_normal, d_depth, d_low_accum_rgb, d_low_accum_count, d_low_albedo, d_low_normal, d_low_depth};
+    const void* outs[2] = {d_out_rgb, d_out_support};
+    if ((rc = check_outputs_apart(ins, 8, outs, d_out_support ? 2 : 1))) return rc;
+    DevCamera full, low;
+    make_camera(cam, full);
+    make_camera(cam_low, low);
+    full.lens_size = low.lens_size = 0.0f; // the feature planes' rays: from the cameras' origins
+    const rgk_upsample_params p = *up;
+    const uint32_t demod = p.demodulate ? 1u : 0u;
+    return post_call(s, "rgk_upsample_device", POST_UPSAMPLE, true, [&](PostTimer& tm) -> int {
+        // The record planes are the entry's own (the library's allocation path: RGK_POISON covers them); nothing a round reads or writes.
+        if ((rc = s->us_rec.alloc(3 * (size_t)xl * yl)) || (rc = tm.mark())) return rc;
+        rgk_launch_us_prepare(s->stream, low, xl, yl, d_low_accum_rgb, d_low_accum_count, d_low_albedo, d_low_normal, d_low_depth, demod, p.albedo_floor, s->us_rec.p);
+        if ((rc = tm.mark())) return rc;
+        rgk_launch_us_gather(s->stream, full, low, xres, yres, xl, yl, d_albedo, d_normal, d_depth, d_low_accum_rgb, d_low_accum_count, s->us_rec.p, p.plane_tol,
+                             p.normal_cos, demod, p.albedo_floor, d_out_rgb, d_out_support);
+        return tm.mark();
     });
 }
 

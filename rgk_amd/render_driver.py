@@ -213,10 +213,22 @@ class Scene:
         capi.check(self.lib, self.lib.rgk_temporal_blend_device(self.h, xres, yres, d_accum_rgb, d_accum_count, d_albedo, d_hist_rgb, d_hist_len,
                                                                 C.byref(params), d_out_hist_rgb, d_out_hist_len, d_out_rgb))
 
+    def upsample_device(self, xres, yres, cam, d_albedo, d_normal, d_depth, xl, yl, cam_low, d_low_accum_rgb, d_low_accum_count, d_low_albedo,
+                        d_low_normal, d_low_depth, params, d_out_rgb, d_out_support=None):
+        """rgk_upsample_device: a low-resolution accumulator (xl x yl, cam_low) reconstructed on the xres x yres grid of `cam`, guided
+        by the feature planes of both grids; DEVICE pointers (ints) on the scene's GPU, params a capi.UpsampleParams (its ranges
+        are checked here first: ValueError).  The albedo planes may be None without demodulation, d_out_support (P bytes: 1 ring 1,
+        2 ring 2, 0 nearest or outside) too."""
+        params.check()
+        capi.check(self.lib, self.lib.rgk_upsample_device(self.h, xres, yres, C.byref(cam), d_albedo, d_normal, d_depth, xl, yl, C.byref(cam_low),
+                                                          d_low_accum_rgb, d_low_accum_count, d_low_albedo, d_low_normal, d_low_depth, C.byref(params),
+                                                          d_out_rgb, d_out_support))
+
     def post_timing(self, which):
         """HIP-event times (ms) of the launches of the last feature pass (0) / denoise call (1) / variance-guided denoise call (2) /
         noise estimate (3) / round fold (4: the copy of its tile list, the fold) / temporal pair (5: reproject, blend) /
-        followed feature pass (6: list + ray generation, then walker and k_aov_hop per hop); set_tuning(time_post=1) first."""
+        followed feature pass (6: list + ray generation, then walker and k_aov_hop per hop) / upsample call (7: prepare, gather);
+        set_tuning(time_post=1) first."""
         ms, n = (C.c_double * 32)(), C.c_uint32(32)
         capi.check(self.lib, self.lib.rgk_scene_get_post_timing(self.h, which, ms, C.byref(n)))
         return list(ms[:min(n.value, 32)])
@@ -657,6 +669,54 @@ class RenderDriver:
         hist.share = share
         return filtered
 
+    def default_upsample_params(self):
+        """The shipped defaults of the guided upsampler (capi.UpsampleParams)."""
+        return capi.UpsampleParams()
+
+    def upsample(self, camera, xres, yres, params=None, denoise=None):
+        """The current accumulator -- this driver's grid is the LOW side -- reconstructed on the xres x yres grid of `camera`
+        (rgk_upsample_device), guided by this driver's feature planes and those of (camera, xres, yres), which are rendered once and
+        kept: (rgb (yres, xres, 3) float32, support (yres, xres) uint8) tensors on the device; not normalised, the accumulator is not
+        changed.  support: 1 where the four bilinear taps served, 2 where the 4 x 4 ring did, 0 where the pixel has the nearest low
+        pixel's plain colour.  denoise (a capi.DenoiseParams, or True for the shipped ones): rgb then goes through the guided a-trous filter with the full
+        grid's planes and sample counts of 1 (rgk_denoise_device), as denoise_temporal's blend does.  Root rank only."""
+        import torch
+        if self.rank != 0:
+            return None
+        if self.aov_hops > 0:
+            raise ValueError("upsample cannot be combined with aov_hops > 0: both grids are tested against first-hit geometry")
+        params = (params or self.default_upsample_params()).check()
+        low = self.render_aov()
+        key = (bytes(camera), int(xres), int(yres))
+        if getattr(self, "_up_key", None) != key:
+            prm = capi.Params.from_buffer_copy(self.params)
+            prm.xres, prm.yres = xres, yres
+            full = {"albedo": torch.empty((yres, xres, 3), dtype=torch.float32, device=self.device),
+                    "normal": torch.empty((yres, xres, 3), dtype=torch.float32, device=self.device),
+                    "depth": torch.empty((yres, xres), dtype=torch.float32, device=self.device)}
+            torch.cuda.current_stream(self.device).synchronize()
+            self.scene.render_aov_device(camera, prm, generate_task_list(xres, yres, SEEDSTART, 0), full["albedo"].data_ptr(), full["normal"].data_ptr(),
+                                         full["depth"].data_ptr(), None)
+            self._up_key, self._up_aov = key, full
+        full = self._up_aov
+        out = torch.empty((yres, xres, 3), dtype=torch.float32, device=self.device)
+        support = torch.empty((yres, xres), dtype=torch.uint8, device=self.device)
+        torch.cuda.current_stream(self.device).synchronize()
+        self.scene.upsample_device(xres, yres, camera, full["albedo"].data_ptr(), full["normal"].data_ptr(), full["depth"].data_ptr(),
+                                   self.cfg.xres, self.cfg.yres, self.camera, self.total_ob.data.data_ptr(), self.total_ob.count.data_ptr(),
+                                   low["albedo"].data_ptr(), low["normal"].data_ptr(), low["depth"].data_ptr(), params, out.data_ptr(), support.data_ptr())
+        if denoise is True:  # the shipped defaults, sigma_color from the upsampled image as default_denoise_params takes it from the accumulator's
+            level = float(out.max(dim=-1).values.double().mean())
+            denoise = capi.DenoiseParams(sigma_color=DENOISE_SIGMA_K * level if level > 0 else 1.0)
+        if denoise is not None and denoise is not False:
+            ones = torch.ones((yres, xres), dtype=torch.int32, device=self.device)
+            filtered = torch.empty_like(out)
+            torch.cuda.current_stream(self.device).synchronize()
+            self.scene.denoise_device(xres, yres, out.data_ptr(), ones.data_ptr(), full["albedo"].data_ptr(), full["normal"].data_ptr(), full["depth"].data_ptr(),
+                                      denoise, filtered.data_ptr())
+            out = filtered
+        return out, support
+
     def save_checkpoint(self, path):
         """Raw-accumulator checkpoint (rgk_accum_save): accumulator + rounds done + the running task counter.  With track_noise the
         half-buffer goes beside it as `<path>.half`, same format, same tag."""
@@ -715,7 +775,7 @@ class RenderDriver:
         return yes
 
     def render_frame(self, rounds=None, minutes=None, output_file=None, checkpoint=None, aov_files=None, denoised_file=None,
-                     until_noise=None, noise_file=None, on_noise=None, temporal=False):
+                     until_noise=None, noise_file=None, on_noise=None, temporal=False, upsampled_file=None, upsample_to=None):
         """RenderFrame: Rounds mode (render_driver.cpp:229-235) or Timed mode (:237-247); with `output_file` the
         normalised image is rewritten after every round, as the reference does (rank 0 only).
         aov_files: {"albedo" / "normal" / "depth" / "hops": path} -- the feature planes, written once (depth and hops replicated to
@@ -730,7 +790,12 @@ class RenderDriver:
         The rule keeps no state, so a frame resumed from a checkpoint goes on with the tiles the interrupted one would have rendered.
         temporal (needs a driver with a history, and denoised_file): after the frame's LAST round denoised_file is rewritten once more,
         from denoise_temporal(), which also commits the history for the next frame; the rewrites after earlier rounds are the
-        single-frame filter's as without it."""
+        single-frame filter's as without it.
+        upsampled_file with upsample_to = (camera, xres, yres): after every round that rewrites output_file, upsample() to that grid,
+        scaled like output_file; filtered with the shipped denoise defaults when there is a denoised_file (which itself stays this
+        driver's own resolution).  Not with noise tracking, a history or aov_hops."""
+        if upsampled_file and (upsample_to is None or not output_file or self.track_noise or self.history is not None or self.aov_hops > 0):
+            raise ValueError("upsampled_file needs upsample_to=(camera, xres, yres) and an output_file, on a driver without track_noise, history or aov_hops")
         if temporal and (self.history is None or not denoised_file):
             raise ValueError("temporal=True needs a driver made with history=TemporalHistory() and a denoised_file")
         if (until_noise is not None or noise_file or on_noise) and not self.track_noise:
@@ -766,6 +831,8 @@ class RenderDriver:
                         write_exr(noise_file, (var.sqrt() * val).unsqueeze(-1).expand(-1, -1, 3).cpu().numpy())
                 elif denoised_file:
                     write_exr(denoised_file, (self.denoise() * val).cpu().numpy())
+                if upsampled_file:
+                    write_exr(upsampled_file, (self.upsample(*upsample_to, denoise=True if denoised_file else None)[0] * val).cpu().numpy())
             if checkpoint and self.rank == 0:
                 self.save_checkpoint(checkpoint)
             nz = self.noise() if on_noise or until_noise is not None else None
