@@ -1,10 +1,12 @@
-// Hand-written HIP kernels for gfx950 (MI355X): the wavefront path-tracing pipeline.  This file is the one translation unit: the
-// kernels live in the headers below, one per concern, and the launch layer (host) follows them in the same order.
+// Hand-written HIP kernels for gfx950 (MI355X): the wavefront path-tracing pipeline.  The kernels live in the headers below, one per
+// concern, and the launch layer (host) follows them in the same order.  This translation unit instantiates all of them but k_shade
+// and k_last_vertex: those two are rgk_shade_kernels.hip's, which is built with flags of its own (rgk_amd/build.py SOURCE_FLAGS).
 //
 //   rgk_trace.h          k_trace_camera  K1+K2  RenderPixel ray generation + FindIntersectKdOtherThan  reference src/path_tracer.cpp:53-61, src/camera.cpp:32-46
 //                        k_trace_closest K2  FindIntersectKdOtherThan  reference src/scene_intersect.cpp:211-327 + src/primitives.cpp:75-166
 //                        k_trace_shadow[_first][_cl], k_trace_shadow_jobs  K5  Scene::Visibility + accumulate  reference src/scene.cpp:670-673, src/path_tracer.cpp:431,455-457
-//   rgk_shade.h          k_shade  K3/K4/K6/K7  GeneratePath body + NEE + compaction  reference src/path_tracer.cpp:134-300,427-460,485-496;
+//   rgk_shade.h          k_shade  K3/K4/K6/K7  GeneratePath body + NEE + compaction  reference src/path_tracer.cpp:134-300,427-460,485-496
+//                        (launched from rgk_shade_kernels.hip);
 //                        the queue records, the compaction and the path step that k_shade_light shares with it;
 //                        k_last_vertex  the last bounce of a unidirectional pass: k_shade's last vertex in two phases (ring: rgk_ring.h)
 //   rgk_bdpt.h           k_raygen_light, k_list_hits, k_shade_light, k_connect  K8  the bidirectional half (reverse > 0)
@@ -14,7 +16,7 @@
 //                        k_libm_eval: the unit-level entries of rgk_probe.cpp; no round launches them
 //   rgk_entry.h          k_entry_points, k_group_trange_wave, k_entry_points_light  where a pixel group's camera rays / first shadow rays
 //                        start in the tree (no reference counterpart: work shared by the rays of a group)
-//   here                 k_stage_mark, beside its launcher; at the end of the file the launcher that instantiates k_last_vertex
+//   here                 k_stage_mark, beside its launcher
 // The order of the includes, and of the launchers that instantiate kernel templates, is the order of the kernels in the assembly:
 // a kernel's labels carry its number in the file, so a reordering changes the text of every kernel behind it
 // (tools/device_code_diff.sh, profiles/shade_pieces_device_code.txt).
@@ -98,32 +100,8 @@ void rgk_launch_trace_shadow(hipStream_t st, const DevScene& sc, const RgkTraceC
 }
 
 // ------------------------------------------------------------------ rgk_shade.h
-// (k_last_vertex is instantiated at the end of this file -- its place in the assembly, behind every kernel that was there before it)
-static void launch_last_vertex(hipStream_t st, const DevScene& sc, const PassParams& pp, uint32_t bounce, const float4* rayA, const float4* rayB, const float4* hit,
-                               const float4* thr, float4* tot, float4* shA, float4* shB, float4* shC, uint32_t* counters, uint32_t bound, bool const_light);
-void rgk_launch_shade(hipStream_t st, const DevScene& sc, const DevCamera& cam, const PassParams& pp, uint32_t bounce, const float4* rayA,
-                      const float4* rayB, const float4* hit, float4* thr, float4* tot, float4* nextA, float4* nextB, float4* shA,
-                      float4* shB, float4* shC, uint32_t* counters, uint32_t bound, bool bdpt, bool const_light, bool last_vertex) {
-    const RgkGridPair g = rgk_shade_grids(bounce, bound);
-    // every vertex of the launch is its path's last: the fast launch is k_last_vertex, the GENERIC one k_shade on the list it fills
-    const bool lv = last_vertex && rgk_last_bounce(bounce, pp.depth, bdpt);
-    // the second launch shades the vertices the first one listed (materials on the generic BxDF route); it returns at once when there are none
-    auto pair = [&](auto first, auto bd, auto cl) {
-        constexpr bool FIRST = decltype(first)::value, BDPT = decltype(bd)::value, CL = decltype(cl)::value;
-        if (!lv) k_shade<false, FIRST, BDPT, CL><<<g.fast, g.block, RGK_LDS_SHADE_BYTES, st>>>(sc, cam, pp, bounce, rayA, rayB, hit, thr, tot, nextA, nextB, shA, shB, shC, counters);
-        else launch_last_vertex(st, sc, pp, bounce, rayA, rayB, hit, thr, tot, shA, shB, shC, counters, bound, CL);
-        k_shade<true, FIRST, BDPT, CL><<<g.generic, g.block, RGK_LDS_SHADE_BYTES, st>>>(sc, cam, pp, bounce, rayA, rayB, hit, thr, tot, nextA, nextB, shA, shB, shC, counters);
-    };
-    constexpr std::true_type T{}; constexpr std::false_type F{};
-    switch ((bounce == 0 ? 4 : 0) | (bdpt ? 2 : (const_light ? 1 : 0))) { // (FIRST, BDPT, CL): a bidirectional round never takes the constant-light route
-    case 4 | 2: pair(T, T, F); break;
-    case 2: pair(F, T, F); break;
-    case 4 | 1: pair(T, F, T); break;
-    case 1: pair(F, F, T); break;
-    case 4: pair(T, F, F); break;
-    default: pair(F, F, F); break;
-    }
-}
+// (k_shade and k_last_vertex are instantiated in rgk_shade_kernels.hip, a translation unit with compiler flags of its own; what this
+// file takes from rgk_shade.h is the pieces that rgk_bdpt.h and rgk_probe_kernels.h share with them)
 
 // ------------------------------------------------------------------ rgk_bdpt.h
 void rgk_launch_raygen_light(hipStream_t st, const DevScene& sc, const DevCamera& cam, const PassParams& pp, float4* rayA, float4* rayB,
@@ -208,12 +186,4 @@ void rgk_launch_group_trange(hipStream_t st, const PassParams& pp, const float4*
 void rgk_launch_light_entry_points(hipStream_t st, const DevScene& sc, const DevCamera& cam, const PassParams& pp, uint32_t n_pixels_round, const uint32_t* trange, int* entries, float4* lbox) {
     const RgkGroupRange g = rgk_group_range(pp.j0, pp.npix);
     k_entry_points_light<<<(g.count() + 63u) / 64u, 64, 0, st>>>(sc, cam, pp.xres, pp.yres, pp.pix_xy, n_pixels_round, g.first, g.count(), trange, entries, lbox);
-}
-
-// ------------------------------------------------------------------ rgk_shade.h, k_last_vertex (declared above rgk_launch_shade)
-static void launch_last_vertex(hipStream_t st, const DevScene& sc, const PassParams& pp, uint32_t bounce, const float4* rayA, const float4* rayB, const float4* hit,
-                               const float4* thr, float4* tot, float4* shA, float4* shB, float4* shC, uint32_t* counters, uint32_t bound, bool const_light) {
-    const int grid = rgk_last_vertex_grid(bound);
-    if (const_light) k_last_vertex<true><<<grid, RGK_SHADE_BLOCK_LATER, RGK_LDS_SHADE_BYTES, st>>>(sc, pp, bounce, rayA, rayB, hit, thr, tot, shA, shB, shC, counters);
-    else k_last_vertex<false><<<grid, RGK_SHADE_BLOCK_LATER, RGK_LDS_SHADE_BYTES, st>>>(sc, pp, bounce, rayA, rayB, hit, thr, tot, shA, shB, shC, counters);
 }

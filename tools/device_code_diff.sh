@@ -1,9 +1,10 @@
 #!/bin/bash
 # Device code of two checkouts, compared kernel by kernel (no GPU needed): tools/device_code_diff.sh <parent-tree> <head-tree>
 #
-# Compiles rgk_kernels.hip, rgk_post.hip and rgk_build.hip of both trees to gfx950 assembly with the command recorded in
-# profiles/host_split_device_code.txt, normalises what differs between two checkouts of the SAME source (the checkout path and
-# the compilation-unit word __hip_cuid_<16 hex digits>) and prints
+# Compiles rgk_kernels.hip, rgk_shade_kernels.hip, rgk_post.hip and rgk_build.hip of both trees to gfx950 assembly with the command
+# recorded in profiles/host_split_device_code.txt (per source: the flags rgk_amd/build.py SOURCE_FLAGS gives it), normalises what
+# differs between two checkouts of the SAME source (the checkout path and the compilation-unit word __hip_cuid_<16 hex digits>)
+# and prints
 #   per source: the sha256 of the normalised .s on both sides;
 #   per kernel: `same`, or the two rows of VGPRs, scratch bytes, LDS bytes, occupancy and code bytes.
 # A kernel is `same` when its whole block of the assembly -- instructions, descriptor, register and scratch figures -- is
@@ -14,7 +15,9 @@ HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 command -v "$HIPCC" >/dev/null || { echo "$0: no hipcc ($HIPCC)" >&2; exit 2; }
 CXXFILT=$(dirname "$(readlink -f "$(command -v "$HIPCC")")")/../llvm/bin/llvm-cxxfilt
 [ -x "$CXXFILT" ] || CXXFILT=$(command -v llvm-cxxfilt || command -v c++filt || echo cat)
-SOURCES="rgk_kernels rgk_post rgk_build"
+SOURCES="rgk_kernels rgk_shade_kernels rgk_post rgk_build"
+# rgk_amd/build.py SOURCE_FLAGS: the shading kernels are built without SLP vectorisation
+source_flags() { case $1 in rgk_shade_kernels) echo -fno-slp-vectorize ;; esac; }
 work=$(mktemp -d) || exit 2
 trap 'rm -rf "$work"' EXIT
 
@@ -24,7 +27,8 @@ for side in parent head; do
     tree=$(cd "$tree" && pwd) || exit 2
     mkdir -p "$work/$side"
     for f in $SOURCES; do
-        (cd "$tree" && "$HIPCC" --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-fast-math -x hip --cuda-device-only -S -Iinclude \
+        [ -e "$tree/rgk_amd/csrc/$f.hip" ] || { : >"$work/$side/$f.s"; continue; } # a tree from before the source existed: its kernels show as absent
+        (cd "$tree" && "$HIPCC" --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-fast-math $(source_flags $f) -x hip --cuda-device-only -S -Iinclude \
              rgk_amd/csrc/$f.hip -o "$work/$side/$f.raw" 2>"$work/$side/$f.err" &&
          sed -e "s|$tree|TREE|g" -e 's/__hip_cuid_[0-9a-f]*/__hip_cuid_X/g' "$work/$side/$f.raw" >"$work/$side/$f.s") &
         pids+=($!)
