@@ -500,7 +500,10 @@ int rgk_denoise_device(rgk_scene *scene, uint32_t xres, uint32_t yres, const flo
  * which = 5: the temporal pair -- {the last rgk_temporal_reproject_device, the last rgk_temporal_blend_device}, one launch each;
  * two entries once either has run with "time_post" on, 0 ms for the one that has not.
  * which = 6: the last rgk_render_aov_chain[_device] -- pixel list + ray generation, then {walker, k_aov_hop} per hop 0 .. max_hops.
- * which = 7: the last rgk_upsample_device -- {k_us_prepare, k_us_gather}. */
+ * which = 7: the last rgk_upsample_device -- {k_us_prepare, k_us_gather}.
+ * which = 8: the last rgk_remodulate_device -- {k_remodulate}.
+ * which = 9: the last rgk_render_round_demod_device -- {its k_demod_divisor launches, its k_resolve_demod launches}, each summed
+ * over the round's passes (the round's other launches: rgk_counters with RGK_FLAG_TIME_KERNELS). */
 int rgk_scene_get_post_timing(const rgk_scene *scene, uint32_t which, double *ms, uint32_t *n);
 
 /* ---- noise estimate from two half-buffers and the variance-guided filter (DESIGN.md "Half-buffer noise estimate") ----
@@ -678,6 +681,47 @@ int rgk_upsample_device(rgk_scene *scene, uint32_t xres, uint32_t yres, const rg
                         const float *d_low_albedo, const float *d_low_normal, const float *d_low_depth,
                         const rgk_upsample_params *params,
                         float *d_out_rgb /*3P*/, uint8_t *d_out_support /*P, may be NULL*/);
+
+/* ---- per-sample demodulated accumulation (DESIGN.md "Per-sample demodulated accumulation") ----
+ *
+ * The post stages above divide a pixel's MEAN radiance by the albedo of the one ray through the pixel centre, which is the
+ * irradiance only where the texture is constant over the pixel's footprint.  A demodulated round keeps, beside the accumulator
+ * S = sum of L_s, two more planes of 3P floats:
+ *   D = sum over samples s of L_s / div_s      (d_demod_rgb)
+ *   A = sum over samples s of div_s            (d_div_rgb, the anti-aliased divisor: D / n is multiplied back with A / n)
+ * where div_s belongs to sample s's OWN camera ray -- pixel jitter and lens included, the ray the round's first walk traced.
+ * Float32, only + * / max, no contraction, sums in sample order.  Per path slot of a pass (pixel j, sample s):
+ *   (o, d) = the camera ray of the slot; h = its first hit as the bounce-0 walk left it
+ *   a miss: div = (1, 1, 1).  Else the path vertex at h (hit point, interpolated normal, uv, as the integrator forms it, with
+ *   bumpmap_scale); a vertex the integrator drops (no usable normal): div = (1, 1, 1).  Else a = the albedo of the vertex's material
+ *   at uv as the feature pass defines it above (mixes to two levels, mirror / dielectric / transparent = 1), and per channel
+ *   div_c = a_c > 0 ? max(a_c, albedo_floor) : 1
+ *   v_s = the value the round adds to S for the sample: clamped to params->clamp, then NaN and negatives set to 0 (the clamp comes
+ *   before the division)
+ * Per pixel, in sample order: Dsum += v_s / div_s, Asum += div_s, both from 0, carried across the sample passes of a round the way the
+ * radiance sum is; with the pixel's last sample d_demod_rgb[p] += Dsum and d_div_rgb[p] += Asum, one addition per element.
+ *
+ * d_accum_rgb, d_accum_count and *counters receive exactly what the plain round entry gives them, bit for bit: the two entries share
+ * one body, and the plain entry launches, allocates and branches as it did before this one existed.  The extra launches -- the
+ * divisors behind the first walk, a second resolve behind the first -- are not entered in counters.  Workspace: 16 B per path of the
+ * batch and 32 B per pixel of the round, allocated by the first demodulated round of a scene.
+ * RGK_ERR_UNSUPPORTED: params->reverse > 0 (a light-tracing splat has no path slot to demodulate), depth == 0 (no first hit), and
+ * everything the plain entry refuses.  RGK_ERR_INVALID: a NULL plane, two of the four planes the same buffer, albedo_floor negative,
+ * NaN or infinite, and everything the plain entry refuses as invalid.  All DEVICE pointers on the scene's GPU; blocking. */
+int rgk_render_round_demod_device(rgk_scene *scene, const rgk_camera *camera, const rgk_params *params,
+                                  const rgk_tile *tiles, uint32_t n_tiles, float *d_accum_rgb, uint32_t *d_accum_count,
+                                  float *d_demod_rgb /*3P, +=*/, float *d_div_rgb /*3P, +=*/, float albedo_floor,
+                                  rgk_counters *counters);
+/* out = in * dbar per pixel and channel, float32, one multiplication:
+ *   d_div_count given:  dbar = n > 0 ? A / (float)n : 1      (d_div_rgb is the A plane of demodulated rounds, n its sample count)
+ *   d_div_count NULL:   dbar = a > 0 ? max(a, albedo_floor) : 1      (d_div_rgb is an albedo plane of the feature pass)
+ * in: 3P floats, e.g. D / n after a filter that ran with demodulate == 0.  The output is not one of the inputs.  albedo_floor >= 0 and
+ * finite (read in the second form only, checked in both).  All DEVICE pointers on the scene's GPU; whole frame; one launch on the
+ * scene's stream; blocking.  Arguments are checked before the scene or the device is touched; not while a round is in flight on this
+ * scene.  Uses no workspace.  The launch's time is which = 8 of the post timing query above. */
+int rgk_remodulate_device(rgk_scene *scene, uint32_t xres, uint32_t yres, const float *d_in_rgb /*3P*/,
+                          const float *d_div_rgb /*3P*/, const uint32_t *d_div_count /* P, or NULL: d_div_rgb is an albedo plane */,
+                          float albedo_floor, float *d_out_rgb /*3P*/);
 
 /* The pinned transcendental functions of the path (include/rgk_libm.h) evaluated on the device, for the test that the GPU
  * and the CPU produce the same bits: fn 0 sin, 1 cos, 2 acos, 3 asin, 4 atan2(a[i], b[i]) (b may be NULL otherwise). */

@@ -43,6 +43,14 @@
                     takes radiance only from quarter-resolution pixels on its own surface; scaled like the plain output.  With --denoise the upsampled image
                     is filtered at full resolution; the `denoised` file stays the quarter-resolution one.  Not with --temporal,
                     --noise, --until-noise, --adaptive, --aov-hops or -d.  Every other file is unchanged
+  --demod           needs --denoise or --upsample: rounds also accumulate each sample's radiance over the albedo at the first hit of the
+                    sample's own camera ray (floored at 0.02) and the sum of those divisors.  The `denoised` image is then that
+                    irradiance filtered without the centre-ray division and multiplied by the pixel's mean divisor; the `upsampled`
+                    image is the quarter-resolution irradiance reconstructed (and, with --denoise, filtered) on the full grid and
+                    multiplied by the full-resolution albedo.  Also writes the suffix `irradiance`, scaled like the plain output,
+                    after every round that rewrites the output.  With --checkpoint the two sums are saved beside it as `F.demod`
+                    and `F.div`; resuming a checkpoint that has none is refused.  Not with --noise, --until-noise, --adaptive,
+                    --temporal, --aov-hops, -d or bidirectional rounds ("reverse" > 0).  Without the switch every file is unchanged
 FILE is a .json or .rtc scene config.  One process drives one GPU; several GPUs: python -m torch.distributed.run ... bench.py.
 """
 import argparse
@@ -109,6 +117,7 @@ def main(argv=None):
     ap.add_argument("--frames", type=int, default=None, help="with -r: stop after this many frames (default: all 501)")
     ap.add_argument("--aov-hops", type=int, default=None, metavar="K")
     ap.add_argument("--upsample", action="store_true")
+    ap.add_argument("--demod", action="store_true")
     args = ap.parse_args(argv)
     verbosity = max(0, 2 + args.v - args.q)
     say = lambda lvl, *a: print(*a) if verbosity >= lvl else None
@@ -138,10 +147,22 @@ def main(argv=None):
         if clash:
             print(f"ERROR: --upsample cannot be combined with {clash[0]}.")
             return 1
+    if args.demod:
+        if not (args.denoise or args.upsample):
+            print("ERROR: --demod needs --denoise or --upsample.")
+            return 1
+        clash = [name for name, on in (("--noise", args.noise), ("--until-noise", args.until_noise is not None), ("--adaptive", args.adaptive is not None),
+                                       ("--temporal", args.temporal), ("--aov-hops", args.aov_hops is not None), ("-d", args.debug is not None)) if on]
+        if clash:
+            print(f"ERROR: --demod cannot be combined with {clash[0]}.")
+            return 1
     try:
         cfg = load_config(args.file)
     except ConfigFileException as e:
         print("Failed to load config file:", e)
+        return 1
+    if args.demod and int(getattr(cfg, "reverse", 0)) > 0:
+        print('ERROR: --demod cannot be combined with bidirectional rounds ("reverse" > 0 in the configuration).')
         return 1
     if args.timed is not None:
         if args.timed <= 0:
@@ -154,6 +175,11 @@ def main(argv=None):
     if args.until_noise is not None and not args.until_noise > 0:
         print("ERROR: Invalid argument for --until-noise.")
         return 1
+    if args.demod and not args.rotate and args.checkpoint and os.path.exists(args.checkpoint):
+        for suffix in (".demod", ".div"):
+            if not os.path.exists(args.checkpoint + suffix):
+                print(f"ERROR: cannot resume from `{args.checkpoint}`: {rd.missing_demod_message(args.checkpoint, suffix)}")  # (before the scene is built and a GPU is asked for)
+                return 1
     if track_noise and not args.rotate and args.checkpoint and os.path.exists(args.checkpoint) and not os.path.exists(args.checkpoint + ".half"):
         print(f"ERROR: cannot resume from `{args.checkpoint}`: {rd.missing_half_message(args.checkpoint)}")  # (before the scene is built and a GPU is asked for)
         return 1
@@ -203,7 +229,7 @@ def main(argv=None):
         try:
             drv = rd.RenderDriver(scene, cfg, camera, device=device, track_noise=track_noise,
                                   adaptive=capi.AdaptParams(args.until_noise, args.adaptive) if args.adaptive is not None else None, history=history,
-                                  aov_hops=aov_hops)
+                                  aov_hops=aov_hops, **(dict(track_demod=True) if args.demod else {}))
         except ValueError as e:
             print(f"ERROR: {e}")
             return 1
@@ -243,6 +269,7 @@ def main(argv=None):
                              aov_files={k: insert_file_suffix(out, k) for k in ("albedo", "normal", "depth") + (("hops",) if aov_hops > 0 else ())} if args.aov else None,
                              denoised_file=insert_file_suffix(out, "denoised") if args.denoise else None, temporal=args.temporal,
                              **(dict(upsampled_file=insert_file_suffix(out, "upsampled"), upsample_to=upsample_to) if args.upsample else {}),
+                             **(dict(irradiance_file=insert_file_suffix(out, "irradiance")) if args.demod else {}),
                              **(dict(until_noise=args.until_noise, noise_file=insert_file_suffix(out, "noise"),
                                      on_noise=lambda r, rel, n_live=None: say(1, f"Round {r}: " + (f"{n_live} live tiles, " if n_live is not None else "") +
                                                                                   f"relative noise {rel:.4g}")) if track_noise else {}))

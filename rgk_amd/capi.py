@@ -224,8 +224,10 @@ EXPORTS = ["rgk_last_error", "rgk_device_count", "rgk_scene_create", "rgk_scene_
            "rgk_render_aov_device", "rgk_render_aov", "rgk_denoise_device", "rgk_scene_get_post_timing",
            "rgk_noise_estimate_device", "rgk_denoise_variance_device", "rgk_adapt_select", "rgk_round_fold_device",
            "rgk_temporal_reproject_device", "rgk_temporal_blend_device",
-           "rgk_render_aov_chain_device", "rgk_render_aov_chain", "rgk_debug_poisoned_bytes", "rgk_upsample_device"]
+           "rgk_render_aov_chain_device", "rgk_render_aov_chain", "rgk_debug_poisoned_bytes", "rgk_upsample_device",
+           "rgk_render_round_demod_device", "rgk_remodulate_device"]
 AOV_MAX_HOPS = 8  # RGK_AOV_MAX_HOPS
+DEMOD_ALBEDO_FLOOR = 0.02  # the floor demodulated rounds ship with: the temporal and upsample stages' value
 
 _p = C.POINTER
 
@@ -300,6 +302,9 @@ def _bind(lib):
     lib.rgk_temporal_blend_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32] + [C.c_void_p] * 5 + [_p(TemporalParams)] + [C.c_void_p] * 3
     lib.rgk_upsample_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, _p(Camera)] + [C.c_void_p] * 3 + [C.c_uint32, C.c_uint32, _p(Camera)] + [
         C.c_void_p] * 5 + [_p(UpsampleParams), C.c_void_p, C.c_void_p]
+    lib.rgk_render_round_demod_device.argtypes = [C.c_void_p, _p(Camera), _p(Params), _p(Tile), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_float, _p(Counters)]
+    lib.rgk_remodulate_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
     lib.rgk_scene_get_post_timing.argtypes =[C.c_void_p, C.c_uint32, _p(C.c_double), _p(C.c_uint32)]
     lib.rgk_float_to_half.argtypes = [C.c_float]
     lib.rgk_float_to_half.restype = C.c_uint16

@@ -848,6 +848,15 @@ struct Vertex {
     quatf g2l;
 };
 __device__ __forceinline__ f3 clamp3(f3 v, float c) { return mk3(v.x > c ? c : v.x, v.y > c ? c : v.y, v.z > c ? c : v.z); }
+// A finished sample as the resolve takes it (path_tracer.cpp:502-507): clamped, then NaN and negatives scrubbed to 0 (rgk_resolve.h
+// resolve_add; k_resolve_demod, rgk_post.hip)
+__device__ __forceinline__ f3 resolve_value(float4 t, float clamp) {
+    f3 v = clamp3(mk3(t.x, t.y, t.z), clamp);
+    if (v.x != v.x || v.x < 0.0f) v.x = 0.0f;
+    if (v.y != v.y || v.y < 0.0f) v.y = 0.0f;
+    if (v.z != v.z || v.z < 0.0f) v.z = 0.0f;
+    return v;
+}
 
 // Interpolated face normal, not yet normalised, with the NaN fallbacks (path_tracer.cpp:157-171) and the zero test (:175): for
 // surface_point() below and for k_shade.  (`ok` by reference: returned in a struct with the normal, k_shade_light changes.)

@@ -159,3 +159,8 @@ void rgk_launch_us_prepare(hipStream_t st, const DevCamera& low, uint32_t xl, ui
 void rgk_launch_us_gather(hipStream_t st, const DevCamera& cam, const DevCamera& low, uint32_t xres, uint32_t yres, uint32_t xl, uint32_t yl, const float* albedo,
                           const float* normal, const float* depth, const float* low_rgb, const uint32_t* low_count, const float4* rec, float plane_tol, float normal_cos,
                           uint32_t demodulate, float albedo_floor, float* out_rgb, uint8_t* out_support);
+// per-sample demodulated accumulation (rgk_post.hip): the divisor per path slot behind bounce 0's walk (div: 16 B per slot of the pass),
+// the second resolve (pixsum2: two float4 per pixel of the round), and out = in * dbar per pixel (div_count NULL: div_rgb is an albedo plane)
+void rgk_launch_demod_divisor(hipStream_t st, const DevScene& sc, const DevCamera& cam, const PassParams& pp, const float4* hit, float albedo_floor, float4* div);
+void rgk_launch_resolve_demod(hipStream_t st, const PassParams& pp, const float4* tot, const float4* div, float4* pixsum2, float* demod_rgb, float* div_rgb);
+void rgk_launch_remodulate(hipStream_t st, size_t P, const float* in_rgb, const float* div_rgb, const uint32_t* div_count, float albedo_floor, float* out_rgb);

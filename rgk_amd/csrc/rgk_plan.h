@@ -120,6 +120,15 @@ inline RgkResolvePlan rgk_resolve_plan(uint32_t npix, uint32_t gshift) {
     const uint32_t PT = G <= 8 ? 64u : 512u / G; // pixels per tile: ~9 KB of LDS per wave (more waves per CU matter more here than full lanes in the short summing phase)
     return {(int)std::min<uint32_t>((npix + PT - 1) / PT, RGK_CUS * 64), PT, (size_t)PT * (G + 1) * 16}; // (16: sizeof(float4))
 }
+// k_demod_divisor (rgk_post.hip): workgroups of 256 striding over the pass's slots; each fills the LDS tables once
+inline int rgk_demod_divisor_grid(uint32_t slots) { return rgk_bounded_grid(RGK_CUS * 8, slots, 256u); }
+// k_resolve_demod (rgk_post.hip): waves of 64 lanes for both slot orders, a lane per pixel; gshift > 0 stages two planes, tot and the
+// divisors, so twice k_resolve_tiled's LDS at its tile size
+inline RgkResolvePlan rgk_resolve_demod_plan(uint32_t npix, uint32_t gshift) {
+    if (gshift == 0) return {(int)std::min<uint32_t>((npix + 63u) / 64u, RGK_CUS * 64), 64u, 0};
+    const RgkResolvePlan r = rgk_resolve_plan(npix, gshift);
+    return {r.grid, r.PT, 2 * r.lds};
+}
 
 // ------------------------------------------------------------------ denoisers and noise estimate (rgk_post.hip, k_dn_* / k_nz_*)
 // a thread per pixel in blocks of 256; the filters' 2-D workgroups of 32 x 8 pixels; the statistics' workgroup per tile of

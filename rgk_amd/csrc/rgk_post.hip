@@ -798,3 +798,119 @@ void rgk_launch_us_gather(hipStream_t st, const DevCamera& cam, const DevCamera&
     k_us_gather<0><<<dim3(g.x, g.y), RGK_POST_BX * RGK_POST_BY, 0, st>>>(cam, low, (int)xres, (int)yres, (int)xl, (int)yl, albedo, normal, depth, low_rgb, low_count, rec,
                                                                          plane_tol, normal_cos, demodulate, albedo_floor, out_rgb, out_support);
 }
+
+// ------------------------------------------------------------------ per-sample demodulated accumulation (rgk.h rgk_render_round_demod_device)
+// Beside the accumulator S = sum of L_s a demodulated round keeps D = sum of L_s / div_s and A = sum of div_s, div_s the albedo at the
+// first hit of sample s's OWN camera ray (jitter and lens included) through the floor rule of demod_div.  No shading kernel or walker
+// takes part: at bounce 0 hit[] is indexed by path slot -- every walker writes the record of every slot below npix * ns, misses
+// included (k_trace_camera at the lane's retirement, k_trace_camera_beam when it sets the sample up), which k_shade<FIRST> relies on
+// as well -- camera_ray_of_slot re-derives the ray from the slot number, and tot[slot] holds the finished sample until the resolve.
+//   k_demod_divisor  a lane per slot (a bounded grid of 256-lane workgroups striding over the slots), behind bounce 0's walk and before its shading (later bounces index hit[] by queue position):
+//                    surface_point() + albedo_of() as k_aov_gather has them -> div[slot] = {div.rgb, 0}.  Reads 16 B, writes 16 B per path.
+//   k_resolve_demod  behind k_resolve, over the same pass: per pixel, in sample order, Dsum += v_s / div_s and Asum += div_s with v_s
+//                    the value resolve_add adds (resolve_value, rgk_device.h: the clamp comes before the division); carried across
+//                    sample passes in pixsum2[2 * pixel] / [2 * pixel + 1]; added to the two planes with the pixel's last sample.
+//                    gshift > 0: the sample blocks of tot and div are staged through LDS as k_resolve_tiled stages tot.
+//   k_remodulate     a lane per pixel: out = in * dbar, dbar = A / n (1 where n == 0) or the floor rule of an albedo plane.
+// Float32, + * / max only, nothing contracted, sums in sample order: tests/demod_ref.py gives the same bits.
+// (Templates for the reason k_tp_reproject is one; last in the file, so every earlier kernel keeps its text.)
+template <int = 0>
+__global__ __launch_bounds__(256) void k_demod_divisor(const DevScene sc, const DevCamera cam, const PassParams pp, const float4* __restrict__ hit, float albedo_floor,
+                                                        float4* __restrict__ div) {
+    lut_lds_fill(sc); // (a barrier: before any lane leaves; once per workgroup, which is why the grid is bounded and the lanes stride)
+    const uint32_t n = pp.npix * pp.ns;
+    for (uint32_t slot = blockIdx.x * 256u + threadIdx.x; slot < n; slot += gridDim.x * 256u) {
+        const float4 h = hit[slot];
+        f3 dv = mk3(1.f, 1.f, 1.f);
+        if (__float_as_int(h.w) >= 0) {
+            f3 o, d;
+            camera_ray_of_slot(cam, pp, slot, o, d);
+            Vertex v;
+            surface_point(sc, pp.bumpmap_scale, o, d, h, v);
+            if (v.ok) {
+                const f3 a = albedo_of(sc, v.mat, v.uv);
+                dv = mk3(demod_div(a.x, albedo_floor), demod_div(a.y, albedo_floor), demod_div(a.z, albedo_floor));
+            }
+        }
+        div[slot] = make_float4(dv.x, dv.y, dv.z, 0.f);
+    }
+}
+
+__device__ __forceinline__ void demod_add(float4& D, float4& A, float4 t, float4 dv, float clamp) {
+    const f3 v = resolve_value(t, clamp);
+    D.x = D.x + v.x / dv.x; D.y = D.y + v.y / dv.y; D.z = D.z + v.z / dv.z;
+    A.x = A.x + dv.x; A.y = A.y + dv.y; A.z = A.z + dv.z;
+}
+// One wave per PT <= 64 pixels, lane p owns pixel p.  gshift == 0: consecutive lanes read consecutive slots, nothing to stage.
+template <int = 0>
+__global__ __launch_bounds__(64) void k_resolve_demod(const PassParams pp, const float4* __restrict__ tot, const float4* __restrict__ div, float4* __restrict__ pixsum2,
+                                                       float* __restrict__ demod_rgb, float* __restrict__ div_rgb, const uint32_t PT) {
+    extern __shared__ float4 tile[]; // gshift > 0: [2][PT pixels][G + 1] -- tot, then div
+    const uint32_t G = 1u << pp.gshift, lane = threadIdx.x;
+    for (uint32_t jb = blockIdx.x * PT; jb < pp.npix; jb += gridDim.x * PT) {
+        const uint32_t np = min(PT, pp.npix - jb), j = jb + lane;
+        float4 D = make_float4(0.f, 0.f, 0.f, 0.f), A = D;
+        if (lane < np && pp.s0 != 0) { D = pixsum2[2 * (size_t)(pp.j0 + j)]; A = pixsum2[2 * (size_t)(pp.j0 + j) + 1]; }
+        if (pp.gshift == 0) {
+            if (lane < np)
+                for (uint32_t srel = 0; srel < pp.ns; srel++) {
+                    const size_t slot = (size_t)srel * pp.npix + j; // slot_of at gshift 0
+                    demod_add(D, A, tot[slot], div[slot], pp.clamp);
+                }
+        } else {
+            float4* const tile_d = tile + PT * (G + 1u);
+            for (uint32_t sb = 0; sb < (pp.ns >> pp.gshift); sb++) {
+                const size_t base = (size_t)(sb * pp.npix + jb) << pp.gshift; // np * G consecutive slots
+                for (uint32_t k = 0; k * 64u < np * G; k++) {
+                    const uint32_t idx = k * 64u + lane;
+                    if (idx < np * G) {
+                        const uint32_t at = (idx >> pp.gshift) * (G + 1u) + (idx & (G - 1u));
+                        tile[at] = tot[base + idx];
+                        tile_d[at] = div[base + idx];
+                    }
+                }
+                __syncthreads();
+                if (lane < np)
+                    for (uint32_t g = 0; g < G; g++) demod_add(D, A, tile[lane * (G + 1u) + g], tile_d[lane * (G + 1u) + g], pp.clamp);
+                __syncthreads();
+            }
+        }
+        if (lane < np) {
+            if (pp.s0 + pp.ns >= pp.multisample) {
+                const uint32_t pix = pp.pix_xy[pp.j0 + j];
+                const size_t p = (size_t)(pix >> 16) * pp.xres + (pix & 0xffffu);
+                demod_rgb[3 * p] += D.x; demod_rgb[3 * p + 1] += D.y; demod_rgb[3 * p + 2] += D.z;
+                div_rgb[3 * p] += A.x; div_rgb[3 * p + 1] += A.y; div_rgb[3 * p + 2] += A.z;
+            } else {
+                pixsum2[2 * (size_t)(pp.j0 + j)] = D;
+                pixsum2[2 * (size_t)(pp.j0 + j) + 1] = A;
+            }
+        }
+    }
+}
+
+template <int = 0>
+__global__ __launch_bounds__(RGK_POST_BLOCK) void k_remodulate(size_t P, const float* __restrict__ in_rgb, const float* __restrict__ div_rgb,
+                                                                const uint32_t* __restrict__ div_count, float albedo_floor, float* __restrict__ out_rgb) {
+    const size_t p = (size_t)blockIdx.x * RGK_POST_BLOCK + threadIdx.x;
+    if (p >= P) return;
+    f3 dbar = mk3(1.f, 1.f, 1.f);
+    const f3 a = ld3(div_rgb, p);
+    if (div_count) {
+        const uint32_t n = div_count[p];
+        if (n) dbar = a / (float)n;
+    } else dbar = mk3(demod_div(a.x, albedo_floor), demod_div(a.y, albedo_floor), demod_div(a.z, albedo_floor));
+    const f3 c = ld3(in_rgb, p);
+    out_rgb[3 * p] = c.x * dbar.x; out_rgb[3 * p + 1] = c.y * dbar.y; out_rgb[3 * p + 2] = c.z * dbar.z;
+}
+
+void rgk_launch_demod_divisor(hipStream_t st, const DevScene& sc, const DevCamera& cam, const PassParams& pp, const float4* hit, float albedo_floor, float4* div) {
+    k_demod_divisor<0><<<rgk_demod_divisor_grid(pp.npix * pp.ns), 256, RGK_LDS_SHADE_BYTES, st>>>(sc, cam, pp, hit, albedo_floor, div);
+}
+void rgk_launch_resolve_demod(hipStream_t st, const PassParams& pp, const float4* tot, const float4* div, float4* pixsum2, float* demod_rgb, float* div_rgb) {
+    const RgkResolvePlan r = rgk_resolve_demod_plan(pp.npix, pp.gshift);
+    k_resolve_demod<0><<<r.grid, 64, r.lds, st>>>(pp, tot, div, pixsum2, demod_rgb, div_rgb, r.PT);
+}
+void rgk_launch_remodulate(hipStream_t st, size_t P, const float* in_rgb, const float* div_rgb, const uint32_t* div_count, float albedo_floor, float* out_rgb) {
+    k_remodulate<0><<<rgk_post_pixel_grid(P), RGK_POST_BLOCK, 0, st>>>(P, in_rgb, div_rgb, div_count, albedo_floor, out_rgb);
+}

@@ -407,6 +407,22 @@ int rgk_upsample_device(rgk_scene* s, uint32_t xres, uint32_t yres, const rgk_ca
     });
 }
 
+int rgk_remodulate_device(rgk_scene* s, uint32_t xres, uint32_t yres, const float* d_in_rgb, const float* d_div_rgb, const uint32_t* d_div_count, float albedo_floor,
+                          float* d_out_rgb) {
+    // (every check before the scene or the device is touched)
+    if (!s || !d_in_rgb || !d_div_rgb || !d_out_rgb) return fail(RGK_ERR_INVALID, "null argument");
+    if (!(albedo_floor >= 0.0f) || std::isinf(albedo_floor)) return fail(RGK_ERR_INVALID, "albedo_floor must be >= 0 and finite");
+    int rc;
+    const void* ins[3] = {d_in_rgb, d_div_rgb, d_div_count};
+    const void* outs[1] = {d_out_rgb};
+    if ((rc = check_frame_size(xres, yres)) || (rc = check_outputs_apart(ins, 3, outs, 1))) return rc;
+    return post_call(s, "rgk_remodulate_device", POST_REMODULATE, true, [&](PostTimer& tm) -> int {
+        if ((rc = tm.mark())) return rc;
+        rgk_launch_remodulate(s->stream, (size_t)xres * yres, d_in_rgb, d_div_rgb, d_div_count, albedo_floor, d_out_rgb);
+        return tm.mark();
+    });
+}
+
 int rgk_scene_get_post_timing(const rgk_scene* s, uint32_t which, double* ms, uint32_t* n) {
     if (!s || !n || which >= POST_SLOTS || (!ms && *n)) return fail(RGK_ERR_INVALID, "bad argument");
     if (s->magic != RGK_SCENE_MAGIC) return fail(RGK_ERR_INVALID, "not a live scene handle");

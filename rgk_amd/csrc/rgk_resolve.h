@@ -9,10 +9,7 @@
 // final clamp + NaN/negative scrub (path_tracer.cpp:502-507), per-pixel sum over the pass's
 // samples in sample order (RenderPixel :64), then AddPixel when the pixel's last sample is in.
 __device__ __forceinline__ float4 resolve_add(float4 acc, float4 t, float clamp) {
-    f3 v = clamp3(mk3(t.x, t.y, t.z), clamp);
-    if (v.x != v.x || v.x < 0.0f) v.x = 0.0f;
-    if (v.y != v.y || v.y < 0.0f) v.y = 0.0f;
-    if (v.z != v.z || v.z < 0.0f) v.z = 0.0f;
+    const f3 v = resolve_value(t, clamp);
     acc.x = acc.x + v.x; acc.y = acc.y + v.y; acc.z = acc.z + v.z;
     return acc;
 }

@@ -1,6 +1,7 @@
 // The round driver: tiles -> per-pixel seeds (a2) -> passes of paths resident in HBM -> raygen / trace / shade / shadow / resolve
 // launches on one HIP stream.
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 
 #include "rgk_scene_impl.h"
@@ -196,11 +197,21 @@ int queue_first_hit_lists(rgk_scene* s, KernelLog& kl, const DevCamera& cam, Pas
     return 0;
 }
 
+// What a demodulated round has beside the accumulator (rgk.h rgk_render_round_demod_device).
+// `timed` (the scene's "time_post" switch): event pairs around the two extra launches of every pass, {divisor, resolve} alternating.
+struct DemodPlanes {
+    float* demod_rgb; float* div_rgb; float albedo_floor;
+    bool timed = false;
+    std::vector<hipEvent_t> evs = {};
+};
+
 // One pass, queued on the scene's stream: the light sub-path (reverse > 0), the camera path's bounces, the resolve into the
 // accumulator, a progress mark behind every bounce (`stage`: the round's stages before this pass), and the copy of the pass's
 // counter blocks into h_counters.
+// `dm` (a demodulated round, else null): behind bounce 0's walk the divisor of every slot, behind the resolve the second one.  Neither
+// launch goes through the kernel log: the counters of a demodulated round are the plain round's.
 int queue_pass(rgk_scene* s, KernelLog& kl, const DevCamera& cam, PassParams& pp, size_t P, bool light_entry, bool const_light, float* d_accum_rgb,
-               uint32_t* d_accum_count, uint32_t stage) {
+               uint32_t* d_accum_count, uint32_t stage, DemodPlanes* dm) {
     hipStream_t st = s->stream;
     const RgkTraceCfg& tc = s->tcfg;
     const bool count_stats = kl.count_stats, cap_entries = s->entry.p != nullptr && s->tune.entry_cap;
@@ -215,6 +226,19 @@ int queue_pass(rgk_scene* s, KernelLog& kl, const DevCamera& cam, PassParams& pp
     uint32_t* const cn = s->counters.p;      // camera-phase counters
     uint32_t* const cl = cn + RGK_CNT_TOTAL; // light-phase counters
     int rc;
+    const auto demod_launch = [&](auto&& launch) -> int { // outside the kernel log; between two events of the scene's pool when timed
+        hipEvent_t a = nullptr, b = nullptr;
+        if (dm->timed) {
+            if ((rc = kl.event(a)) || (rc = kl.event(b))) return rc;
+            HIPCHK(hipEventRecord(a, st));
+        }
+        launch();
+        if (dm->timed) {
+            HIPCHK(hipEventRecord(b, st));
+            dm->evs.push_back(a); dm->evs.push_back(b);
+        }
+        return 0;
+    };
     if (R > 0) {
         // light sub-path first (its sampler dimensions are fixed), splats straight into the accumulator
         if ((rc = kl.run(RGK_K_OTHER, [&] { rgk_launch_init_counters(st, cl, 0u); })) || // (k_raygen_light queues the light rays that can touch the scene's box)
@@ -242,6 +266,7 @@ int queue_pass(rgk_scene* s, KernelLog& kl, const DevCamera& cam, PassParams& pp
         else
             rc = kl.run(RGK_K_TRACE_CLOSEST, [&] { rgk_launch_trace_closest(st, s->dev, tc, count_stats, rayA[q], rayB[q], nullptr, hit, wq, s->stats.p); });
         if (rc || (b == 0 && (rc = queue_first_hit_lists(s, kl, cam, pp, (uint32_t)P, cap_entries, light_entry)))) return rc;
+        if (dm && b == 0 && (rc = demod_launch([&] { rgk_launch_demod_divisor(st, s->dev, cam, pp, hit, dm->albedo_floor, s->demod_div.p); }))) return rc;
         if ((rc = kl.run(b == 0 ? RGK_K_SHADE_FIRST : RGK_K_SHADE, [&] { rgk_launch_shade(st, s->dev, cam, pp, b, rayA[q], rayB[q], hit, thr, tot, rayA[q ^ 1], rayB[q ^ 1], shA, shB, shC, cn, ub, R > 0, const_light, s->tune.last_vertex); })) ||
             (R > 0 && (rc = kl.run(RGK_K_CONNECT, [&] { rgk_launch_connect(st, s->dev, pp, b, s->jobs.p, s->rads.p, cn, ub); }))))
             return rc;
@@ -255,16 +280,15 @@ int queue_pass(rgk_scene* s, KernelLog& kl, const DevCamera& cam, PassParams& pp
         if (track && b >= 3 && (b & 1) && b + 1 < pp.depth && (rc = queue_len(s, cn + RGK_CNT_QUEUE + b + 1, ub))) return rc;
     }
     if ((rc = kl.run(RGK_K_RESOLVE, [&] { rgk_launch_resolve(st, pp, tot, s->pixsum.p, d_accum_rgb, d_accum_count); }))) return rc;
+    if (dm && (rc = demod_launch([&] { rgk_launch_resolve_demod(st, pp, tot, s->demod_div.p, s->demod_pixsum.p, dm->demod_rgb, dm->div_rgb); }))) return rc;
     rgk_launch_stage_mark(st, s->h_stage, stage + std::max(1u, pp.depth)); // (all of the pass's stages: bounces that never ran count too)
     HIPCHK(hipMemcpyAsync(s->h_counters, cn, 2 * RGK_CNT_TOTAL * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     return 0;
 }
-} // namespace
 
-extern "C" {
-
-int rgk_render_round_device(rgk_scene* s, const rgk_camera* camera, const rgk_params* prm, const rgk_tile* tiles, uint32_t n_tiles,
-                            float* d_accum_rgb, uint32_t* d_accum_count, rgk_counters* counters) {
+// The body of both round entries.  dm == null: rgk_render_round_device, as it was before the demodulated round existed.
+int render_round(rgk_scene* s, const rgk_camera* camera, const rgk_params* prm, const rgk_tile* tiles, uint32_t n_tiles, float* d_accum_rgb, uint32_t* d_accum_count,
+                 rgk_counters* counters, DemodPlanes* dm) {
     if (!s || !camera || !prm || (!tiles && n_tiles) || !d_accum_rgb || !d_accum_count) return fail(RGK_ERR_INVALID, "null argument");
     if (int rc = check_frame_size(prm->xres, prm->yres)) return rc;
     if (prm->multisample == 0) return fail(RGK_ERR_INVALID, "multisample must be >= 1");
@@ -282,6 +306,7 @@ int rgk_render_round_device(rgk_scene* s, const rgk_camera* camera, const rgk_pa
     // no light at all: TracePath builds no light sub-path (`reverse > 0 && valid light`), same as reverse == 0
     const uint32_t R = (s->dev.total_point_power + s->dev.total_areal_power > 0.0f) ? prm->reverse : 0u;
     if ((rc = plan_passes(s, prm, P, R, plan))) return rc;
+    if (dm && ((rc = s->demod_div.alloc(s->batch)) || (rc = s->demod_pixsum.alloc(2 * P)))) return rc;
 
     DevCamera cam;
     make_camera(camera, cam);
@@ -325,13 +350,23 @@ int rgk_render_round_device(rgk_scene* s, const rgk_camera* camera, const rgk_pa
         for (uint32_t s0 = 0; s0 < prm->multisample; s0 += plan.ns_pass, stage += pass_stages) {
             pp.s0 = s0;
             pp.ns = std::min(plan.ns_pass, prm->multisample - s0);
-            if ((rc = queue_pass(s, kl, cam, pp, P, light_entry, const_light, d_accum_rgb, d_accum_count, stage))) return rc;
+            if ((rc = queue_pass(s, kl, cam, pp, P, light_entry, const_light, d_accum_rgb, d_accum_count, stage, dm))) return rc;
             HIPCHK(hipStreamSynchronize(s->stream));
             rgk_add_pass_counters(s->h_counters, s->h_counters + RGK_CNT_TOTAL, pp.depth, pp.reverse, pp.npix * pp.ns, light_entry, tot);
         }
     }
     HIPCHK(hipGetLastError());
     s->prog_rounds++;
+    if (dm) { // rgk_scene_get_post_timing(9): {the round's k_demod_divisor launches, its k_resolve_demod launches}, summed over the passes
+        std::vector<double>& ms = s->post_ms[POST_DEMOD_ROUND];
+        ms.clear();
+        if (dm->timed) ms.assign(2, 0.0);
+        for (size_t i = 0; i + 1 < dm->evs.size(); i += 2) {
+            float t = 0.f;
+            HIPCHK(hipEventElapsedTime(&t, dm->evs[i], dm->evs[i + 1]));
+            ms[(i / 2) & 1] += t;
+        }
+    }
     if (counters) {
         tot.paths = (uint64_t)P * prm->multisample;
         if (kl.count_stats) {
@@ -343,6 +378,31 @@ int rgk_render_round_device(rgk_scene* s, const rgk_camera* camera, const rgk_pa
         *counters = tot;
     }
     return RGK_OK;
+}
+} // namespace
+
+extern "C" {
+
+int rgk_render_round_device(rgk_scene* s, const rgk_camera* camera, const rgk_params* prm, const rgk_tile* tiles, uint32_t n_tiles,
+                            float* d_accum_rgb, uint32_t* d_accum_count, rgk_counters* counters) {
+    return render_round(s, camera, prm, tiles, n_tiles, d_accum_rgb, d_accum_count, counters, nullptr);
+}
+
+int rgk_render_round_demod_device(rgk_scene* s, const rgk_camera* camera, const rgk_params* prm, const rgk_tile* tiles, uint32_t n_tiles, float* d_accum_rgb,
+                                  uint32_t* d_accum_count, float* d_demod_rgb, float* d_div_rgb, float albedo_floor, rgk_counters* counters) {
+    // (its own checks first, like the shared ones before the scene or the device is touched)
+    if (!d_demod_rgb || !d_div_rgb) return fail(RGK_ERR_INVALID, "null argument");
+    if (!(albedo_floor >= 0.0f) || std::isinf(albedo_floor)) return fail(RGK_ERR_INVALID, "albedo_floor must be >= 0 and finite");
+    if (d_demod_rgb == d_div_rgb || d_demod_rgb == d_accum_rgb || d_div_rgb == d_accum_rgb || (const void*)d_demod_rgb == d_accum_count || (const void*)d_div_rgb == d_accum_count)
+        return fail(RGK_ERR_INVALID, "the four planes must be four different buffers");
+    if (prm && prm->reverse > 0) return fail(RGK_ERR_UNSUPPORTED, "a demodulated round cannot be bidirectional (reverse %u): a light-tracing splat has no path slot", prm->reverse);
+    if (prm && prm->depth == 0) return fail(RGK_ERR_UNSUPPORTED, "a demodulated round needs depth >= 1: without a bounce there is no first hit");
+    DemodPlanes dm = {d_demod_rgb, d_div_rgb, albedo_floor};
+    if (s && s->magic == RGK_SCENE_MAGIC) {
+        dm.timed = s->tune.time_post;
+        if (!s->prog_busy.load()) s->post_ms[POST_DEMOD_ROUND].clear(); // (a round that ends early, with no pixel, leaves no earlier round's times)
+    }
+    return render_round(s, camera, prm, tiles, n_tiles, d_accum_rgb, d_accum_count, counters, &dm);
 }
 
 int rgk_render_round(rgk_scene* s, const rgk_camera* camera, const rgk_params* prm, const rgk_tile* tiles, uint32_t n_tiles,

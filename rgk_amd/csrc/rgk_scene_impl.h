@@ -88,7 +88,7 @@ struct RgkTuning {
 };
 
 // rgk_scene_get_post_timing's `which` (rgk.h): the post-processing call whose launch times a slot holds
-enum PostSlot : uint32_t { POST_AOV = 0, POST_DENOISE = 1, POST_DENOISE_VARIANCE = 2, POST_NOISE = 3, POST_FOLD = 4, POST_TEMPORAL = 5, POST_AOV_CHAIN = 6, POST_UPSAMPLE = 7, POST_SLOTS = 8 };
+enum PostSlot : uint32_t { POST_AOV = 0, POST_DENOISE = 1, POST_DENOISE_VARIANCE = 2, POST_NOISE = 3, POST_FOLD = 4, POST_TEMPORAL = 5, POST_AOV_CHAIN = 6, POST_UPSAMPLE = 7, POST_REMODULATE = 8, POST_DEMOD_ROUND = 9, POST_SLOTS = 10 };
 constexpr uint32_t RGK_SCENE_MAGIC = 0x53474b52u; // "RKGS": what a live scene handle starts with (rgk_scene_get_post_timing)
 struct rgk_scene {
     uint32_t magic = RGK_SCENE_MAGIC;
@@ -152,6 +152,9 @@ struct rgk_scene {
     DevBuf<rgk_noise_tile> nz_tiles;    // the noise estimate's per-tile sums
     DevBuf<uint32_t> fold_buf;          // the round fold's tile list (5 words per tile), then its flags (a byte per tile)
     DevBuf<float4> us_rec;              // the upsampler's tap records: three planes of the low grid (k_us_prepare)
+    // demodulated rounds (rgk_render_round_demod_device), allocated by the first one; beside the workspace, not part of its table
+    DevBuf<float4> demod_div;           // per path slot of a pass: the sample's divisor {div.rgb, 0} (k_demod_divisor), `batch` entries
+    DevBuf<float4> demod_pixsum;        // per pixel of the round: {Dsum}, {Asum} carried across sample passes (k_resolve_demod)
     std::vector<double> post_ms[POST_SLOTS]; // launch times of the last call of each kind (tuning "time_post")
     std::vector<hipEvent_t> events;
     uint32_t* h_counters = nullptr; // pinned

@@ -224,10 +224,24 @@ class Scene:
                                                           d_low_accum_rgb, d_low_accum_count, d_low_albedo, d_low_normal, d_low_depth, C.byref(params),
                                                           d_out_rgb, d_out_support))
 
+    def render_round_demod_device(self, camera, params, tiles, d_accum_ptr, d_count_ptr, d_demod_ptr, d_div_ptr, albedo_floor=capi.DEMOD_ALBEDO_FLOOR):
+        """rgk_render_round_demod_device: render_round_device, which gets the same bits, plus D += sum of L_s / div_s and A += sum of
+        div_s per pixel, div_s the floored albedo at the first hit of the sample's own camera ray; DEVICE pointers (ints)."""
+        cnt = capi.Counters()
+        capi.check(self.lib, self.lib.rgk_render_round_demod_device(self.h, C.byref(camera), C.byref(params), tiles, len(tiles), d_accum_ptr, d_count_ptr,
+                                                                    d_demod_ptr, d_div_ptr, albedo_floor, C.byref(cnt)))
+        return cnt
+
+    def remodulate_device(self, xres, yres, d_in_rgb, d_div_rgb, d_div_count, d_out_rgb, albedo_floor=capi.DEMOD_ALBEDO_FLOOR):
+        """rgk_remodulate_device: out = in * (A / n) with d_div_count, or in * floored albedo with d_div_count None (d_div_rgb then an
+        albedo plane); DEVICE pointers (ints), the output none of the inputs."""
+        capi.check(self.lib, self.lib.rgk_remodulate_device(self.h, xres, yres, d_in_rgb, d_div_rgb, d_div_count, albedo_floor, d_out_rgb))
+
     def post_timing(self, which):
         """HIP-event times (ms) of the launches of the last feature pass (0) / denoise call (1) / variance-guided denoise call (2) /
         noise estimate (3) / round fold (4: the copy of its tile list, the fold) / temporal pair (5: reproject, blend) /
-        followed feature pass (6: list + ray generation, then walker and k_aov_hop per hop) / upsample call (7: prepare, gather);
+        followed feature pass (6: list + ray generation, then walker and k_aov_hop per hop) / upsample call (7: prepare, gather) /
+        remodulate call (8) / demodulated round (9: its divisor launches, its second resolves, summed over the passes);
         set_tuning(time_post=1) first."""
         ms, n = (C.c_double * 32)(), C.c_uint32(32)
         capi.check(self.lib, self.lib.rgk_scene_get_post_timing(self.h, which, ms, C.byref(n)))
@@ -372,6 +386,11 @@ class EXRTexture:
         return rd_.value, sc_.value
 
 
+def missing_demod_message(path, suffix):
+    return (f"`{path}` has no `{path}{suffix}` beside it: it was written without demodulated accumulation, and the irradiance sums "
+            "cannot be continued from it (render without --demod, or start the frame again)")
+
+
 def missing_half_message(path):
     return (f"`{path}` has no half-buffer `{path}.half` beside it: it was written without noise tracking, and the noise estimate "
             "cannot be continued from it (render without --noise, or start the frame again)")
@@ -406,8 +425,28 @@ class RenderDriver:
     """RenderDriver::RenderFrame / RenderRound for one process per GPU."""
 
     def __init__(self, scene, cfg, camera, rank=0, world_size=1, device=None, sampler=capi.SAMPLER_HALTON, flags=0,
-                 host_reduce=False, track_noise=False, adaptive=None, history=None, aov_hops=0):
+                 host_reduce=False, track_noise=False, adaptive=None, history=None, aov_hops=0, track_demod=False,
+                 albedo_floor=capi.DEMOD_ALBEDO_FLOOR):
         import torch
+        # track_demod: rounds go through rgk_render_round_demod_device and keep, beside total_ob (which gets the bits it gets without),
+        # demod_ob = D, the sum of each sample's radiance over the floored albedo at ITS OWN first hit, and div_ob = A, the sum of those
+        # divisors; denoise() and upsample() then filter D / n with demodulate = 0 and multiply back (rgk_remodulate_device).
+        # albedo_floor: the floor on a sample's divisor, and on the full-resolution albedo upsample() multiplies back with.
+        # Everything that keeps a second accumulator of its own, or more than one rank, is refused, not half-supported.
+        self.track_demod = bool(track_demod)
+        if self.track_demod:
+            clash = [why for on, why in (
+                (track_noise, "track_noise: the half-buffers of the irradiance sums that the noise estimate would need are not kept"),
+                (adaptive is not None, "adaptive: it needs track_noise"),
+                (history is not None, "history: temporal reuse of irradiance is not done"),
+                (int(aov_hops) > 0, "aov_hops > 0: the per-sample divisor is the first hit's, not the followed one"),
+                (world_size > 1, "world_size > 1: the irradiance sums are not reduced across ranks"),
+                (int(cfg.get_params(sampler=sampler, flags=flags).reverse) > 0, "reverse > 0: a light-tracing splat has no sample to demodulate")) if on]
+            if clash:
+                raise ValueError("track_demod cannot be combined with " + clash[0])
+            if not (float(albedo_floor) >= 0.0 and float(albedo_floor) != float("inf")):
+                raise ValueError(f"albedo_floor must be >= 0 and finite, got {albedo_floor}")
+        self.albedo_floor = float(albedo_floor)
         # aov_hops (0 .. capi.AOV_MAX_HOPS): render_aov() -- and with it denoise(), denoise_variance() and the aov_files -- takes its
         # planes from rgk_render_aov_chain_device, which follows mirrors and glass to the first other surface; aov_hops_plane() is
         # the number of such surfaces a pixel passed.  0: the first-hit planes, every code path the one without it.
@@ -449,6 +488,9 @@ class RenderDriver:
         # which may differ in the last place.  Off: every code path is the untracked one.
         self.track_noise = bool(track_noise)
         self.half_ob = EXRTexture(cfg.xres, cfg.yres, self.device) if self.track_noise and rank == 0 else None
+        # (their count planes are not kept up: the sample count of all three is total_ob's; a checkpoint copies it in)
+        self.demod_ob = EXRTexture(cfg.xres, cfg.yres, self.device) if self.track_demod else None
+        self.div_ob = EXRTexture(cfg.xres, cfg.yres, self.device) if self.track_demod else None
         # adaptive (a capi.AdaptParams; its target is render_frame's until_noise): a round renders a subset of the tiles -- those
         # rgk_adapt_select leaves live -- and the fold's odd rounds are each TILE's odd visits.
         # `visits`: rounds each tile was rendered in, in the row-major tile order of noise()["tiles"]; `task_tile`: for task i of
@@ -498,7 +540,11 @@ class RenderDriver:
                 self.round_ob = EXRTexture(self.cfg.xres, self.cfg.yres, self.device)
             ob = self.round_ob
         torch.cuda.current_stream(self.device).synchronize()
-        cnt = self.scene.render_round_device(self.camera, self.params, tiles, ob.data.data_ptr(), ob.count.data_ptr())
+        if self.track_demod:  # (single rank, untracked: ob is total_ob)
+            cnt = self.scene.render_round_demod_device(self.camera, self.params, tiles, ob.data.data_ptr(), ob.count.data_ptr(),
+                                                       self.demod_ob.data.data_ptr(), self.div_ob.data.data_ptr(), self.albedo_floor)
+        else:
+            cnt = self.scene.render_round_device(self.camera, self.params, tiles, ob.data.data_ptr(), ob.count.data_ptr())
         if self.world_size > 1:
             if reduce:
                 self._reduce_round()
@@ -562,10 +608,32 @@ class RenderDriver:
             return None
         return a["hops"] if "hops" in a else torch.zeros((self.cfg.yres, self.cfg.xres), dtype=torch.uint8, device=self.device)
 
+    def _over_count(self, plane):
+        """plane / total_ob's sample count per pixel, 0 where the count is 0 (EXRTexture.get_pixels for a plane that shares the count)."""
+        import torch
+        c = self.total_ob.count.to(torch.float32).unsqueeze(-1)
+        return torch.where(c > 0, plane / c.clamp(min=1), torch.zeros_like(plane))
+
+    def irradiance(self):
+        """D / n of a track_demod driver: the mean over a pixel's samples of radiance over the sample's own floored first-hit albedo;
+        (y, x, 3) float32 tensor on the device, 0 where no sample fell."""
+        if not self.track_demod:
+            raise ValueError("irradiance() needs a driver made with track_demod=True")
+        return self._over_count(self.demod_ob.data)
+
+    def albedo_mean(self):
+        """A / n of a track_demod driver: the mean of the samples' divisors, i.e. the floored first-hit albedo anti-aliased over the
+        pixel's footprint (1 for a sample that missed); (y, x, 3) float32 tensor on the device, 0 where no sample fell."""
+        if not self.track_demod:
+            raise ValueError("albedo_mean() needs a driver made with track_demod=True")
+        return self._over_count(self.div_ob.data)
+
     def default_denoise_params(self):
-        """The shipped defaults; sigma_color = DENOISE_SIGMA_K x the mean over pixels of the largest channel of the image."""
-        level = float(self.total_ob.get_pixels().max(dim=-1).values.double().mean())
-        return capi.DenoiseParams(sigma_color=DENOISE_SIGMA_K * level if level > 0 else 1.0)
+        """The shipped defaults; sigma_color = DENOISE_SIGMA_K x the mean over pixels of the largest channel of the image -- of
+        irradiance() on a track_demod driver, whose filter runs on that image, with demodulate = 0."""
+        img = self.irradiance() if self.track_demod else self.total_ob.get_pixels()
+        level = float(img.max(dim=-1).values.double().mean())
+        return capi.DenoiseParams(sigma_color=DENOISE_SIGMA_K * level if level > 0 else 1.0, demodulate=0 if self.track_demod else 1)
 
     def noise(self, tile_size=TILE_SIZE):
         """The half-buffer noise estimate of the current accumulator (rgk_noise_estimate_device): {"rel": the frame's relative
@@ -606,6 +674,8 @@ class RenderDriver:
     def denoise(self, params=None, variance=False):
         """The current accumulator's image (data / count, not normalised) through the guided a-trous filter
         (rgk_denoise_device): a (y, x, 3) float32 torch tensor on the device.  The accumulator is not changed.  Root rank only.
+        On a track_demod driver the filter runs on D / n with demodulate = 0 (whatever `params` says) and the result is multiplied by
+        A / n (rgk_remodulate_device): texture detail inside a pixel's footprint never enters the filter.
         variance=True (needs track_noise): the variance-guided filter instead, `params` then a capi.DenoiseVarParams; while fewer
         than two rounds are done there is no estimate yet and the fixed filter with its defaults runs."""
         import torch
@@ -621,6 +691,14 @@ class RenderDriver:
         params = params or self.default_denoise_params()
         out = torch.empty_like(self.total_ob.data)
         torch.cuda.current_stream(self.device).synchronize()
+        if self.track_demod:
+            params = capi.DenoiseParams(params.iterations, params.sigma_color, params.sigma_depth, params.normal_power_log2, 0)
+            filtered = torch.empty_like(out)
+            self.scene.denoise_device(self.cfg.xres, self.cfg.yres, self.demod_ob.data.data_ptr(), self.total_ob.count.data_ptr(),
+                                      a["albedo"].data_ptr(), a["normal"].data_ptr(), a["depth"].data_ptr(), params, filtered.data_ptr())
+            self.scene.remodulate_device(self.cfg.xres, self.cfg.yres, filtered.data_ptr(), self.div_ob.data.data_ptr(), self.total_ob.count.data_ptr(),
+                                         out.data_ptr(), self.albedo_floor)
+            return out
         self.scene.denoise_device(self.cfg.xres, self.cfg.yres, self.total_ob.data.data_ptr(), self.total_ob.count.data_ptr(),
                                   a["albedo"].data_ptr(), a["normal"].data_ptr(), a["depth"].data_ptr(), params, out.data_ptr())
         return out
@@ -679,13 +757,19 @@ class RenderDriver:
         kept: (rgb (yres, xres, 3) float32, support (yres, xres) uint8) tensors on the device; not normalised, the accumulator is not
         changed.  support: 1 where the four bilinear taps served, 2 where the 4 x 4 ring did, 0 where the pixel has the nearest low
         pixel's plain colour.  denoise (a capi.DenoiseParams, or True for the shipped ones): rgb then goes through the guided a-trous filter with the full
-        grid's planes and sample counts of 1 (rgk_denoise_device), as denoise_temporal's blend does.  Root rank only."""
+        grid's planes and sample counts of 1 (rgk_denoise_device), as denoise_temporal's blend does.  Root rank only.
+        On a track_demod driver the low accumulator handed over is D, with demodulate = 0 in the upsampler and in the filter (whatever
+        the parameters say), and the result is multiplied by the full grid's albedo plane through the floor rule
+        (rgk_remodulate_device, albedo_floor the driver's): the full-resolution texture detail comes back without a division of a
+        box-averaged radiance by a centre-ray albedo."""
         import torch
         if self.rank != 0:
             return None
         if self.aov_hops > 0:
             raise ValueError("upsample cannot be combined with aov_hops > 0: both grids are tested against first-hit geometry")
         params = (params or self.default_upsample_params()).check()
+        if self.track_demod:
+            params = capi.UpsampleParams(params.plane_tol, params.normal_cos, 0, params.albedo_floor)
         low = self.render_aov()
         key = (bytes(camera), int(xres), int(yres))
         if getattr(self, "_up_key", None) != key:
@@ -703,18 +787,25 @@ class RenderDriver:
         support = torch.empty((yres, xres), dtype=torch.uint8, device=self.device)
         torch.cuda.current_stream(self.device).synchronize()
         self.scene.upsample_device(xres, yres, camera, full["albedo"].data_ptr(), full["normal"].data_ptr(), full["depth"].data_ptr(),
-                                   self.cfg.xres, self.cfg.yres, self.camera, self.total_ob.data.data_ptr(), self.total_ob.count.data_ptr(),
+                                   self.cfg.xres, self.cfg.yres, self.camera, (self.demod_ob if self.track_demod else self.total_ob).data.data_ptr(), self.total_ob.count.data_ptr(),
                                    low["albedo"].data_ptr(), low["normal"].data_ptr(), low["depth"].data_ptr(), params, out.data_ptr(), support.data_ptr())
         if denoise is True:  # the shipped defaults, sigma_color from the upsampled image as default_denoise_params takes it from the accumulator's
             level = float(out.max(dim=-1).values.double().mean())
             denoise = capi.DenoiseParams(sigma_color=DENOISE_SIGMA_K * level if level > 0 else 1.0)
         if denoise is not None and denoise is not False:
+            if self.track_demod:
+                denoise = capi.DenoiseParams(denoise.iterations, denoise.sigma_color, denoise.sigma_depth, denoise.normal_power_log2, 0)
             ones = torch.ones((yres, xres), dtype=torch.int32, device=self.device)
             filtered = torch.empty_like(out)
             torch.cuda.current_stream(self.device).synchronize()
             self.scene.denoise_device(xres, yres, out.data_ptr(), ones.data_ptr(), full["albedo"].data_ptr(), full["normal"].data_ptr(), full["depth"].data_ptr(),
                                       denoise, filtered.data_ptr())
             out = filtered
+        if self.track_demod:
+            remod = torch.empty_like(out)
+            torch.cuda.current_stream(self.device).synchronize()
+            self.scene.remodulate_device(xres, yres, out.data_ptr(), full["albedo"].data_ptr(), None, remod.data_ptr(), self.albedo_floor)
+            out = remod
         return out, support
 
     def save_checkpoint(self, path):
@@ -724,15 +815,28 @@ class RenderDriver:
         self.total_ob.save(path, *state)
         if self.track_noise:
             self.half_ob.save(str(path) + ".half", *state)
+        if self.track_demod:  # `<path>.demod` (D) and `<path>.div` (A): same format, same tag, total_ob's sample counts
+            for ob, suffix in ((self.demod_ob, ".demod"), (self.div_ob, ".div")):
+                ob.count.copy_(self.total_ob.count)
+                ob.save(str(path) + suffix, *state)
 
     def load_checkpoint(self, path):
         """Resume: the next render_round continues the seed sequence where the saved run stopped.  With track_noise the
-        half-buffer `<path>.half` must be there: without it S != S_A + S_B and the estimate would be silently wrong."""
+        half-buffer `<path>.half` must be there: without it S != S_A + S_B and the estimate would be silently wrong.  With track_demod
+        `<path>.demod` and `<path>.div` must be there for the same reason: D and A would cover fewer samples than the count says."""
         import os
         half = str(path) + ".half"
         if self.track_noise and not os.path.exists(half):
             raise RuntimeError(missing_half_message(path))
+        if self.track_demod:
+            for suffix in (".demod", ".div"):
+                if not os.path.exists(str(path) + suffix):
+                    raise RuntimeError(missing_demod_message(path, suffix))
         rounds_done, seedcount = self.total_ob.load(path, self.scene.device, self.checkpoint_tag)
+        if self.track_demod:
+            for ob, suffix in ((self.demod_ob, ".demod"), (self.div_ob, ".div")):
+                if ob.load(str(path) + suffix, self.scene.device, self.checkpoint_tag) != (rounds_done, seedcount):
+                    raise RuntimeError(f"`{path}{suffix}` was not written together with `{path}`")
         if self.track_noise:
             if self.half_ob.load(half, self.scene.device, self.checkpoint_tag) != (rounds_done, seedcount):
                 raise RuntimeError(f"`{half}` was not written together with `{path}`")
@@ -775,7 +879,8 @@ class RenderDriver:
         return yes
 
     def render_frame(self, rounds=None, minutes=None, output_file=None, checkpoint=None, aov_files=None, denoised_file=None,
-                     until_noise=None, noise_file=None, on_noise=None, temporal=False, upsampled_file=None, upsample_to=None):
+                     until_noise=None, noise_file=None, on_noise=None, temporal=False, upsampled_file=None, upsample_to=None,
+                     irradiance_file=None):
         """RenderFrame: Rounds mode (render_driver.cpp:229-235) or Timed mode (:237-247); with `output_file` the
         normalised image is rewritten after every round, as the reference does (rank 0 only).
         aov_files: {"albedo" / "normal" / "depth" / "hops": path} -- the feature planes, written once (depth and hops replicated to
@@ -793,7 +898,10 @@ class RenderDriver:
         single-frame filter's as without it.
         upsampled_file with upsample_to = (camera, xres, yres): after every round that rewrites output_file, upsample() to that grid,
         scaled like output_file; filtered with the shipped denoise defaults when there is a denoised_file (which itself stays this
-        driver's own resolution).  Not with noise tracking, a history or aov_hops."""
+        driver's own resolution).  Not with noise tracking, a history or aov_hops.
+        irradiance_file (a track_demod driver): irradiance(), scaled like output_file, after every round that rewrites output_file."""
+        if irradiance_file and (not self.track_demod or not output_file):
+            raise ValueError("irradiance_file needs a driver made with track_demod=True and an output_file")
         if upsampled_file and (upsample_to is None or not output_file or self.track_noise or self.history is not None or self.aov_hops > 0):
             raise ValueError("upsampled_file needs upsample_to=(camera, xres, yres) and an output_file, on a driver without track_noise, history or aov_hops")
         if temporal and (self.history is None or not denoised_file):
@@ -831,6 +939,8 @@ class RenderDriver:
                         write_exr(noise_file, (var.sqrt() * val).unsqueeze(-1).expand(-1, -1, 3).cpu().numpy())
                 elif denoised_file:
                     write_exr(denoised_file, (self.denoise() * val).cpu().numpy())
+                if irradiance_file:
+                    write_exr(irradiance_file, (self.irradiance() * val).cpu().numpy())
                 if upsampled_file:
                     write_exr(upsampled_file, (self.upsample(*upsample_to, denoise=True if denoised_file else None)[0] * val).cpu().numpy())
             if checkpoint and self.rank == 0:
