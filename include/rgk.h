@@ -503,7 +503,9 @@ int rgk_denoise_device(rgk_scene *scene, uint32_t xres, uint32_t yres, const flo
  * which = 7: the last rgk_upsample_device -- {k_us_prepare, k_us_gather}.
  * which = 8: the last rgk_remodulate_device -- {k_remodulate}.
  * which = 9: the last rgk_render_round_demod_device -- {its k_demod_divisor launches, its k_resolve_demod launches}, each summed
- * over the round's passes (the round's other launches: rgk_counters with RGK_FLAG_TIME_KERNELS). */
+ * over the round's passes (the round's other launches: rgk_counters with RGK_FLAG_TIME_KERNELS).
+ * which = 10: the last rgk_display_measure_device -- {the clear of the histogram, k_display_hist}.
+ * which = 11: the last rgk_display_encode_device -- {k_display_encode}. */
 int rgk_scene_get_post_timing(const rgk_scene *scene, uint32_t which, double *ms, uint32_t *n);
 
 /* ---- noise estimate from two half-buffers and the variance-guided filter (DESIGN.md "Half-buffer noise estimate") ----
@@ -723,6 +725,82 @@ int rgk_remodulate_device(rgk_scene *scene, uint32_t xres, uint32_t yres, const 
                           const float *d_div_rgb /*3P*/, const uint32_t *d_div_count /* P, or NULL: d_div_rgb is an albedo plane */,
                           float albedo_floor, float *d_out_rgb /*3P*/);
 
+/* ---- display output: auto exposure, tone mapping, sRGB bytes (DESIGN.md "Display output") ----
+ *
+ * From a radiance image to a picture a viewer shows: a histogram of the luminances (measure, device), an exposure and a white point
+ * from it (solve, host, integers up to the last step), and per pixel the exposure, a tone curve and the sRGB transfer function to
+ * 8 bits (encode, device).  Everything on the device is float32 with + - * / min max and integer operations on float bit patterns,
+ * no contraction and no transcendental function, so a numpy restatement in the same order gives the same bits
+ * (tests/display_ref.py); bits of a float f: its 32-bit pattern as an unsigned integer.
+ *
+ * Per pixel, the input colour:
+ *   with a count plane:  c = rgb / (float)count per channel, 0 where the count is 0
+ *   d_count == NULL (an image that is a mean already: a denoised or an upsampled one):  c = rgb
+ *   then per channel  c = c > 0 ? c : 0          (NaN and negatives become 0; +inf stays)
+ *   Y = (0.2126f * c.r + 0.7152f * c.g) + 0.0722f * c.b
+ *
+ * Measure: a 256-bin histogram of Y, 8 bins per octave over [2^-20, 2^12), from the bits:
+ *   Y > 0 (+inf too):  bin = clamp((int)(bits of Y >> 20) - ((127 - 20) << 3), 0, 255), hist[bin] += 1
+ *   Y == 0:            not binned, n_dark += 1
+ * so luminances below 2^-20 fall into bin 0 and those from 2^12 on into bin 255.  Lower edge of a bin: the float whose bits are
+ * (bin + ((127 - 20) << 3)) << 20; upper edge: the lower edge of bin + 1 (4096 for bin 255).  Counts are uint32, added as
+ * integers: the histogram does not depend on the order the pixels are visited in.
+ *
+ * Solve, from the histogram alone:  N = sum of hist (n_lit);  N == 0: y_median = y_white = 0, exposure 1, white 1 -- unless fixed
+ * ones are given, below.  Else, in 64-bit integers, rank_m = (N + 1) / 2 and rank_w = max(1, (N * white_permille + 999) / 1000);
+ * the bin holding rank r is the first bin b whose running sum hist[0] + .. + hist[b] reaches r.
+ *   y_white  = the upper edge of the bin holding rank_w
+ *   y_median = lo + (hi - lo) * (((float)(rank_m - before) - 0.5f) / (float)hist[b]),  b the bin holding rank_m, lo / hi its edges,
+ *              before = hist[0] + .. + hist[b - 1]
+ *   exposure = params->exposure > 0 ? params->exposure : key / y_median
+ *   white    = params->white > 0 ? params->white : max(exposure * y_white, 1)
+ *
+ * Encode, per channel:  x = min(exposure * c, 65504.0f), and the operator takes x to v:
+ *   RGK_DISPLAY_LINEAR    v = min(x, 1)
+ *   RGK_DISPLAY_REINHARD  L = the luminance of x by the formula of Y;  s = (1 + L / (white * white)) / (1 + L);  v = min(x * s, 1)
+ *   RGK_DISPLAY_FILMIC    v = min((x * (2.51f * x + 0.03f)) / (x * (2.43f * x + 0.59f) + 0.14f), 1)
+ *   byte = the number of k in 1 .. 255 with v >= T[k]
+ * T is the table of the display entry below: T[0] = 0, T[k] = (float)srgb_to_linear((k - 0.5) / 255) for k = 1 .. 255, built once
+ * on the host in double (srgb_to_linear(s) = s <= 0.04045 ? s / 12.92 : pow((s + 0.055) / 1.055, 2.4)): the thresholds at which
+ * the rounded sRGB byte changes.  The table IS the transfer function here; the device only compares against it.  Output: one uint32
+ * per pixel whose bytes in memory order are R, G, B, 255. */
+#define RGK_DISPLAY_LINEAR 0
+#define RGK_DISPLAY_REINHARD 1
+#define RGK_DISPLAY_FILMIC 2
+typedef struct rgk_display_params {
+    uint32_t op;             /* RGK_DISPLAY_* */
+    float exposure;          /* > 0: this scale; <= 0: automatic, key / y_median.  Finite */
+    float key;               /* > 0, finite: the value the median luminance is taken to (0.18) */
+    uint32_t white_permille; /* 1 .. 1000: the share of the lit pixels at or below the white point (995) */
+    float white;             /* > 0: this white point for RGK_DISPLAY_REINHARD; <= 0: from the measurement.  Finite */
+} rgk_display_params;
+typedef struct rgk_display_stats {
+    uint32_t hist[256];
+    uint32_t n_lit, n_dark;  /* pixels binned, pixels with Y == 0 */
+    float y_median, y_white, exposure, white;
+} rgk_display_stats;
+/* T: 256 floats, strictly increasing; the library's own storage, valid for the life of the process.  No device is touched. */
+const float *rgk_display_table(void);
+/* The solve above on a host histogram of 256 counts; fills every member of *stats (hist and n_dark copied).  HOST only: no scene,
+ * no device.  RGK_ERR_INVALID: a NULL pointer, op none of the three, key not finite and > 0, exposure or white not finite,
+ * white_permille outside 1 .. 1000, counts whose sum does not fit 32 bits. */
+int rgk_display_solve(const uint32_t *hist /*256*/, uint32_t n_dark, const rgk_display_params *params, rgk_display_stats *stats);
+/* Measure + solve of a whole frame: d_rgb 3P floats, d_count P counts or NULL, DEVICE pointers on the scene's GPU, P = xres * yres,
+ * row-major from the top row; *stats is host memory.  The histogram buffer is the scene's own, cleared on the scene's stream before
+ * the one launch that fills it; blocking.  Arguments are checked before the scene or the device is touched (what the solve
+ * refuses, NULL scene / d_rgb / stats, xres, yres in 1 .. 65535); not while a round is in flight on this scene.  Uses no buffer, list
+ * or counter a round reads or writes. */
+int rgk_display_measure_device(rgk_scene *scene, uint32_t xres, uint32_t yres, const float *d_rgb /*3P*/,
+                               const uint32_t *d_count /* P, or NULL: d_rgb is a mean */, const rgk_display_params *params,
+                               rgk_display_stats *stats);
+/* Encode of a whole frame with params->op, stats->exposure and stats->white (no other member of *stats is read; a caller may fill
+ * the two by hand): d_out_rgba P uint32 words, a DEVICE pointer, neither d_rgb nor d_count.  One launch on the scene's stream; blocking.
+ * Checked first, as above, and: stats->exposure and stats->white finite and > 0.  The table is uploaded to a buffer of the scene
+ * by the scene's first call. */
+int rgk_display_encode_device(rgk_scene *scene, uint32_t xres, uint32_t yres, const float *d_rgb /*3P*/,
+                              const uint32_t *d_count /* P, or NULL */, const rgk_display_params *params,
+                              const rgk_display_stats *stats, uint32_t *d_out_rgba /*P*/);
+
 /* The pinned transcendental functions of the path (include/rgk_libm.h) evaluated on the device, for the test that the GPU
  * and the CPU produce the same bits: fn 0 sin, 1 cos, 2 acos, 3 asin, 4 atan2(a[i], b[i]) (b may be NULL otherwise). */
 int rgk_libm_eval(int fn, uint32_t n, const float *a, const float *b, float *out);
@@ -746,6 +824,14 @@ int rgk_output_normalize(const float *accum_rgb, const uint32_t *accum_count, ui
  * to nearest even, overflow to infinity).  Written uncompressed; the reference's RgbaOutputFile default is PIZ --
  * the same pixels in another container encoding. */
 int rgk_output_write_exr(const char *path, uint32_t xres, uint32_t yres, const float *rgb);
+
+/* An 8-bit truecolour PNG (colour type 2) of rgba -- xres * yres words as rgk_display_encode_device writes them, HOST memory; bytes
+ * R, G, B of each word are stored, the fourth is dropped.  Filter 0 on every row; the zlib stream is stored (uncompressed)
+ * deflate blocks of at most 65535 bytes, CRC-32 and Adler-32 computed here: no dependency, as the EXR writer above has none, and
+ * 3 bytes per pixel on disk.  One IDAT chunk: the stream must stay below 2^31 bytes (about 26,700 x 26,700 pixels).
+ * RGK_ERR_INVALID: a NULL pointer, an empty image, a side above 2^31 - 1, an image beyond that size, a path that cannot be
+ * opened; RGK_ERR_DEVICE: a short write. */
+int rgk_output_write_png(const char *path, uint32_t xres, uint32_t yres, const uint32_t *rgba);
 
 /* float -> IEEE half bits exactly as the writer stores them (exposed for the tests). */
 uint16_t rgk_float_to_half(float v);

@@ -51,6 +51,14 @@
                     after every round that rewrites the output.  With --checkpoint the two sums are saved beside it as `F.demod`
                     and `F.div`; resuming a checkpoint that has none is refused.  Not with --noise, --until-noise, --adaptive,
                     --temporal, --aov-hops, -d or bidirectional rounds ("reverse" > 0).  Without the switch every file is unchanged
+  --png [OP]        also writes a picture a viewer can show: beside the output and, with --denoise and --upsample, beside the `denoised`
+                    and `upsampled` files, an 8-bit sRGB PNG of the same stem after every round that rewrites them.  Made from the
+                    image before its brightness scale: automatic exposure (the median luminance of the lit pixels goes to 0.18),
+                    the tone curve OP = linear (clip at 1), reinhard (luminance, white point at the 99.5th percentile) or filmic
+                    (default; per channel), then the sRGB transfer function.  Exposure and white point are measured on the
+                    accumulator and shared by the pictures of a round, per frame under -r.  Give FILE first, or write --png=OP.
+                    Not with -d.  Without the switch every file is unchanged
+  --exposure EV     needs --png: a fixed exposure scale of 2^EV (-100 .. 100) instead of the automatic one
 FILE is a .json or .rtc scene config.  One process drives one GPU; several GPUs: python -m torch.distributed.run ... bench.py.
 """
 import argparse
@@ -118,6 +126,8 @@ def main(argv=None):
     ap.add_argument("--aov-hops", type=int, default=None, metavar="K")
     ap.add_argument("--upsample", action="store_true")
     ap.add_argument("--demod", action="store_true")
+    ap.add_argument("--png", nargs="?", const="filmic", default=None, choices=sorted(capi.DISPLAY_OPS), metavar="OP")
+    ap.add_argument("--exposure", type=float, default=None, metavar="EV")
     args = ap.parse_args(argv)
     verbosity = max(0, 2 + args.v - args.q)
     say = lambda lvl, *a: print(*a) if verbosity >= lvl else None
@@ -156,6 +166,15 @@ def main(argv=None):
         if clash:
             print(f"ERROR: --demod cannot be combined with {clash[0]}.")
             return 1
+    display = None
+    if args.exposure is not None and (args.png is None or not -100.0 <= args.exposure <= 100.0):  # (false for NaN)
+        print("ERROR: --exposure needs --png." if args.png is None else "ERROR: Invalid argument for --exposure (-100 to 100).")
+        return 1
+    if args.png is not None:
+        if args.debug is not None:
+            print("ERROR: --png cannot be combined with -d.")
+            return 1
+        display = capi.DisplayParams(op=capi.DISPLAY_OPS[args.png], exposure=2.0 ** args.exposure if args.exposure is not None else 0.0)
     try:
         cfg = load_config(args.file)
     except ConfigFileException as e:
@@ -270,10 +289,14 @@ def main(argv=None):
                              denoised_file=insert_file_suffix(out, "denoised") if args.denoise else None, temporal=args.temporal,
                              **(dict(upsampled_file=insert_file_suffix(out, "upsampled"), upsample_to=upsample_to) if args.upsample else {}),
                              **(dict(irradiance_file=insert_file_suffix(out, "irradiance")) if args.demod else {}),
+                             **(dict(display=display) if display is not None else {}),
                              **(dict(until_noise=args.until_noise, noise_file=insert_file_suffix(out, "noise"),
                                      on_noise=lambda r, rel, n_live=None: say(1, f"Round {r}: " + (f"{n_live} live tiles, " if n_live is not None else "") +
                                                                                   f"relative noise {rel:.4g}")) if track_noise else {}))
             mon.rays_done = sum(c.path_rays for c in drv.counters)
+        if display is not None and drv.display_stats is not None:
+            st = drv.display_stats
+            say(2, f"Display: exposure {st.exposure:.9g} white {st.white:.9g} (median luminance {st.y_median:.9g}, {st.n_lit} lit and {st.n_dark} black pixels)")
     return 0
 
 

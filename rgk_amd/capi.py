@@ -212,6 +212,40 @@ class UpsampleParams(C.Structure):
         return self
 
 
+DISPLAY_LINEAR, DISPLAY_REINHARD, DISPLAY_FILMIC = 0, 1, 2  # RGK_DISPLAY_*
+DISPLAY_OPS = {"linear": DISPLAY_LINEAR, "reinhard": DISPLAY_REINHARD, "filmic": DISPLAY_FILMIC}
+
+
+class DisplayParams(C.Structure):
+    """rgk_display_params: the tone curve, the exposure (> 0: fixed; <= 0: key / the median luminance) and the white point of the
+    Reinhard curve (> 0: fixed; <= 0: exposure x the luminance below which white_permille of the lit pixels lie, at least 1).  The
+    defaults are stated choices -- the customary middle-grey key 0.18, and the top half per cent of the lit pixels above white -- not tuned values."""
+    _fields_ = [("op", C.c_uint32), ("exposure", C.c_float), ("key", C.c_float), ("white_permille", C.c_uint32), ("white", C.c_float)]
+
+    def __init__(self, op=DISPLAY_FILMIC, exposure=0.0, key=0.18, white_permille=995, white=0.0):
+        super().__init__(op, exposure, key, white_permille, white)
+
+    def check(self):
+        """The ranges the entries enforce, as a ValueError before anything is launched."""
+        import math
+        if self.op not in (DISPLAY_LINEAR, DISPLAY_REINHARD, DISPLAY_FILMIC):
+            raise ValueError(f"display op must be one of {sorted(DISPLAY_OPS)} (0, 1, 2), got {self.op}")
+        if not (math.isfinite(self.exposure) and math.isfinite(self.white)):
+            raise ValueError("display exposure and white must be finite")
+        if not (math.isfinite(self.key) and self.key > 0):
+            raise ValueError("display key must be > 0 and finite")
+        if not 1 <= self.white_permille <= 1000:
+            raise ValueError("display white_permille must be 1 .. 1000")
+        return self
+
+
+class DisplayStats(C.Structure):
+    """rgk_display_stats: the luminance histogram (8 bins per octave from 2^-20), the lit and the black pixels, and what the solve made
+    of them; an encode reads exposure and white alone."""
+    _fields_ = [("hist", C.c_uint32 * 256), ("n_lit", C.c_uint32), ("n_dark", C.c_uint32),
+                ("y_median", C.c_float), ("y_white", C.c_float), ("exposure", C.c_float), ("white", C.c_float)]
+
+
 # every symbol include/rgk.h declares (tests check the .so exports all of them)
 EXPORTS = ["rgk_last_error", "rgk_device_count", "rgk_scene_create", "rgk_scene_destroy",
            "rgk_scene_get_info", "rgk_scene_get_progress", "rgk_scene_set_tuning", "rgk_scene_refit", "rgk_generate_task_list", "rgk_camera_init", "rgk_render_round",
@@ -225,7 +259,8 @@ EXPORTS = ["rgk_last_error", "rgk_device_count", "rgk_scene_create", "rgk_scene_
            "rgk_noise_estimate_device", "rgk_denoise_variance_device", "rgk_adapt_select", "rgk_round_fold_device",
            "rgk_temporal_reproject_device", "rgk_temporal_blend_device",
            "rgk_render_aov_chain_device", "rgk_render_aov_chain", "rgk_debug_poisoned_bytes", "rgk_upsample_device",
-           "rgk_render_round_demod_device", "rgk_remodulate_device"]
+           "rgk_render_round_demod_device", "rgk_remodulate_device",
+           "rgk_display_table", "rgk_display_solve", "rgk_display_measure_device", "rgk_display_encode_device", "rgk_output_write_png"]
 AOV_MAX_HOPS = 8  # RGK_AOV_MAX_HOPS
 DEMOD_ALBEDO_FLOOR = 0.02  # the floor demodulated rounds ship with: the temporal and upsample stages' value
 
@@ -305,6 +340,12 @@ def _bind(lib):
     lib.rgk_render_round_demod_device.argtypes = [C.c_void_p, _p(Camera), _p(Params), _p(Tile), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                   C.c_float, _p(Counters)]
     lib.rgk_remodulate_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
+    lib.rgk_display_table.argtypes = []
+    lib.rgk_display_table.restype = _p(C.c_float)
+    lib.rgk_display_solve.argtypes = [C.c_void_p, C.c_uint32, _p(DisplayParams), _p(DisplayStats)]
+    lib.rgk_display_measure_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, _p(DisplayParams), _p(DisplayStats)]
+    lib.rgk_display_encode_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, _p(DisplayParams), _p(DisplayStats), C.c_void_p]
+    lib.rgk_output_write_png.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_void_p]
     lib.rgk_scene_get_post_timing.argtypes =[C.c_void_p, C.c_uint32, _p(C.c_double), _p(C.c_uint32)]
     lib.rgk_float_to_half.argtypes = [C.c_float]
     lib.rgk_float_to_half.restype = C.c_uint16

@@ -164,3 +164,9 @@ void rgk_launch_us_gather(hipStream_t st, const DevCamera& cam, const DevCamera&
 void rgk_launch_demod_divisor(hipStream_t st, const DevScene& sc, const DevCamera& cam, const PassParams& pp, const float4* hit, float albedo_floor, float4* div);
 void rgk_launch_resolve_demod(hipStream_t st, const PassParams& pp, const float4* tot, const float4* div, float4* pixsum2, float* demod_rgb, float* div_rgb);
 void rgk_launch_remodulate(hipStream_t st, size_t P, const float* in_rgb, const float* div_rgb, const uint32_t* div_count, float albedo_floor, float* out_rgb);
+// display output (rgk_post.hip): the histogram of luminances into hist (RGK_DISPLAY_HIST_WORDS words, cleared by the caller on the stream),
+// and the sRGB words; count may be NULL (rgb is a mean); table: the 256 thresholds on the device.  Both pick the four-pixel kernel
+// when the planes are 16-byte aligned (rgk_plan.h rgk_display_vec).
+void rgk_launch_display_hist(hipStream_t st, size_t P, const float* rgb, const uint32_t* count, uint32_t* hist);
+void rgk_launch_display_encode(hipStream_t st, size_t P, const float* rgb, const uint32_t* count, const float* table, uint32_t op, float exposure, float white,
+                               uint32_t* out);

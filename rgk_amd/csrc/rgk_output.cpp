@@ -1,5 +1,5 @@
 // Output path: normalise the accumulator the way RenderFrame does after every round and write
-// the half-float RGBA OpenEXR file.  Host code, no device work: the reference does this once per round on the
+// the half-float RGBA OpenEXR file; and the PNG container of the display stage's bytes.  Host code, no device work: the reference does this once per round on the
 // host as well (src/render_driver.cpp:229-247), O(pixels).
 #include <cmath>
 #include <cstdint>
@@ -109,5 +109,86 @@ extern "C" int rgk_output_write_exr(const char* path, uint32_t xres, uint32_t yr
     const size_t w = std::fwrite(o.b.data(), 1, o.b.size(), f);
     const int rc = std::fclose(f);
     if (w != o.b.size() || rc != 0) return rgk_internal_fail(RGK_ERR_DEVICE, "rgk_output_write_exr: short write");
+    return RGK_OK;
+}
+
+// ---- PNG (rgk.h rgk_output_write_png): 8-bit truecolour, filter 0, stored deflate blocks; the two checksums are the file's own
+namespace {
+uint32_t crc32_of(const uint8_t* p, size_t n, uint32_t crc = 0) { // ISO 3309 / PNG annex D, bit by bit into a table built once
+    static const struct Table {
+        uint32_t t[256];
+        Table() {
+            for (uint32_t i = 0; i < 256; i++) {
+                uint32_t c = i;
+                for (int k = 0; k < 8; k++) c = (c & 1u) ? 0xedb88320u ^ (c >> 1) : c >> 1;
+                t[i] = c;
+            }
+        }
+    } tab;
+    crc = ~crc;
+    for (size_t i = 0; i < n; i++) crc = tab.t[(crc ^ p[i]) & 0xffu] ^ (crc >> 8);
+    return ~crc;
+}
+uint32_t adler32_of(const uint8_t* p, size_t n) { // RFC 1950; 5552: the most bytes whose sums cannot overflow 32 bits before the modulo
+    uint32_t a = 1, b = 0;
+    while (n) {
+        const size_t k = n < 5552 ? n : 5552;
+        for (size_t i = 0; i < k; i++) { a += p[i]; b += a; }
+        a %= 65521u; b %= 65521u;
+        p += k; n -= k;
+    }
+    return (b << 16) | a;
+}
+void be32(std::vector<uint8_t>& o, uint32_t v) { for (int s = 24; s >= 0; s -= 8) o.push_back((uint8_t)(v >> s)); }
+// length, type, data, CRC of type + data
+void png_chunk(std::vector<uint8_t>& o, const char type[4], const std::vector<uint8_t>& data) {
+    be32(o, (uint32_t)data.size());
+    const size_t at = o.size();
+    o.insert(o.end(), type, type + 4);
+    o.insert(o.end(), data.begin(), data.end());
+    be32(o, crc32_of(o.data() + at, o.size() - at));
+}
+} // namespace
+
+extern "C" int rgk_output_write_png(const char* path, uint32_t xres, uint32_t yres, const uint32_t* rgba) {
+    if (!path || !rgba || xres == 0 || yres == 0 || xres > 0x7fffffffu || yres > 0x7fffffffu)
+        return rgk_internal_fail(RGK_ERR_INVALID, "rgk_output_write_png: null argument, or a side that is 0 or above 2^31 - 1");
+    const uint64_t raw_bytes = ((uint64_t)xres * 3 + 1) * yres; // a filter byte and the row's R, G, B bytes, row after row
+    const uint64_t blocks = (raw_bytes + 65534) / 65535;
+    if (2 + raw_bytes + 5 * blocks + 4 > 0x7fffffffull) return rgk_internal_fail(RGK_ERR_INVALID, "rgk_output_write_png: the image does not fit one IDAT chunk");
+    std::vector<uint8_t> raw;
+    raw.reserve((size_t)raw_bytes);
+    for (uint32_t y = 0; y < yres; y++) {
+        raw.push_back(0); // filter 0: none
+        const uint32_t* src = rgba + (size_t)y * xres;
+        for (uint32_t x = 0; x < xres; x++) {
+            raw.push_back((uint8_t)(src[x] & 0xffu));
+            raw.push_back((uint8_t)((src[x] >> 8) & 0xffu));
+            raw.push_back((uint8_t)((src[x] >> 16) & 0xffu));
+        }
+    }
+    std::vector<uint8_t> z;
+    z.reserve(raw.size() + 5 * (size_t)blocks + 6);
+    z.push_back(0x78); z.push_back(0x01); // zlib header: deflate, 32 K window, no preset dictionary (0x7801 is a multiple of 31)
+    for (size_t at = 0; at < raw.size();) {
+        const size_t n = raw.size() - at < 65535 ? raw.size() - at : 65535;
+        z.push_back(at + n == raw.size() ? 1 : 0); // BFINAL, BTYPE 00: stored
+        z.push_back((uint8_t)(n & 0xff)); z.push_back((uint8_t)(n >> 8));
+        z.push_back((uint8_t)(~n & 0xff)); z.push_back((uint8_t)((~n >> 8) & 0xff));
+        z.insert(z.end(), raw.begin() + at, raw.begin() + at + n);
+        at += n;
+    }
+    be32(z, adler32_of(raw.data(), raw.size()));
+    std::vector<uint8_t> o = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a}, ihdr;
+    be32(ihdr, xres); be32(ihdr, yres);
+    for (uint8_t v : {8, 2, 0, 0, 0}) ihdr.push_back(v); // bit depth 8, colour type 2 (truecolour), deflate, adaptive filtering, no interlace
+    png_chunk(o, "IHDR", ihdr);
+    png_chunk(o, "IDAT", z);
+    png_chunk(o, "IEND", {});
+    FILE* f = std::fopen(path, "wb");
+    if (!f) return rgk_internal_fail(RGK_ERR_INVALID, "rgk_output_write_png: cannot open the output file");
+    const size_t w = std::fwrite(o.data(), 1, o.size(), f);
+    const int rc = std::fclose(f);
+    if (w != o.size() || rc != 0) return rgk_internal_fail(RGK_ERR_DEVICE, "rgk_output_write_png: short write");
     return RGK_OK;
 }

@@ -141,6 +141,28 @@ inline RgkGrid2 rgk_nz_tile_grid(uint32_t xres, uint32_t yres, uint32_t tile_siz
     return {(uint32_t)(((uint64_t)xres + tile_size - 1) / tile_size), (uint32_t)(((uint64_t)yres + tile_size - 1) / tile_size)};
 }
 
+// ------------------------------------------------------------------ display output (rgk_post.hip, k_display_hist / k_display_encode)
+// Four pixels per lane when the planes a launch is given (a NULL one does not count) all start on 16-byte boundaries, else one; an
+// item is such a group or one of the P % 4 pixels behind the last group (every pixel when not vectorised).  The grids: workgroups of
+// RGK_POST_BLOCK lanes striding over the items, bounded -- each fills an LDS table (the histogram, the transfer table) once, and
+// every workgroup of the histogram kernel ends with one global integer add per non-empty bin, all workgroups onto the same 257
+// words: its time grows with the workgroups.  Measured at 1920 x 1080 on the Sponza proxy, ms by HIP events, at 256 / 512 / 1024 /
+// 2048 / 4096 workgroups: k_display_hist 0.0155 / 0.0174 / 0.0252 / 0.0429 / 0.0435; k_display_encode (filmic) 0.0292 / 0.0210 /
+// 0.0179 / 0.0169 / 0.0168 (an empty launch between two events reads 0.008).  So one workgroup per CU for the histogram, four for
+// the encode (the last 0.001 ms is not worth a bound that only frames above two million pixels would reach).
+#ifndef RGK_DISPLAY_HIST_WGS
+#define RGK_DISPLAY_HIST_WGS RGK_CUS
+#endif
+#ifndef RGK_DISPLAY_ENCODE_WGS
+#define RGK_DISPLAY_ENCODE_WGS (RGK_CUS * 4)
+#endif
+inline bool rgk_display_vec(const void* a, const void* b, const void* c) { return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15u) == 0; }
+inline size_t rgk_display_items(size_t P, bool vec) { return vec ? P / 4 + P % 4 : P; }
+inline int rgk_display_grid(size_t P, bool vec, int full) {
+    const size_t need = (rgk_display_items(P, vec) + RGK_POST_BLOCK - 1) / RGK_POST_BLOCK;
+    return (int)std::max<size_t>(1, std::min<size_t>((size_t)full, need));
+}
+
 // ------------------------------------------------------------------ the round fold (rgk_post.hip, k_round_fold)
 // Workgroup (i, b) of RGK_POST_BLOCK threads takes band b of listed tile i: its rows [b * RGK_FOLD_ROWS, + RGK_FOLD_ROWS), cut at
 // the tile's height (a band past it is empty: the grid is as high as the list's highest tile needs).  A band of `rows` rows of a

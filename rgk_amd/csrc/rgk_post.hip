@@ -19,6 +19,8 @@
 //                            -> the planes, a delta vertex -> the continuation ray, compacted into the next hop's queue
 //   k_us_prepare             a low-resolution accumulator and its feature planes -> 16-byte tap records {m.rgb, flags}, {x_q}, {n_q}
 //   k_us_gather              the full grid's pixels projected into the low grid: ring 1 (bilinear), ring 2 (4 x 4), nearest
+//   k_display_hist           an image's luminances -> a 256-bin histogram, 8 bins per octave, and the count of black pixels
+//   k_display_encode         an image -> exposure, tone curve, sRGB transfer table -> one R, G, B, 255 word per pixel
 // (tests/noise_ref.py's k_nz_prepare, k_nz_prefilter and k_nz_atrous are k_dn_prepare<true> and k_dn_atrous<VarianceMean / VarianceGuided>)
 //
 // The traversal between raygen and gather is the round's own k_trace_closest (rgk_launch_trace_closest): no second walker.
@@ -26,6 +28,7 @@
 // the same bits (tests/post_ref.py, tests/noise_ref.py).
 #include <hip/hip_runtime.h>
 #include "rgk_device.h"
+#include "rgk_display.h"
 #include "rgk_kernels.h"
 #include "rgk_trace.h" // camera_ray
 
@@ -913,4 +916,97 @@ void rgk_launch_resolve_demod(hipStream_t st, const PassParams& pp, const float4
 }
 void rgk_launch_remodulate(hipStream_t st, size_t P, const float* in_rgb, const float* div_rgb, const uint32_t* div_count, float albedo_floor, float* out_rgb) {
     k_remodulate<0><<<rgk_post_pixel_grid(P), RGK_POST_BLOCK, 0, st>>>(P, in_rgb, div_rgb, div_count, albedo_floor, out_rgb);
+}
+
+// ------------------------------------------------------------------ display output (rgk.h rgk_display_measure_device / rgk_display_encode_device)
+// From radiance to 8-bit sRGB: a luminance histogram for the exposure, then exposure, tone curve and transfer function per pixel.
+// The arithmetic is rgk_display.h's, which the host and the CPU harness include too; float32, + - * / min max and comparisons,
+// nothing contracted, no transcendental function (tests/display_ref.py gives the same bits).
+//   k_display_hist    a bounded grid of 256-lane workgroups striding over the frame (rgk_plan.h: one per CU).  A per-workgroup histogram in LDS (256 bins
+//                     and the dark count), integer LDS adds, then one integer add per non-empty bin per workgroup into the scene's
+//                     histogram, which the host cleared on the stream: integers only, so the order of the adds does not matter.
+//                     Reads 16 B per pixel (12 without a count plane).
+//   k_display_encode  the same striding; the table T in 1 KB of LDS, filled once per workgroup; per channel the curve and the
+//                     8-step search of rgk_display_byte in T.  Reads 16 B, writes 4 B per pixel.
+// VEC: a lane takes four consecutive pixels at a time -- three 16-byte loads of the rgb plane, one of the counts, and for the
+// encode one 16-byte store -- when every plane's base is 16-byte aligned; the frame's last P % 4 pixels, and every pixel of a
+// frame whose planes are not aligned, are taken one per lane.  An item is a group of four or one such pixel.
+// (Templates for the reason k_tp_reproject is one; last in the file, so every earlier kernel keeps its text.)
+struct DisplayItems {
+    size_t groups, items;
+    __device__ DisplayItems(size_t P, bool vec) : groups(vec ? P / 4 : 0), items(groups + (P - 4 * groups)) {}
+};
+
+__device__ __forceinline__ void display_hist_add(uint32_t* s_hist, float r, float g, float b, bool counted, uint32_t n) {
+    const float Y = rgk_display_lum(rgk_display_colour(r, g, b, counted, n));
+    atomicAdd(&s_hist[Y > 0.0f ? rgk_display_bin(Y) : RGK_DISPLAY_BINS], 1u);
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(RGK_POST_BLOCK) void k_display_hist(size_t P, const float* __restrict__ rgb, const uint32_t* __restrict__ count, uint32_t* __restrict__ hist) {
+    __shared__ uint32_t s_hist[RGK_DISPLAY_HIST_WORDS];
+    static_assert(RGK_POST_BLOCK == RGK_DISPLAY_BINS, "a lane per bin");
+    s_hist[threadIdx.x] = 0;
+    if (threadIdx.x == 0) s_hist[RGK_DISPLAY_BINS] = 0;
+    __syncthreads();
+    const DisplayItems it(P, VEC);
+    const bool counted = count != nullptr;
+    for (size_t i = (size_t)blockIdx.x * RGK_POST_BLOCK + threadIdx.x; i < it.items; i += (size_t)gridDim.x * RGK_POST_BLOCK) {
+        if (VEC && i < it.groups) {
+            const float4* q = reinterpret_cast<const float4*>(rgb) + 3 * i;
+            const float4 a = q[0], b = q[1], c = q[2];
+            const uint4 n = counted ? reinterpret_cast<const uint4*>(count)[i] : make_uint4(0u, 0u, 0u, 0u);
+            display_hist_add(s_hist, a.x, a.y, a.z, counted, n.x);
+            display_hist_add(s_hist, a.w, b.x, b.y, counted, n.y);
+            display_hist_add(s_hist, b.z, b.w, c.x, counted, n.z);
+            display_hist_add(s_hist, c.y, c.z, c.w, counted, n.w);
+        } else {
+            const size_t p = 4 * it.groups + (i - it.groups);
+            display_hist_add(s_hist, rgb[3 * p], rgb[3 * p + 1], rgb[3 * p + 2], counted, counted ? count[p] : 0u);
+        }
+    }
+    __syncthreads();
+    const uint32_t v = s_hist[threadIdx.x];
+    if (v) atomicAdd(&hist[threadIdx.x], v);
+    if (threadIdx.x == 0 && s_hist[RGK_DISPLAY_BINS]) atomicAdd(&hist[RGK_DISPLAY_BINS], s_hist[RGK_DISPLAY_BINS]);
+}
+
+__device__ __forceinline__ uint32_t display_encode_pixel(const float* s_T, float r, float g, float b, bool counted, uint32_t n, uint32_t op, float exposure, float white) {
+    return rgk_display_word(s_T, rgk_display_curve(op, rgk_display_colour(r, g, b, counted, n), exposure, white));
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(RGK_POST_BLOCK) void k_display_encode(size_t P, const float* __restrict__ rgb, const uint32_t* __restrict__ count, const float* __restrict__ table,
+                                                                    uint32_t op, float exposure, float white, uint32_t* __restrict__ out) {
+    __shared__ float s_T[RGK_DISPLAY_BINS];
+    static_assert(RGK_POST_BLOCK == RGK_DISPLAY_BINS, "a lane per threshold");
+    s_T[threadIdx.x] = table[threadIdx.x];
+    __syncthreads();
+    const DisplayItems it(P, VEC);
+    const bool counted = count != nullptr;
+    for (size_t i = (size_t)blockIdx.x * RGK_POST_BLOCK + threadIdx.x; i < it.items; i += (size_t)gridDim.x * RGK_POST_BLOCK) {
+        if (VEC && i < it.groups) {
+            const float4* q = reinterpret_cast<const float4*>(rgb) + 3 * i;
+            const float4 a = q[0], b = q[1], c = q[2];
+            const uint4 n = counted ? reinterpret_cast<const uint4*>(count)[i] : make_uint4(0u, 0u, 0u, 0u);
+            uint4 w;
+            w.x = display_encode_pixel(s_T, a.x, a.y, a.z, counted, n.x, op, exposure, white);
+            w.y = display_encode_pixel(s_T, a.w, b.x, b.y, counted, n.y, op, exposure, white);
+            w.z = display_encode_pixel(s_T, b.z, b.w, c.x, counted, n.z, op, exposure, white);
+            w.w = display_encode_pixel(s_T, c.y, c.z, c.w, counted, n.w, op, exposure, white);
+            reinterpret_cast<uint4*>(out)[i] = w;
+        } else {
+            const size_t p = 4 * it.groups + (i - it.groups);
+            out[p] = display_encode_pixel(s_T, rgb[3 * p], rgb[3 * p + 1], rgb[3 * p + 2], counted, counted ? count[p] : 0u, op, exposure, white);
+        }
+    }
+}
+
+void rgk_launch_display_hist(hipStream_t st, size_t P, const float* rgb, const uint32_t* count, uint32_t* hist) {
+    if (rgk_display_vec(rgb, count, nullptr)) k_display_hist<true><<<rgk_display_grid(P, true, RGK_DISPLAY_HIST_WGS), RGK_POST_BLOCK, 0, st>>>(P, rgb, count, hist);
+    else k_display_hist<false><<<rgk_display_grid(P, false, RGK_DISPLAY_HIST_WGS), RGK_POST_BLOCK, 0, st>>>(P, rgb, count, hist);
+}
+void rgk_launch_display_encode(hipStream_t st, size_t P, const float* rgb, const uint32_t* count, const float* table, uint32_t op, float exposure, float white, uint32_t* out) {
+    if (rgk_display_vec(rgb, count, out)) k_display_encode<true><<<rgk_display_grid(P, true, RGK_DISPLAY_ENCODE_WGS), RGK_POST_BLOCK, 0, st>>>(P, rgb, count, table, op, exposure, white, out);
+    else k_display_encode<false><<<rgk_display_grid(P, false, RGK_DISPLAY_ENCODE_WGS), RGK_POST_BLOCK, 0, st>>>(P, rgb, count, table, op, exposure, white, out);
 }

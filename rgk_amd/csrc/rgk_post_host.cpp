@@ -1,10 +1,11 @@
 // The post-processing entries: feature buffers, both denoisers, the noise estimate, tile selection, the round fold, temporal reuse and
-// guided upsampling (kernels: rgk_post.hip).
+// guided upsampling and the display output (kernels: rgk_post.hip).
 #include <algorithm>
 #include <cmath>
 
 #include "rgk_scene_impl.h"
 #include "rgk_adapt.h"
+#include "rgk_display.h"
 
 namespace {
 // HIP events (the scene's pool, from its first) around the launches of one post call, when the scene's "time_post" switch is on.
@@ -138,6 +139,23 @@ int temporal_call(rgk_scene* s, const char* entry, int half, Launch&& launch) {
     pair.resize(2, 0.0);
     pair[half] = v[0];
     v = pair;
+    return RGK_OK;
+}
+
+// ---- display output
+struct DisplayTable {
+    float T[RGK_DISPLAY_BINS];
+    DisplayTable() { rgk_display_build_table(T); }
+};
+const float* display_table() {
+    static const DisplayTable t; // built once, by the first caller
+    return t.T;
+}
+// (every check before the scene or the device is touched)
+int check_display_args(const rgk_scene* s, uint32_t xres, uint32_t yres, const float* d_rgb, const rgk_display_params* p) {
+    if (!s || !d_rgb || !p) return fail(RGK_ERR_INVALID, "null argument");
+    if (int rc = check_frame_size(xres, yres)) return rc;
+    if (const char* why = rgk_display_check_params(p)) return fail(RGK_ERR_INVALID, "display parameters: %s", why);
     return RGK_OK;
 }
 } // namespace
@@ -419,6 +437,57 @@ int rgk_remodulate_device(rgk_scene* s, uint32_t xres, uint32_t yres, const floa
     return post_call(s, "rgk_remodulate_device", POST_REMODULATE, true, [&](PostTimer& tm) -> int {
         if ((rc = tm.mark())) return rc;
         rgk_launch_remodulate(s->stream, (size_t)xres * yres, d_in_rgb, d_div_rgb, d_div_count, albedo_floor, d_out_rgb);
+        return tm.mark();
+    });
+}
+
+const float* rgk_display_table(void) { return display_table(); }
+
+int rgk_display_solve(const uint32_t* hist, uint32_t n_dark, const rgk_display_params* params, rgk_display_stats* stats) {
+    if (!hist || !stats) return fail(RGK_ERR_INVALID, "null argument");
+    if (const char* why = rgk_display_check_params(params)) return fail(RGK_ERR_INVALID, "display parameters: %s", why);
+    if (!rgk_display_solve_hist(hist, n_dark, *params, *stats)) return fail(RGK_ERR_INVALID, "the histogram's counts do not fit 32 bits");
+    return RGK_OK;
+}
+
+int rgk_display_measure_device(rgk_scene* s, uint32_t xres, uint32_t yres, const float* d_rgb, const uint32_t* d_count, const rgk_display_params* params,
+                               rgk_display_stats* stats) {
+    int rc;
+    if (!stats) return fail(RGK_ERR_INVALID, "null argument");
+    if ((rc = check_display_args(s, xres, yres, d_rgb, params))) return rc;
+    const rgk_display_params p = *params;
+    rc = post_call(s, "rgk_display_measure_device", POST_DISPLAY_MEASURE, true, [&](PostTimer& tm) -> int {
+        // The histogram is the entry's own buffer (the library's allocation path: RGK_POISON covers it) and is cleared here, on the
+        // stream, before the launch that adds to it; nothing a round reads or writes.
+        int rc;
+        if ((rc = s->disp_hist.alloc(RGK_DISPLAY_HIST_WORDS)) || (rc = tm.mark())) return rc;
+        HIPCHK(hipMemsetAsync(s->disp_hist.p, 0, RGK_DISPLAY_HIST_WORDS * sizeof(uint32_t), s->stream));
+        if ((rc = tm.mark())) return rc;
+        rgk_launch_display_hist(s->stream, (size_t)xres * yres, d_rgb, d_count, s->disp_hist.p);
+        return tm.mark();
+    });
+    uint32_t h[RGK_DISPLAY_HIST_WORDS];
+    if (rc || (rc = down(h, s->disp_hist, RGK_DISPLAY_HIST_WORDS))) return rc;
+    if (!rgk_display_solve_hist(h, h[RGK_DISPLAY_BINS], p, *stats)) return fail(RGK_ERR_DEVICE, "the histogram's counts do not fit 32 bits"); // (P < 2^32: not reached)
+    return RGK_OK;
+}
+
+int rgk_display_encode_device(rgk_scene* s, uint32_t xres, uint32_t yres, const float* d_rgb, const uint32_t* d_count, const rgk_display_params* params,
+                              const rgk_display_stats* stats, uint32_t* d_out_rgba) {
+    int rc;
+    if (!stats || !d_out_rgba) return fail(RGK_ERR_INVALID, "null argument");
+    if ((rc = check_display_args(s, xres, yres, d_rgb, params))) return rc;
+    if (const char* why = rgk_display_check_scale(stats->exposure, stats->white)) return fail(RGK_ERR_INVALID, "display stats: %s", why);
+    const void* ins[2] = {d_rgb, d_count};
+    const void* outs[1] = {d_out_rgba};
+    if ((rc = check_outputs_apart(ins, 2, outs, 1))) return rc;
+    const uint32_t op = params->op;
+    const float exposure = stats->exposure, white = stats->white;
+    return post_call(s, "rgk_display_encode_device", POST_DISPLAY_ENCODE, true, [&](PostTimer& tm) -> int {
+        int rc;
+        if (!s->disp_table.p && (rc = s->disp_table.upload(display_table(), RGK_DISPLAY_BINS))) return rc; // (a blocking copy: done before the launch is queued)
+        if ((rc = tm.mark())) return rc;
+        rgk_launch_display_encode(s->stream, (size_t)xres * yres, d_rgb, d_count, s->disp_table.p, op, exposure, white, d_out_rgba);
         return tm.mark();
     });
 }

@@ -2,7 +2,7 @@
 //   rgk_scene.cpp      create / refit / tuning / progress, the workspace, task list and camera
 //   rgk_round.cpp      the round driver (rgk_render_round[_device])
 //   rgk_probe.cpp      the unit-level entries the parity tests call
-//   rgk_post_host.cpp  feature pass, denoisers, noise estimate, round fold
+//   rgk_post_host.cpp  feature pass, denoisers, noise estimate, round fold, temporal reuse, upsampling, display output
 // The arithmetic that needs no device is in rgk_round_plan.h, rgk_plan.h, rgk_adapt.h and rgk_commit.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -88,7 +88,7 @@ struct RgkTuning {
 };
 
 // rgk_scene_get_post_timing's `which` (rgk.h): the post-processing call whose launch times a slot holds
-enum PostSlot : uint32_t { POST_AOV = 0, POST_DENOISE = 1, POST_DENOISE_VARIANCE = 2, POST_NOISE = 3, POST_FOLD = 4, POST_TEMPORAL = 5, POST_AOV_CHAIN = 6, POST_UPSAMPLE = 7, POST_REMODULATE = 8, POST_DEMOD_ROUND = 9, POST_SLOTS = 10 };
+enum PostSlot : uint32_t { POST_AOV = 0, POST_DENOISE = 1, POST_DENOISE_VARIANCE = 2, POST_NOISE = 3, POST_FOLD = 4, POST_TEMPORAL = 5, POST_AOV_CHAIN = 6, POST_UPSAMPLE = 7, POST_REMODULATE = 8, POST_DEMOD_ROUND = 9, POST_DISPLAY_MEASURE = 10, POST_DISPLAY_ENCODE = 11, POST_SLOTS = 12 };
 constexpr uint32_t RGK_SCENE_MAGIC = 0x53474b52u; // "RKGS": what a live scene handle starts with (rgk_scene_get_post_timing)
 struct rgk_scene {
     uint32_t magic = RGK_SCENE_MAGIC;
@@ -155,6 +155,9 @@ struct rgk_scene {
     // demodulated rounds (rgk_render_round_demod_device), allocated by the first one; beside the workspace, not part of its table
     DevBuf<float4> demod_div;           // per path slot of a pass: the sample's divisor {div.rgb, 0} (k_demod_divisor), `batch` entries
     DevBuf<float4> demod_pixsum;        // per pixel of the round: {Dsum}, {Asum} carried across sample passes (k_resolve_demod)
+    // display output (rgk_display_measure_device / rgk_display_encode_device), allocated by the first call of either
+    DevBuf<uint32_t> disp_hist;         // 256 bins, then the dark count; cleared on the stream by every measure before its launch
+    DevBuf<float> disp_table;           // the 256 thresholds of the sRGB bytes (rgk_display_table), uploaded once
     std::vector<double> post_ms[POST_SLOTS]; // launch times of the last call of each kind (tuning "time_post")
     std::vector<hipEvent_t> events;
     uint32_t* h_counters = nullptr; // pinned

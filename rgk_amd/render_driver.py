@@ -237,11 +237,27 @@ class Scene:
         albedo plane); DEVICE pointers (ints), the output none of the inputs."""
         capi.check(self.lib, self.lib.rgk_remodulate_device(self.h, xres, yres, d_in_rgb, d_div_rgb, d_div_count, albedo_floor, d_out_rgb))
 
+    def display_measure_device(self, xres, yres, d_rgb, d_count, params):
+        """rgk_display_measure_device: the luminance histogram of a frame and the exposure and white point solved from it, a
+        capi.DisplayStats; DEVICE pointers (ints), d_count None for an image that is a mean already, params a capi.DisplayParams (its
+        ranges are checked here first: ValueError)."""
+        params.check()
+        stats = capi.DisplayStats()
+        capi.check(self.lib, self.lib.rgk_display_measure_device(self.h, xres, yres, d_rgb, d_count, C.byref(params), C.byref(stats)))
+        return stats
+
+    def display_encode_device(self, xres, yres, d_rgb, d_count, params, stats, d_out_rgba):
+        """rgk_display_encode_device: params.op with stats.exposure and stats.white -> one R, G, B, 255 word per pixel at d_out_rgba;
+        DEVICE pointers (ints), d_count None for an image that is a mean already."""
+        params.check()
+        capi.check(self.lib, self.lib.rgk_display_encode_device(self.h, xres, yres, d_rgb, d_count, C.byref(params), C.byref(stats), d_out_rgba))
+
     def post_timing(self, which):
         """HIP-event times (ms) of the launches of the last feature pass (0) / denoise call (1) / variance-guided denoise call (2) /
         noise estimate (3) / round fold (4: the copy of its tile list, the fold) / temporal pair (5: reproject, blend) /
         followed feature pass (6: list + ray generation, then walker and k_aov_hop per hop) / upsample call (7: prepare, gather) /
-        remodulate call (8) / demodulated round (9: its divisor launches, its second resolves, summed over the passes);
+        remodulate call (8) / demodulated round (9: its divisor launches, its second resolves, summed over the passes) /
+        display measure (10: the clear of the histogram, k_display_hist) / display encode (11: k_display_encode);
         set_tuning(time_post=1) first."""
         ms, n = (C.c_double * 32)(), C.c_uint32(32)
         capi.check(self.lib, self.lib.rgk_scene_get_post_timing(self.h, which, ms, C.byref(n)))
@@ -315,6 +331,41 @@ def write_exr(path, rgb):
     lib = capi.load_product()
     rgb = np.ascontiguousarray(rgb, dtype=np.float32)
     capi.check(lib, lib.rgk_output_write_exr(str(path).encode(), rgb.shape[1], rgb.shape[0], rgb.ctypes.data))
+
+
+def display_table():
+    """rgk_display_table: the 256 float32 thresholds of the sRGB bytes (a copy)."""
+    lib = capi.load_product()
+    return np.ctypeslib.as_array(lib.rgk_display_table(), shape=(256,)).copy()
+
+
+def display_solve(hist, n_dark, params):
+    """rgk_display_solve (host only): exposure and white point from a histogram of 256 counts -> capi.DisplayStats."""
+    lib = capi.load_product()
+    h = np.ascontiguousarray(hist, dtype=np.uint32)
+    if h.shape != (256,):
+        raise ValueError(f"256 bins expected, got {h.shape}")
+    stats = capi.DisplayStats()
+    capi.check(lib, lib.rgk_display_solve(h.ctypes.data, int(n_dark), C.byref(params), C.byref(stats)))
+    return stats
+
+
+def write_png(path, rgba):
+    """rgk_output_write_png of a (y, x, 4) uint8 image (R, G, B, anything; a torch tensor or an array): 8-bit truecolour, the fourth
+    byte dropped."""
+    lib = capi.load_product()
+    if hasattr(rgba, "cpu"):
+        rgba = rgba.cpu().numpy()
+    rgba = np.ascontiguousarray(rgba, dtype=np.uint8)
+    if rgba.ndim != 3 or rgba.shape[2] != 4:
+        raise ValueError(f"a (y, x, 4) uint8 image expected, got {rgba.shape}")
+    capi.check(lib, lib.rgk_output_write_png(str(path).encode(), rgba.shape[1], rgba.shape[0], rgba.ctypes.data))
+
+
+def png_beside(path):
+    """The PNG that goes with an EXR: the same stem."""
+    import os
+    return os.path.splitext(str(path))[0] + ".png"
 
 
 class EXRTexture:
@@ -480,6 +531,7 @@ class RenderDriver:
         self.clock = time.time
         self.checkpoint_tag = 0  # digest of scene + camera + parameters (rgk_accum_set_tag); 0: checkpoints are not compared
         self.aov = None  # the frame's feature planes once render_aov() has made them
+        self.display_stats = None  # render_frame(display=...): the capi.DisplayStats of the last rewrite's pictures
         # track_noise: rank 0 keeps a second accumulator, the sum of the ODD rounds (the second, fourth, ...), for the half-buffer
         # noise estimate.  A single-rank driver then renders every round into the per-round accumulator (the one a multi-rank
         # driver has anyway) and one launch over the rendered tiles folds it into total_ob, into half_ob too on odd rounds, and
@@ -808,6 +860,32 @@ class RenderDriver:
             out = remod
         return out, support
 
+    def display(self, image=None, params=None, stats=None):
+        """A display image: exposure, tone curve and the sRGB transfer function to 8 bits (rgk_display_measure_device,
+        rgk_display_encode_device) -> ((y, x, 4) uint8 tensor on the device, bytes R, G, B, 255; the capi.DisplayStats used).
+        image None: the current accumulator (data / count, not normalised; not changed).  Else a (y, x, 3) float32 tensor on the
+        device that is a mean already -- denoise()'s or upsample()'s result, at any resolution.  params: a capi.DisplayParams,
+        default the shipped ones (filmic, automatic exposure).  stats: what an earlier call returned -- its exposure and white are
+        used and nothing is measured, so that several images of one frame are comparable.  Root rank only."""
+        import torch
+        if self.rank != 0:
+            return None
+        params = (params or capi.DisplayParams()).check()
+        if image is None:
+            rgb, count = self.total_ob.data, self.total_ob.count
+        else:
+            if image.dim() != 3 or image.shape[2] != 3 or image.dtype != torch.float32 or not image.is_cuda:
+                raise ValueError("display(image=...) takes a (y, x, 3) float32 tensor on the device")
+            rgb, count = image.contiguous(), None
+        y, x = int(rgb.shape[0]), int(rgb.shape[1])
+        out = torch.empty((y, x, 4), dtype=torch.uint8, device=rgb.device)
+        torch.cuda.current_stream(self.device).synchronize()
+        d_count = None if count is None else count.data_ptr()
+        if stats is None:
+            stats = self.scene.display_measure_device(x, y, rgb.data_ptr(), d_count, params)
+        self.scene.display_encode_device(x, y, rgb.data_ptr(), d_count, params, stats, out.data_ptr())
+        return out, stats
+
     def save_checkpoint(self, path):
         """Raw-accumulator checkpoint (rgk_accum_save): accumulator + rounds done + the running task counter.  With track_noise the
         half-buffer goes beside it as `<path>.half`, same format, same tag."""
@@ -880,7 +958,7 @@ class RenderDriver:
 
     def render_frame(self, rounds=None, minutes=None, output_file=None, checkpoint=None, aov_files=None, denoised_file=None,
                      until_noise=None, noise_file=None, on_noise=None, temporal=False, upsampled_file=None, upsample_to=None,
-                     irradiance_file=None):
+                     irradiance_file=None, display=None):
         """RenderFrame: Rounds mode (render_driver.cpp:229-235) or Timed mode (:237-247); with `output_file` the
         normalised image is rewritten after every round, as the reference does (rank 0 only).
         aov_files: {"albedo" / "normal" / "depth" / "hops": path} -- the feature planes, written once (depth and hops replicated to
@@ -899,7 +977,22 @@ class RenderDriver:
         upsampled_file with upsample_to = (camera, xres, yres): after every round that rewrites output_file, upsample() to that grid,
         scaled like output_file; filtered with the shipped denoise defaults when there is a denoised_file (which itself stays this
         driver's own resolution).  Not with noise tracking, a history or aov_hops.
-        irradiance_file (a track_demod driver): irradiance(), scaled like output_file, after every round that rewrites output_file."""
+        irradiance_file (a track_demod driver): irradiance(), scaled like output_file, after every round that rewrites output_file.
+        display (a capi.DisplayParams; needs output_file): every rewrite of output_file, denoised_file and upsampled_file also writes a
+        PNG of the same stem beside it (png_beside), made by display() from the image BEFORE its normalisation.  Exposure and white
+        point are measured once per rewrite, on the accumulator, and reused for the other two; display_stats keeps the last ones."""
+        if display is not None:
+            if not output_file:
+                raise ValueError("display needs an output_file")
+            display.check()
+        self.display_stats = None
+
+        def picture(path, image=None):
+            """The PNG beside `path`: the accumulator's (which measures), or an image's with the accumulator's exposure."""
+            if display is not None:
+                rgba, st = self.display(image, display, None if image is None else self.display_stats)
+                self.display_stats = st
+                write_png(png_beside(path), rgba)
         if irradiance_file and (not self.track_demod or not output_file):
             raise ValueError("irradiance_file needs a driver made with track_demod=True and an output_file")
         if upsampled_file and (upsample_to is None or not output_file or self.track_noise or self.history is not None or self.aov_hops > 0):
@@ -931,18 +1024,24 @@ class RenderDriver:
             self.render_round(live=live)
             if output_file and self.rank == 0:
                 val = self.total_ob.write(output_file, getattr(self.cfg, "output_scale", -1.0))
+                picture(output_file)
                 if self.track_noise and self.rounds_done >= 2 and (denoised_file or noise_file):
                     den, var = self.denoise_variance()
                     if denoised_file:
                         write_exr(denoised_file, (den * val).cpu().numpy())
+                        picture(denoised_file, den)
                     if noise_file:
                         write_exr(noise_file, (var.sqrt() * val).unsqueeze(-1).expand(-1, -1, 3).cpu().numpy())
                 elif denoised_file:
-                    write_exr(denoised_file, (self.denoise() * val).cpu().numpy())
+                    den = self.denoise()
+                    write_exr(denoised_file, (den * val).cpu().numpy())
+                    picture(denoised_file, den)
                 if irradiance_file:
                     write_exr(irradiance_file, (self.irradiance() * val).cpu().numpy())
                 if upsampled_file:
-                    write_exr(upsampled_file, (self.upsample(*upsample_to, denoise=True if denoised_file else None)[0] * val).cpu().numpy())
+                    up = self.upsample(*upsample_to, denoise=True if denoised_file else None)[0]
+                    write_exr(upsampled_file, (up * val).cpu().numpy())
+                    picture(upsampled_file, up)
             if checkpoint and self.rank == 0:
                 self.save_checkpoint(checkpoint)
             nz = self.noise() if on_noise or until_noise is not None else None
@@ -958,5 +1057,7 @@ class RenderDriver:
             if done:
                 break
         if temporal and val is not None and self.rank == 0:
-            write_exr(denoised_file, (self.denoise_temporal() * val).cpu().numpy())
+            den = self.denoise_temporal()
+            write_exr(denoised_file, (den * val).cpu().numpy())
+            picture(denoised_file, den)
         return self.total_ob
