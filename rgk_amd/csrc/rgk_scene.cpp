@@ -124,6 +124,27 @@ int build_accel(rgk_scene* s, uint32_t build_flags, std::vector<Prim>& prims, co
     return 0;
 }
 
+// Which triangles the tree holds no reference of (commit_triangles leaves out those without a plane).
+void note_unreferenced(rgk_scene* s, const std::vector<Prim>& prims, uint32_t n_triangles) {
+    s->h_no_ref.assign(n_triangles, 1);
+    size_t left = n_triangles;
+    for (const Prim& p : prims)
+        if (s->h_no_ref[p.tri]) { s->h_no_ref[p.tri] = 0; left--; }
+    if (!left) s->h_no_ref.clear();
+}
+
+// Does a triangle that the tree holds no reference of have a plane at the new positions?
+bool unreferenced_triangle_gets_a_plane(const rgk_scene* s, const float* vertices) {
+    for (size_t t = 0; t < s->h_no_ref.size(); t++) {
+        if (!s->h_no_ref[t]) continue;
+        V3 v[3];
+        for (int c = 0; c < 3; c++) { const float* p = vertices + 3 * (size_t)s->h_idx[3 * t + c]; v[c] = V3{p[0], p[1], p[2]}; }
+        const TriIsect r = tri_isect_record(v[0], v[1], v[2], (uint32_t)t);
+        if (r.n[0] == r.n[0] && r.n[1] == r.n[1] && r.n[2] == r.n[2]) return true;
+    }
+    return false;
+}
+
 // Traversal stack: the scene's configuration (rgk_round_plan.h rgk_stack_plan) and its overflow area
 int configure_stack(rgk_scene* s, uint32_t max_stack, const BuildOptions& opt) {
     RgkStackPlan sp;
@@ -198,6 +219,27 @@ int fill_dev_scene(rgk_scene* s, const rgk_scene_desc* d, const AccelInfo& acc, 
     return 0;
 }
 
+// The accelerator built again from moved vertices, as rgk_scene_create builds it: rgk_scene_refit's way out when the old topology
+// lacks a triangle.  The refit that follows recomputes the records and boxes it leaves (the same bits) and the shading records.
+int rebuild_accel(rgk_scene* s, const float* vertices, const float mn[3], const float mx[3], float eps) {
+    std::vector<TriIsect> recs;
+    std::vector<Prim> prims;
+    commit_triangles(vertices, s->h_idx.data(), s->n_triangles, split_threshold(s->build_opt, eps), recs, prims);
+    HostAccel host;
+    AccelInfo acc;
+    int rc;
+    if ((rc = build_accel(s, s->build_flags, prims, recs, mn, mx, eps, s->build_opt, host, acc))) return rc;
+    if ((rc = configure_stack(s, acc.max_stack, s->build_opt))) return rc;
+    if (!acc.on_device && ((rc = s->nodes.upload(host.qnodes.data(), host.qnodes.size())) || (rc = s->tris.upload(host.leaf_recs.data(), host.leaf_recs.size())) ||
+                           (rc = s->leaf_pb.upload(host.leaf_pb.data(), host.leaf_pb.size()))))
+        return rc;
+    s->n_refs = acc.n_refs; s->n_nodes = acc.n_nodes;
+    s->dev.nodes = s->nodes.p; s->dev.tris = s->tris.p;
+    s->info.n_nodes = acc.n_nodes; s->info.max_depth = acc.max_depth; s->info.n_leaf_refs = acc.n_refs;
+    note_unreferenced(s, prims, s->n_triangles);
+    return 0;
+}
+
 } // namespace
 
 extern "C" {
@@ -234,6 +276,8 @@ int rgk_scene_create(const rgk_scene_desc* d, int device, rgk_scene** out) {
     std::vector<TriIsect> recs;
     std::vector<Prim> prims;
     commit_triangles(d->vertices, d->tri_indices, d->n_triangles, split_threshold(opt, eps), recs, prims);
+    s->build_flags = d->build_flags; s->build_opt = opt;
+    note_unreferenced(s, prims, d->n_triangles);
 
     // ---- accelerator and its traversal stack
     HostAccel host;
@@ -263,6 +307,8 @@ int rgk_scene_refit(rgk_scene* s, const float* vertices, const float* normals, c
     int rc;
     float mn[3], mx[3], eps;
     if ((rc = commit_bounds(vertices, s->h_idx.data(), nt, mn, mx, &eps))) return rc;
+    // ---- a triangle the tree has no reference of, and that now has a plane: the tree is built again
+    if (unreferenced_triangle_gets_a_plane(s, vertices) && (rc = rebuild_accel(s, vertices, mn, mx, eps))) return rc;
     // ---- records, shading normals / tangents, and the tree's boxes: on the device
     if ((rc = s->scratch_f.upload(vertices, 3 * (size_t)nv))) return rc;
     DevBuf<float> d_n, d_t;

@@ -122,6 +122,11 @@ struct rgk_scene {
     std::vector<rgk_material> h_mats;
     std::vector<float> h_normals;
     uint32_t n_vertices = 0, n_triangles = 0, n_refs = 0, n_nodes = 0;
+    // ... and of the build: a triangle without a plane (NaN: two equal corners, three on a line) gets no reference, so a refit that
+    // gives one of them a plane cannot find it in the old topology and builds the tree again, with the builder and switches kept here
+    std::vector<uint8_t> h_no_ref; // per triangle: 1 where the tree holds no reference of it; empty when every triangle has one
+    uint32_t build_flags = 0;
+    BuildOptions build_opt;
     uint32_t n_textures = 0, n_materials = 0;
     DevBuf<DevHaltonDim> hdims;
     DevBuf<uint16_t> hperm;

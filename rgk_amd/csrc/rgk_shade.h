@@ -137,6 +137,24 @@ __device__ __forceinline__ f3 slot_add(float4* tot, uint32_t slot, f3 tot0, f3 a
     return tot0;
 }
 
+// An emitting vertex that is also lit: the oracle adds ONE term, A = clamp(NEE + emission) * contribution if the light is visible and
+// B = clamp(emission) * contribution if not, to the sum `prev` of the vertices before.  Here B is added when the vertex is shaded and the
+// shadow ray, if it gets through, adds the rest -- which is (prev + A) - (prev + B) in float32, not A - B: then
+// (prev + B) + rest == prev + A to the bit (A >= B >= 0 channel by channel; above half of prev + A the difference is exact, below it
+// its rounding error stays under half a unit of prev + A), where (prev + B) + (A - B) can end one bit off.
+// Adds B to the slot's sum as slot_add does; `prev`, `now`: the sum before and behind the addition.
+template <bool START>
+__device__ __forceinline__ f3 slot_add_keep(float4* tot, uint32_t slot, f3 tot0, f3 add, f3& prev, f3& now) {
+    if (START) { prev = mk3(0.f, 0.f, 0.f); now = mk3(0.f + add.x, 0.f + add.y, 0.f + add.z); return now; }
+    float4 t = tot[slot];
+    prev = mk3(t.x, t.y, t.z);
+    t.x = t.x + add.x; t.y = t.y + add.y; t.z = t.z + add.z;
+    tot[slot] = t;
+    now = mk3(t.x, t.y, t.z);
+    return tot0;
+}
+__device__ __forceinline__ f3 lit_emitter_rest(f3 prev, f3 now, f3 A) { return (prev + A) - now; }
+
 // ------------------------------------------------------------------ K1: ray generation (camera_ray, camera_ray_of_slot: rgk_trace.h)
 // (Unidirectional rounds have no ray-generation kernel: bounce 0 derives the camera ray from the slot number in the traversal
 // kernel and again in the shading kernel, and the first vertex samples the path's light and starts its sum -- see
@@ -319,10 +337,10 @@ __global__ __launch_bounds__((FIRST ? RGK_SHADE_BLOCK : RGK_SHADE_BLOCK_LATER), 
                         const bool has_e = (e_front.x != 0.f) || (e_front.y != 0.f) || (e_front.z != 0.f);
                         // bidirectional: light vertices to connect to (bits 0..6), or an emitting vertex -> the record route
                         if (BDPT) conn = ((pp.lvmask[slot] & 0x7fu) != 0u) || has_e;
-                        f3 B = mk3(0.f, 0.f, 0.f);
+                        f3 e_prev = mk3(0.f, 0.f, 0.f), e_now = mk3(0.f, 0.f, 0.f); // the slot's sum before and behind the emission's addition
                         if (has_e && !conn) {
-                            B = clamp3(mk3(0.f, 0.f, 0.f) + e_front, pp.clamp) * contribution;
-                            tot0 = slot_add<FIRST && !GENERIC>(tot, slot, tot0, B);
+                            const f3 B = clamp3(mk3(0.f, 0.f, 0.f) + e_front, pp.clamp) * contribution;
+                            tot0 = slot_add_keep<FIRST && !GENERIC>(tot, slot, tot0, B, e_prev, e_now);
                         }
                         f3 out = mk3(0.f, 0.f, 0.f); // NEE radiance before visibility, clamp and contribution
                         if (L.type >= 0 && !nee_dead) {
@@ -337,7 +355,7 @@ __global__ __launch_bounds__((FIRST ? RGK_SHADE_BLOCK : RGK_SHADE_BLOCK_LATER), 
                             out = inc * (f * G);
                             if (!conn) {
                                 f3 A = clamp3((mk3(0.f, 0.f, 0.f) + out) + e_front, pp.clamp) * contribution;
-                                f3 rad = has_e ? A - B : A;
+                                f3 rad = has_e ? lit_emitter_rest(e_prev, e_now, A) : A;
                                 if (rad.x != 0.f || rad.y != 0.f || rad.z != 0.f) {
                                     shadow = true;
                                     if (CL && RGK_CL_REC32) {
@@ -421,7 +439,8 @@ __global__ __launch_bounds__((FIRST ? RGK_SHADE_BLOCK : RGK_SHADE_BLOCK_LATER), 
 //                          `nee_dead` test, the deferral test (the GENERIC launch that follows is k_shade<true, false, false, CL>
 //                          on the list this kernel fills) and the emission's addition; a LIVE vertex -- one whose light is above
 //                          both horizons -- leaves a LastVertex;
-//   last_vertex_nee        LastVertex -> texels, LTC entry, BxDF value, G, the clamp, A - B: the shadow record, if any.
+//   last_vertex_nee        LastVertex -> texels, LTC entry, BxDF value, G, the clamp, a lit emitter's addition (slot_add_keep): the
+//                          shadow record, if any.
 // Bounce rays scatter, so the 64 vertices of a wave are unrelated and under half of them are live (Sponza: 45 % live, 48 % dead,
 // 7 % sky): run back to back per lane -- as k_shade does, and as a one-phase build of this kernel did, which measured no faster than
 // k_shade -- the second half has most lanes of every wave masked off.  k_last_vertex runs the halves as two phases of
@@ -510,17 +529,18 @@ __device__ __forceinline__ bool last_vertex_geometry(const DevScene& sc, const P
     f3 e_front = mk3(0.f, 0.f, 0.f);
     if (front) e_front = mk3(mat.emission[0], mat.emission[1], mat.emission[2]);
     const bool has_e = (e_front.x != 0.f) || (e_front.y != 0.f) || (e_front.z != 0.f);
-    if (has_e) {
+    const bool live = L.type >= 0 && !nee_dead;
+    if (has_e && !live) { // (a live vertex adds its emission in last_vertex_nee, which needs the sum before it: slot_add_keep)
         f3 B = clamp3(mk3(0.f, 0.f, 0.f) + e_front, pp.clamp) * contribution;
         slot_add<false>(tot, slot, tot0, B);
     }
     v.pos = pos; v.lightN = lightN; v.VrL = VrL; v.contribution = contribution; v.g2l = g2l; v.uv = uv;
     v.slot = slot; v.matf = mat_id | (front ? RGK_LV_FRONT : 0u); v.li = li;
-    return L.type >= 0 && !nee_dead;
+    return live;
 }
 // returns: the vertex leaves a shadow ray, sA / sB (/ sC) its record
 template <bool CL>
-__device__ __forceinline__ bool last_vertex_nee(const DevScene& sc, const PassParams& pp, const LastVertex& v, float4& sA, float4& sB, float4& sC) {
+__device__ __forceinline__ bool last_vertex_nee(const DevScene& sc, const PassParams& pp, const LastVertex& v, float4* __restrict__ tot, float4& sA, float4& sB, float4& sC) {
     const float eps = sc.epsilon;
     const uint32_t mat_id = v.matf & ~RGK_LV_FRONT;
     const DevMaterial mat = mat_load(sc, mat_id);
@@ -531,8 +551,8 @@ __device__ __forceinline__ bool last_vertex_nee(const DevScene& sc, const PassPa
     f3 e_front = mk3(0.f, 0.f, 0.f);
     if (v.matf & RGK_LV_FRONT) e_front = mk3(mat.emission[0], mat.emission[1], mat.emission[2]);
     const bool has_e = (e_front.x != 0.f) || (e_front.y != 0.f) || (e_front.z != 0.f);
-    f3 B = mk3(0.f, 0.f, 0.f);
-    if (has_e) B = clamp3(mk3(0.f, 0.f, 0.f) + e_front, pp.clamp) * contribution;
+    f3 e_prev = mk3(0.f, 0.f, 0.f), e_now = mk3(0.f, 0.f, 0.f);
+    if (has_e) slot_add_keep<false>(tot, v.slot, mk3(0.f, 0.f, 0.f), clamp3(mk3(0.f, 0.f, 0.f) + e_front, pp.clamp) * contribution, e_prev, e_now);
     const f3 diff = pos - L.pos;
     const f3 sd = norm3(diff);
     const float slen = len3(diff);
@@ -543,7 +563,7 @@ __device__ __forceinline__ bool last_vertex_nee(const DevScene& sc, const PassPa
     const f3 inc = L.color * mk3(k, k, k);
     const f3 out = inc * (f * G);
     f3 A = clamp3((mk3(0.f, 0.f, 0.f) + out) + e_front, pp.clamp) * contribution;
-    f3 rad = has_e ? A - B : A;
+    f3 rad = has_e ? lit_emitter_rest(e_prev, e_now, A) : A;
     if (!(rad.x != 0.f || rad.y != 0.f || rad.z != 0.f)) return false;
     if (CL && RGK_CL_REC32) {
         sA = cl_rec_a(sd, slen - eps * 20.0f);
@@ -638,7 +658,7 @@ __global__ __launch_bounds__(RGK_SHADE_BLOCK_LATER, 3) void k_last_vertex(const 
             if (threadIdx.x < n) {
                 LastVertex v;
                 last_vertex_get<CL>(pp, s_ring, CAP, rgk_ring_read_at(head, threadIdx.x, BLK), v);
-                shadow = last_vertex_nee<CL>(sc, pp, v, sA, sB, sC);
+                shadow = last_vertex_nee<CL>(sc, pp, v, tot, sA, sB, sC);
             }
             // the workgroup's range of the shadow queue: one atomic
             const unsigned long long ms = __ballot(shadow);

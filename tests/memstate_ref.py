@@ -32,6 +32,7 @@ from rgk_amd.config import make_camera, make_params  # noqa: E402
 
 import chain_ref as CR  # noqa: E402
 import pad_ref as PAD  # noqa: E402
+import refit_cases as RC  # noqa: E402
 import trace_ref as T  # noqa: E402
 
 F = np.float32
@@ -217,10 +218,13 @@ def _libm(rd):
 # ======================================================================= rounds
 class RoundSpec:
     """One render-round case.  oracle_key: the cases that share it render the same round (same scene, camera, parameters and
-    tiles) and are held to ONE oracle round.  make() -> (builder, camera).  builder_name: a key of test_gpu_exhaustive.BUILDERS."""
+    tiles) and are held to ONE oracle round.  make() -> (builder, camera).  builder_name: a key of test_gpu_exhaustive.BUILDERS.
+    refit_from() -> the builder the handle is created from; it is then refitted (rgk_scene_refit with vertices, normals and
+    tangents) to the mesh of make()'s builder, the one the oracle renders."""
 
-    def __init__(self, oracle_key, make, prm, rounds=1, tuning=None, builder_name=None):
+    def __init__(self, oracle_key, make, prm, rounds=1, tuning=None, builder_name=None, refit_from=None):
         self.oracle_key, self.make, self.prm, self.rounds, self.tuning, self.builder_name = oracle_key, make, prm, rounds, tuning or {}, builder_name
+        self.refit_from = refit_from
 
 
 ROUNDS = {}
@@ -235,7 +239,12 @@ def gpu_scene_of(rd, spec, sb):
 
 def run_round(rd, spec):
     sb, cam = spec.make()
-    g = gpu_scene_of(rd, spec, sb)
+    if spec.refit_from:
+        g = gpu_scene_of(rd, spec, spec.refit_from())
+        sb.finalize()
+        g.refit(sb.V, sb.N, sb.T)
+    else:
+        g = gpu_scene_of(rd, spec, sb)
     if spec.tuning:
         g.set_tuning(**spec.tuning)
     tiles = rd.generate_task_list(spec.prm.xres, spec.prm.yres)
@@ -297,6 +306,18 @@ round_case("rounds", "round.small-padded-P60-K3", RoundSpec("small-padded", lamb
 round_case("rounds", "round.cornell-sphere-light", RoundSpec("cornell-sphere", _cornell("point", 0.15), params()))
 round_case("rounds", "round.cornell-emissive-quad", RoundSpec("cornell-quad", _cornell("quad"), params()))
 round_case("rounds", "round.envmap-float-sky", RoundSpec("envmap", _envmap, params()))
+
+
+
+def _refitted_point_scene():
+    c = RC.shade_case(point=True)
+    return RC.with_mesh(c["make"], *c["mesh"]["111"]), c["camera"]
+
+
+# a round on a refitted handle of the constant-light scene: the shading records k_refit_shade rewrote, on the refit's scratch
+for _b in ("host-sah", "device"):
+    round_case("rounds", f"round.refit-shade-{_b}", RoundSpec("refit-shade", _refitted_point_scene, params(), builder_name=_b,
+                                                              refit_from=RC.shade_case(point=True)["make"]))
 
 # bidirectional rounds: the splat order is not repeatable, so these are held to the oracle's terms, never to each other
 round_case("bidirectional", "bidir.small-reverse3", RoundSpec("small-reverse3", _small, params(reverse=3)))
@@ -475,27 +496,32 @@ for _s in ("count257", "duplicates", "deep"):
         case("builder", f"builder.{_s}-{_b}")(_built(_s, _b))
 
 
+def refit_moves(scene):
+    """(() -> builder, [(step, vertices, normals or None, tangents or None)]) of a refit case: a scene of trace_ref.SCENES under the
+    twist and swell of refit_cases.py, positions only; "shade" and "lights" of refit_cases.py, with their normals and tangents."""
+    if scene == "shade":
+        c = RC.shade_case()
+        return c["make"], [("moved",) + c["mesh"]["111"], ("back",) + c["mesh"]["000"]]
+    if scene == "lights":
+        c = RC.lights_case()
+        return c["make"], [("moved",) + c["mesh"]["11"], ("back",) + c["mesh"]["00"]]
+    V0 = T.SCENES[scene]().finalize().V.copy()
+    return T.SCENES[scene], [("moved", RC.twist_and_swell(V0), None, None), ("back", V0, None, None)]
+
+
 @functools.lru_cache(maxsize=None)
 def refit_setup(scene):
     """The moved / back refit of test_refitted_tree_equals_the_exhaustive_search_on_the_moved_mesh, made once per process:
     (builder, [(step, vertices, oracle scene of the moved mesh, rays, a, b)])."""
     from oracle import rgk_oracle as O
-    sb = T.SCENES[scene]()
+    make, moves = refit_moves(scene)
+    sb = make()
     sb.finalize()
-    V0 = sb.V.copy()
-    ctr, ext = V0.mean(axis=0), np.ptp(V0, axis=0).max()
-    ang = 0.35 * (V0[:, 1] - ctr[1]) / ext
-    c, s_ = np.cos(ang), np.sin(ang)
-    V1 = V0.copy()
-    V1[:, 0] = ctr[0] + c * (V0[:, 0] - ctr[0]) - s_ * (V0[:, 2] - ctr[2])
-    V1[:, 2] = ctr[2] + s_ * (V0[:, 0] - ctr[0]) + c * (V0[:, 2] - ctr[2])
-    V1 = (V1 + 0.03 * ext * np.sin(3.0 * V0[:, [1, 2, 0]] / ext)).astype(F)
+    ctr = sb.V.mean(axis=0)
     steps = []
     n = 4097
-    for step, V in (("moved", V1), ("back", V0)):
-        moved = T.SCENES[scene]()
-        moved.finalize()
-        moved.vertices = [V]
+    for step, V, N, Tn in moves:
+        moved = RC.with_mesh(make, V, N, Tn)
         osc = O.OracleScene(moved.to_desc())
         kw = dict(inside=(tuple(ctr), 0.5)) if scene == "closed" else {}
         rays = T.ray_mix(osc, n, seed=7, targets=T.targets_of(moved), **kw)
@@ -508,12 +534,13 @@ def _refitted(scene, builder):
     def run(rd):
         import test_gpu_exhaustive as EX
         sb, steps = refit_setup(scene)
+        attrs = {step: (N, Tn) for step, _, N, Tn in refit_moves(scene)[1]}
         g = EX.gpu_scene(rd, sb, builder)
         i = g.info()
         out = {"info": np.array([i.n_nodes, i.max_depth, i.n_leaf_refs], np.uint32)}
         for step, V, osc, rays, a, b in steps:
             before = poisoned()
-            g.refit(V)
+            g.refit(V, *attrs[step])
             out[f"_poisoned_by_refit.{step}"] = np.array([poisoned() - before], np.uint64)
             out.update(hit_arrays(f"{step}.closest", g.trace_closest(rays)[0]))
             out[f"{step}.visible"] = g.visibility(a, b)[0]
@@ -522,7 +549,7 @@ def _refitted(scene, builder):
     return run
 
 
-REFITS = [(s, b) for s in ("closed", "count257") for b in ("host-sah", "device")]
+REFITS = [(s, b) for s in ("closed", "count257", "shade", "lights") for b in ("host-sah", "device")]
 for _s, _b in REFITS:
     case("builder", f"refit.{_s}-{_b}")(_refitted(_s, _b))
 

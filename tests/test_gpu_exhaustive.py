@@ -200,14 +200,10 @@ def test_refitted_tree_equals_the_exhaustive_search_on_the_moved_mesh(rd, oracle
     and edge midpoints, where a node box one step too tight drops the hit."""
     sb = T.SCENES[scene]()
     sb.finalize()
+    import refit_cases as RC
     V0 = sb.V.copy()
-    ctr, ext = V0.mean(axis=0), np.ptp(V0, axis=0).max()
-    ang = 0.35 * (V0[:, 1] - ctr[1]) / ext
-    c, s_ = np.cos(ang), np.sin(ang)
-    V1 = V0.copy()
-    V1[:, 0] = ctr[0] + c * (V0[:, 0] - ctr[0]) - s_ * (V0[:, 2] - ctr[2])
-    V1[:, 2] = ctr[2] + s_ * (V0[:, 0] - ctr[0]) + c * (V0[:, 2] - ctr[2])
-    V1 = (V1 + 0.03 * ext * np.sin(3.0 * V0[:, [1, 2, 0]] / ext)).astype(np.float32)
+    ctr = V0.mean(axis=0)
+    V1 = RC.twist_and_swell(V0)
     g = gpu_scene(rd, sb, builder)
     for step, V in (("moved", V1), ("back", V0)):
         g.refit(V)

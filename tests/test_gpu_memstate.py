@@ -130,7 +130,8 @@ def test_poisoned_allocations_change_no_bit(rd, tmp_path_factory, family):
     of const_light x last_vertex x beam x entry_points (two rounds of a frame each: the second on capped entry lists), with two
     sample passes, at 5 x 3 x 1 spp depth 1 (queues shorter than a workgroup), the material zoo through a lens at depth 8 without
     roulette, the deep tree on the overflow area, a scene padded past both LDS thresholds, sphere light, emissive quad, float
-    environment map.  post: rgk_render_aov over every other tile (pixels outside keep the sentinel), rgk_render_aov_chain with 8
+    environment map, and the point-light scene on a handle refitted with moved vertices, normals and tangents (k_refit_shade) under
+    both builders.  post: rgk_render_aov over every other tile (pixels outside keep the sentinel), rgk_render_aov_chain with 8
     hops, both denoisers, the noise estimate at tile size 5 with and without the variance plane, the round fold -- the output
     planes of the _device entries start as 0xFF bytes and no written element may still hold them (asserted where they are made)."""
     assert_family_equal(rd, family, tmp_path_factory)
@@ -160,7 +161,8 @@ def hits_of(arrays, prefix):
 
 def test_device_builder_and_refit_on_poisoned_scratch(rd, tmp_path_factory):
     """count257, duplicates and deep under device, device-karras and device-karras-rotate4; closed and count257 through the
-    moved / back refit under host-sah and device.  In both runs: n_nodes, max_depth and n_leaf_refs are the baseline's, and closest
+    moved / back refit under host-sah and device, and the shade and lights cases of refit_cases.py through theirs with normals
+    and tangents.  In both runs: n_nodes, max_depth and n_leaf_refs are the baseline's, and closest
     hits (plain and with the first hit ignored) and visibility bytes equal the exhaustive reference for EVERY ray -- node numbers
     come from atomics, so two builds may differ in their nodes' order, never in an answer.  In the poisoned run the byte total
     rises across rgk_scene_create by at least the builder's scratch arrays, n references x their summed element sizes, and across

@@ -1175,6 +1175,7 @@ def test_refit_equals_a_fresh_scene(rd, oracle):
     scene's, the same image; and refitting back gives the original scene's bits again.  Records what the old topology costs on
     the new positions (node visits per ray, refitted vs rebuilt)."""
     import copy, time
+    import refit_cases as RC
     from rgk_amd.workloads import Workload
     cases = [("box6 (emissive triangles)", scene_fixture("box6", scale=0.1, spp=4)), ("sponza-proxy", Workload("sponza-1080p", scale=0.1, spp=4)),
              ("dragon-sponza-proxy 1.05 M", Workload("dragon-sponza-1080p", scale=0.05, spp=2))]
@@ -1182,14 +1183,8 @@ def test_refit_equals_a_fresh_scene(rd, oracle):
         sb = wl.builder
         sb.finalize()
         V0 = sb.V.copy()
-        ctr, ext = V0.mean(axis=0), np.ptp(V0, axis=0).max()
         # a smooth, non-rigid move: a twist about the vertical axis growing with height + a swell, a few per cent of the scene size
-        ang = 0.25 * (V0[:, 1] - ctr[1]) / ext
-        c, s_ = np.cos(ang), np.sin(ang)
-        V1 = V0.copy()
-        V1[:, 0] = ctr[0] + c * (V0[:, 0] - ctr[0]) - s_ * (V0[:, 2] - ctr[2])
-        V1[:, 2] = ctr[2] + s_ * (V0[:, 0] - ctr[0]) + c * (V0[:, 2] - ctr[2])
-        V1 = (V1 + 0.02 * ext * np.sin(3.0 * V0[:, [1, 2, 0]] / ext)).astype(np.float32)
+        V1 = RC.twist_and_swell(V0, angle=0.25, swell=0.02)
         prm = wl.params()
         tiles = rd.generate_task_list(wl.xres, wl.yres)
         for flags, tag in ((capi.BUILD_HOST_SAH, "host tree"), (capi.BUILD_DEVICE, "device tree")):
