@@ -505,7 +505,9 @@ int rgk_denoise_device(rgk_scene *scene, uint32_t xres, uint32_t yres, const flo
  * which = 9: the last rgk_render_round_demod_device -- {its k_demod_divisor launches, its k_resolve_demod launches}, each summed
  * over the round's passes (the round's other launches: rgk_counters with RGK_FLAG_TIME_KERNELS).
  * which = 10: the last rgk_display_measure_device -- {the clear of the histogram, k_display_hist}.
- * which = 11: the last rgk_display_encode_device -- {k_display_encode}. */
+ * which = 11: the last rgk_display_encode_device -- {k_display_encode}.
+ * which = 12: the last rgk_output_write_exr_device -- {k_out_max and its fold, or 0 with a given scale; k_out_pack_exr}.
+ * which = 13: the last rgk_output_write_png_device -- {k_out_pack_png, k_out_png_sums}. */
 int rgk_scene_get_post_timing(const rgk_scene *scene, uint32_t which, double *ms, uint32_t *n);
 
 /* ---- noise estimate from two half-buffers and the variance-guided filter (DESIGN.md "Half-buffer noise estimate") ----
@@ -835,6 +837,27 @@ int rgk_output_write_png(const char *path, uint32_t xres, uint32_t yres, const u
 
 /* float -> IEEE half bits exactly as the writer stores them (exposed for the tests). */
 uint16_t rgk_float_to_half(float v);
+
+/* ---- output path on the device (DESIGN.md "Output files made on the device") ----
+ * The two files above from DEVICE memory on the scene's GPU, byte for byte what the host writers produce from host copies: the
+ * normalisation, the halves and the scan-line blocks, or the IDAT payload and the pieces of its two checksums, are made by kernels
+ * on the scene's stream; the finished bytes reach a pinned buffer of the scene in one copy, the host writes the few bytes around
+ * them there, and the file leaves in one fwrite.  Blocking; not while a round is in flight on this scene; arguments are checked
+ * before the scene, the device or the file is touched.  Each scene keeps one device byte buffer and one pinned host buffer for both
+ * entries, grown on demand and freed with the scene; nothing a round reads or writes is used, so a call between two rounds of a
+ * frame changes nothing those rounds compute.  RGK_ERR_INVALID: a NULL scene, path or image, xres or yres outside 1 .. 65535, a
+ * path that cannot be opened; RGK_ERR_DEVICE: a short write.
+ *
+ * EXR.  d_count != NULL: accumulator mode, rgk_output_normalize followed by rgk_output_write_exr -- output_scale <= 0 is "auto",
+ * and *scale_used (may be NULL) receives the scale applied.  d_count == NULL: image mode, d_rgb is a mean already and every value is
+ * multiplied by output_scale, which must be finite and > 0 (RGK_ERR_INVALID otherwise) and is applied also when it is 1. */
+int rgk_output_write_exr_device(rgk_scene *scene, const char *path, uint32_t xres, uint32_t yres,
+                                const float *d_rgb /*3P*/, const uint32_t *d_count /*P, or NULL*/,
+                                float output_scale, float *scale_used /*may be NULL*/);
+/* PNG.  d_rgba: the words rgk_display_encode_device writes.  RGK_ERR_INVALID also for an image beyond one IDAT chunk, as the host
+ * writer. */
+int rgk_output_write_png_device(rgk_scene *scene, const char *path, uint32_t xres, uint32_t yres,
+                                const uint32_t *d_rgba /*P*/);
 
 #ifdef __cplusplus
 }

@@ -59,6 +59,8 @@
                     accumulator and shared by the pictures of a round, per frame under -r.  Give FILE first, or write --png=OP.
                     Not with -d.  Without the switch every file is unchanged
   --exposure EV     needs --png: a fixed exposure scale of 2^EV (-100 .. 100) instead of the automatic one
+  --host-output     assemble every EXR and PNG on the host from downloaded copies, as before the device writers
+                    (rgk_output_write_exr_device / rgk_output_write_png_device) existed; the files are byte-identical either way
 FILE is a .json or .rtc scene config.  One process drives one GPU; several GPUs: python -m torch.distributed.run ... bench.py.
 """
 import argparse
@@ -128,6 +130,7 @@ def main(argv=None):
     ap.add_argument("--demod", action="store_true")
     ap.add_argument("--png", nargs="?", const="filmic", default=None, choices=sorted(capi.DISPLAY_OPS), metavar="OP")
     ap.add_argument("--exposure", type=float, default=None, metavar="EV")
+    ap.add_argument("--host-output", action="store_true")
     args = ap.parse_args(argv)
     verbosity = max(0, 2 + args.v - args.q)
     say = lambda lvl, *a: print(*a) if verbosity >= lvl else None
@@ -248,7 +251,7 @@ def main(argv=None):
         try:
             drv = rd.RenderDriver(scene, cfg, camera, device=device, track_noise=track_noise,
                                   adaptive=capi.AdaptParams(args.until_noise, args.adaptive) if args.adaptive is not None else None, history=history,
-                                  aov_hops=aov_hops, **(dict(track_demod=True) if args.demod else {}))
+                                  aov_hops=aov_hops, device_output=not args.host_output, **(dict(track_demod=True) if args.demod else {}))
         except ValueError as e:
             print(f"ERROR: {e}")
             return 1

@@ -10,8 +10,8 @@ import tempfile
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "librgk_hip.so")
-SOURCES = ["rgk_kernels.hip", "rgk_shade_kernels.hip", "rgk_post.hip", "rgk_build.hip", "rgk_scene.cpp", "rgk_round.cpp", "rgk_probe.cpp", "rgk_post_host.cpp", "rgk_commit.cpp", "rgk_output.cpp", "rgk_accum.cpp", "rgk_comm.cpp"]
-HEADERS = ["rgk_kernels.h", "rgk_plan.h", "rgk_ring.h", "rgk_round_plan.h", "rgk_scene_impl.h", "rgk_adapt.h", "rgk_build.h", "rgk_commit.h", "rgk_tree.h", "rgk_device.h", "rgk_trace.h", "rgk_shade.h", "rgk_bdpt.h", "rgk_resolve.h", "rgk_probe_kernels.h", "rgk_entry.h", "rgk_poison.h", "rgk_display.h", "device_types.h", os.path.join("..", "..", "include", "rgk.h"), os.path.join("..", "..", "include", "rgk_libm.h")]
+SOURCES = ["rgk_kernels.hip", "rgk_shade_kernels.hip", "rgk_post.hip", "rgk_pack.hip", "rgk_build.hip", "rgk_scene.cpp", "rgk_round.cpp", "rgk_probe.cpp", "rgk_post_host.cpp", "rgk_commit.cpp", "rgk_output.cpp", "rgk_accum.cpp", "rgk_comm.cpp"]
+HEADERS = ["rgk_kernels.h", "rgk_plan.h", "rgk_ring.h", "rgk_round_plan.h", "rgk_scene_impl.h", "rgk_adapt.h", "rgk_build.h", "rgk_commit.h", "rgk_tree.h", "rgk_device.h", "rgk_trace.h", "rgk_shade.h", "rgk_bdpt.h", "rgk_resolve.h", "rgk_probe_kernels.h", "rgk_entry.h", "rgk_poison.h", "rgk_display.h", "rgk_pack.h", "device_types.h", os.path.join("..", "..", "include", "rgk.h"), os.path.join("..", "..", "include", "rgk_libm.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
          # CPU/GPU agreement: no FMA contraction on either side (DESIGN.md "Numerics")
          "-ffp-contract=off", "-fno-fast-math", "-Wall", "-Wno-unused-function", "-x", "hip"]

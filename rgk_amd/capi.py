@@ -260,7 +260,8 @@ EXPORTS = ["rgk_last_error", "rgk_device_count", "rgk_scene_create", "rgk_scene_
            "rgk_temporal_reproject_device", "rgk_temporal_blend_device",
            "rgk_render_aov_chain_device", "rgk_render_aov_chain", "rgk_debug_poisoned_bytes", "rgk_upsample_device",
            "rgk_render_round_demod_device", "rgk_remodulate_device",
-           "rgk_display_table", "rgk_display_solve", "rgk_display_measure_device", "rgk_display_encode_device", "rgk_output_write_png"]
+           "rgk_display_table", "rgk_display_solve", "rgk_display_measure_device", "rgk_display_encode_device", "rgk_output_write_png",
+           "rgk_output_write_exr_device", "rgk_output_write_png_device"]
 AOV_MAX_HOPS = 8  # RGK_AOV_MAX_HOPS
 DEMOD_ALBEDO_FLOOR = 0.02  # the floor demodulated rounds ship with: the temporal and upsample stages' value
 
@@ -346,6 +347,8 @@ def _bind(lib):
     lib.rgk_display_measure_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, _p(DisplayParams), _p(DisplayStats)]
     lib.rgk_display_encode_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, _p(DisplayParams), _p(DisplayStats), C.c_void_p]
     lib.rgk_output_write_png.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_void_p]
+    lib.rgk_output_write_exr_device.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_float, _p(C.c_float)]
+    lib.rgk_output_write_png_device.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_void_p]
     lib.rgk_scene_get_post_timing.argtypes =[C.c_void_p, C.c_uint32, _p(C.c_double), _p(C.c_uint32)]
     lib.rgk_float_to_half.argtypes = [C.c_float]
     lib.rgk_float_to_half.restype = C.c_uint16

@@ -170,3 +170,17 @@ void rgk_launch_remodulate(hipStream_t st, size_t P, const float* in_rgb, const 
 void rgk_launch_display_hist(hipStream_t st, size_t P, const float* rgb, const uint32_t* count, uint32_t* hist);
 void rgk_launch_display_encode(hipStream_t st, size_t P, const float* rgb, const uint32_t* count, const float* table, uint32_t op, float exposure, float white,
                                uint32_t* out);
+// device output path (rgk_pack.hip, arithmetic: rgk_pack.h).  All pointers into the scene's one output byte buffer are 16-byte
+// aligned by the caller.
+//   out_max: the auto scale 1 / max of rgb / count over the counted pixels into *val, by way of `partial` (RGK_OUT_MAX_WGS floats, every
+//            one written by the first launch before the one-workgroup second launch reads it)
+//   out_pack_exr: the pixel-data region of the EXR file image (rgk_pack_exr_data_bytes) into out; count NULL: image mode; d_val NULL:
+//            scale by `val`, else by *d_val
+//   out_pack_png: the IDAT payload (rgk_pack_png_payload_bytes) into out, from one R, G, B, x word per pixel
+//   out_png_sums: per piece of RGK_PACK_SEGMENT bytes the Adler pair of the raw stream (2 words each), then the CRCs of the pieces of
+//            "IDAT" + payload (1 word each), into sums
+constexpr uint32_t RGK_OUT_MAX_WGS = 1024;
+void rgk_launch_out_max(hipStream_t st, size_t P, const float* rgb, const uint32_t* count, float* partial, float* val);
+void rgk_launch_out_pack_exr(hipStream_t st, uint32_t xres, uint32_t yres, const float* rgb, const uint32_t* count, float val, const float* d_val, uint8_t* out);
+void rgk_launch_out_pack_png(hipStream_t st, uint32_t xres, uint32_t yres, const uint32_t* rgba, uint8_t* out);
+void rgk_launch_out_png_sums(hipStream_t st, uint32_t xres, uint32_t yres, const uint8_t* payload, uint32_t* sums);

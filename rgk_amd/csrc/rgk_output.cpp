@@ -1,6 +1,9 @@
-// Output path: normalise the accumulator the way RenderFrame does after every round and write
-// the half-float RGBA OpenEXR file; and the PNG container of the display stage's bytes.  Host code, no device work: the reference does this once per round on the
-// host as well (src/render_driver.cpp:229-247), O(pixels).
+// Output path, the host writers: normalise the accumulator the way RenderFrame does after every round and write
+// the half-float RGBA OpenEXR file; and the PNG container of the display stage's bytes.  Host code on host buffers, no device work,
+// as the reference does it (src/render_driver.cpp:229-247).  A frame that lives on the device does not come through here any more:
+// rgk_output_write_exr_device / rgk_output_write_png_device (rgk_post_host.cpp, kernels rgk_pack.hip, arithmetic rgk_pack.h) assemble
+// the same files, byte for byte, where the image is.  These writers stay as they are: they serve host buffers and CPU tensors, and
+// they are the reference the device path is tested against.
 #include <cmath>
 #include <cstdint>
 #include <cstdio>

@@ -1,11 +1,14 @@
 // The post-processing entries: feature buffers, both denoisers, the noise estimate, tile selection, the round fold, temporal reuse and
-// guided upsampling and the display output (kernels: rgk_post.hip).
+// guided upsampling and the display output (kernels: rgk_post.hip), and the output files made on the device (kernels: rgk_pack.hip).
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
+#include <cstring>
 
 #include "rgk_scene_impl.h"
 #include "rgk_adapt.h"
 #include "rgk_display.h"
+#include "rgk_pack.h"
 
 namespace {
 // HIP events (the scene's pool, from its first) around the launches of one post call, when the scene's "time_post" switch is on.
@@ -156,6 +159,35 @@ int check_display_args(const rgk_scene* s, uint32_t xres, uint32_t yres, const f
     if (!s || !d_rgb || !p) return fail(RGK_ERR_INVALID, "null argument");
     if (int rc = check_frame_size(xres, yres)) return rc;
     if (const char* why = rgk_display_check_params(p)) return fail(RGK_ERR_INVALID, "display parameters: %s", why);
+    return RGK_OK;
+}
+
+// ---- output files made on the device
+struct PackCrcTable {
+    uint32_t t[256];
+    PackCrcTable() { rgk_pack_crc_table(t); }
+};
+const uint32_t* pack_crc_table() {
+    static const PackCrcTable t; // built once, by the first caller
+    return t.t;
+}
+// The scene's pinned buffer with room for `bytes`; it only grows.  (The caller has waited for every copy into the old one.)
+int pinned_room(rgk_scene* s, size_t bytes) {
+    if (s->out_pin && s->out_pin_n >= bytes) return 0;
+    if (s->out_pin) (void)hipHostFree(s->out_pin);
+    s->out_pin = nullptr; s->out_pin_n = 0;
+    hipError_t e = hipHostMalloc((void**)&s->out_pin, bytes);
+    if (e != hipSuccess) { s->out_pin = nullptr; return fail(RGK_ERR_OOM, "hipHostMalloc(%zu bytes): %s", bytes, hipGetErrorString(e)); }
+    s->out_pin_n = bytes;
+    return 0;
+}
+// one fwrite of a finished file image; the host writers' two errors
+int write_file(const char* entry, const char* path, const uint8_t* image, size_t bytes) {
+    FILE* f = std::fopen(path, "wb");
+    if (!f) return fail(RGK_ERR_INVALID, "%s: cannot open the output file", entry);
+    const size_t w = std::fwrite(image, 1, bytes, f);
+    const int rc = std::fclose(f);
+    if (w != bytes || rc != 0) return fail(RGK_ERR_DEVICE, "%s: short write", entry);
     return RGK_OK;
 }
 } // namespace
@@ -490,6 +522,83 @@ int rgk_display_encode_device(rgk_scene* s, uint32_t xres, uint32_t yres, const 
         rgk_launch_display_encode(s->stream, (size_t)xres * yres, d_rgb, d_count, s->disp_table.p, op, exposure, white, d_out_rgba);
         return tm.mark();
     });
+}
+
+// ---- output files made on the device (kernels: rgk_pack.hip; arithmetic and file layout: rgk_pack.h)
+// Both entries: the pack kernels fill the scene's output byte buffer, ONE copy brings the file's device-made region -- and, behind
+// it, the scale word or the checksum pieces -- into the scene's pinned buffer, where the host has written or then writes the bytes
+// around it; one fwrite.  The buffers are the entries' own: nothing a round reads or writes.
+
+int rgk_output_write_exr_device(rgk_scene* s, const char* path, uint32_t xres, uint32_t yres, const float* d_rgb, const uint32_t* d_count, float output_scale,
+                                float* scale_used) {
+    if (!s || !path || !d_rgb) return fail(RGK_ERR_INVALID, "rgk_output_write_exr_device: null argument");
+    if (int rc = check_frame_size(xres, yres)) return rc;
+    if (!d_count && !(std::isfinite(output_scale) && output_scale > 0.0f))
+        return fail(RGK_ERR_INVALID, "rgk_output_write_exr_device: without a count plane output_scale must be > 0 and finite");
+    const bool automatic = d_count && output_scale <= 0.0f; // (the host's `val <= 0`: a NaN scale is applied as it is, there and here)
+    const size_t head = rgk_pack_exr_data_at(yres), data = rgk_pack_exr_data_bytes(xres, yres);
+    const size_t val_at = data, partial_at = (data + 4 + 15) & ~(size_t)15; // in the device buffer; data is a multiple of 8
+    const size_t copy = automatic ? data + 4 : data;
+    const size_t pad = (64 - head % 64) % 64; // the pinned image starts here, so that the copy lands on a 64-byte boundary
+    int rc = post_call(s, "rgk_output_write_exr_device", POST_OUTPUT_EXR, true, [&](PostTimer& tm) -> int {
+        int rc;
+        if ((rc = s->out_dev.alloc(partial_at + RGK_OUT_MAX_WGS * sizeof(float))) || (rc = pinned_room(s, pad + head + data + 4))) return rc;
+        uint8_t* const d = s->out_dev.p;
+        float* const d_val = (float*)(d + val_at);
+        if ((rc = tm.mark())) return rc;
+        if (automatic) {
+            rgk_launch_out_max(s->stream, (size_t)xres * yres, d_rgb, d_count, (float*)(d + partial_at), d_val);
+            if ((rc = tm.mark())) return rc;
+        }
+        rgk_launch_out_pack_exr(s->stream, xres, yres, d_rgb, d_count, output_scale, automatic ? d_val : nullptr, d);
+        if ((rc = tm.mark())) return rc;
+        HIPCHK(hipMemcpyAsync(s->out_pin + pad + head, d, copy, hipMemcpyDeviceToHost, s->stream));
+        rgk_pack_exr_head(s->out_pin + pad, xres, yres); // (host bytes in front of the region the copy fills)
+        return 0;
+    });
+    if (rc) return rc;
+    std::vector<double>& ms = s->post_ms[POST_OUTPUT_EXR];
+    if (!automatic && !ms.empty()) ms.insert(ms.begin(), 0.0); // {k_out_max or 0, pack}
+    float val = output_scale;
+    if (automatic) std::memcpy(&val, s->out_pin + pad + head + data, 4);
+    if (scale_used) *scale_used = val;
+    return write_file("rgk_output_write_exr_device", path, s->out_pin + pad, head + data);
+}
+
+int rgk_output_write_png_device(rgk_scene* s, const char* path, uint32_t xres, uint32_t yres, const uint32_t* d_rgba) {
+    if (!s || !path || !d_rgba) return fail(RGK_ERR_INVALID, "rgk_output_write_png_device: null argument");
+    if (int rc = check_frame_size(xres, yres)) return rc;
+    if (!rgk_pack_png_fits(xres, yres)) return fail(RGK_ERR_INVALID, "rgk_output_write_png_device: the image does not fit one IDAT chunk");
+    const uint32_t raw = (uint32_t)rgk_pack_png_raw_bytes(xres, yres), payload = (uint32_t)rgk_pack_png_payload_bytes(raw);
+    const uint32_t n_adler = rgk_pack_pieces(raw, RGK_PACK_SEGMENT), n_crc = rgk_pack_pieces((uint64_t)payload + 4u, RGK_PACK_SEGMENT);
+    const size_t sums_at = ((size_t)payload + 3) & ~(size_t)3, n_sums = (size_t)2 * n_adler + n_crc; // the kernel writes zeros up to sums_at
+    const size_t copy = sums_at + 4 * n_sums;
+    const size_t pad = (64 - RGK_PACK_PNG_LEAD % 64) % 64;
+    int rc = post_call(s, "rgk_output_write_png_device", POST_OUTPUT_PNG, true, [&](PostTimer& tm) -> int {
+        int rc;
+        if ((rc = s->out_dev.alloc(copy)) || (rc = pinned_room(s, pad + RGK_PACK_PNG_LEAD + copy + RGK_PACK_PNG_TAIL))) return rc;
+        uint8_t* const d = s->out_dev.p;
+        if ((rc = tm.mark())) return rc;
+        rgk_launch_out_pack_png(s->stream, xres, yres, d_rgba, d);
+        if ((rc = tm.mark())) return rc;
+        rgk_launch_out_png_sums(s->stream, xres, yres, d, (uint32_t*)(d + sums_at));
+        if ((rc = tm.mark())) return rc;
+        HIPCHK(hipMemcpyAsync(s->out_pin + pad + RGK_PACK_PNG_LEAD, d, copy, hipMemcpyDeviceToHost, s->stream));
+        rgk_pack_png_lead(s->out_pin + pad, pack_crc_table(), xres, yres, payload);
+        return 0;
+    });
+    if (rc) return rc;
+    uint8_t* const image = s->out_pin + pad;
+    std::vector<uint32_t> sums(n_sums); // (out of the way of the tail, which is written where they arrived)
+    std::memcpy(sums.data(), image + RGK_PACK_PNG_LEAD + sums_at, 4 * n_sums);
+    RgkPackAdler adler;
+    for (uint32_t k = 0; k < n_adler; k++) {
+        const uint32_t left = raw - k * RGK_PACK_SEGMENT;
+        adler.add(sums[2 * k], sums[2 * k + 1], left < RGK_PACK_SEGMENT ? left : RGK_PACK_SEGMENT);
+    }
+    const uint32_t crc = rgk_pack_crc_fold(sums.data() + 2 * (size_t)n_adler, (uint64_t)payload + 4u, RGK_PACK_SEGMENT);
+    rgk_pack_png_tail(image + RGK_PACK_PNG_LEAD + payload, pack_crc_table(), adler.value(), crc);
+    return write_file("rgk_output_write_png_device", path, image, RGK_PACK_PNG_LEAD + (size_t)payload + RGK_PACK_PNG_TAIL);
 }
 
 int rgk_scene_get_post_timing(const rgk_scene* s, uint32_t which, double* ms, uint32_t* n) {

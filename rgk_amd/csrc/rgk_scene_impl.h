@@ -2,7 +2,7 @@
 //   rgk_scene.cpp      create / refit / tuning / progress, the workspace, task list and camera
 //   rgk_round.cpp      the round driver (rgk_render_round[_device])
 //   rgk_probe.cpp      the unit-level entries the parity tests call
-//   rgk_post_host.cpp  feature pass, denoisers, noise estimate, round fold, temporal reuse, upsampling, display output
+//   rgk_post_host.cpp  feature pass, denoisers, noise estimate, round fold, temporal reuse, upsampling, display output, output files
 // The arithmetic that needs no device is in rgk_round_plan.h, rgk_plan.h, rgk_adapt.h and rgk_commit.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -88,7 +88,7 @@ struct RgkTuning {
 };
 
 // rgk_scene_get_post_timing's `which` (rgk.h): the post-processing call whose launch times a slot holds
-enum PostSlot : uint32_t { POST_AOV = 0, POST_DENOISE = 1, POST_DENOISE_VARIANCE = 2, POST_NOISE = 3, POST_FOLD = 4, POST_TEMPORAL = 5, POST_AOV_CHAIN = 6, POST_UPSAMPLE = 7, POST_REMODULATE = 8, POST_DEMOD_ROUND = 9, POST_DISPLAY_MEASURE = 10, POST_DISPLAY_ENCODE = 11, POST_SLOTS = 12 };
+enum PostSlot : uint32_t { POST_AOV = 0, POST_DENOISE = 1, POST_DENOISE_VARIANCE = 2, POST_NOISE = 3, POST_FOLD = 4, POST_TEMPORAL = 5, POST_AOV_CHAIN = 6, POST_UPSAMPLE = 7, POST_REMODULATE = 8, POST_DEMOD_ROUND = 9, POST_DISPLAY_MEASURE = 10, POST_DISPLAY_ENCODE = 11, POST_OUTPUT_EXR = 12, POST_OUTPUT_PNG = 13, POST_SLOTS = 14 };
 constexpr uint32_t RGK_SCENE_MAGIC = 0x53474b52u; // "RKGS": what a live scene handle starts with (rgk_scene_get_post_timing)
 struct rgk_scene {
     uint32_t magic = RGK_SCENE_MAGIC;
@@ -163,6 +163,10 @@ struct rgk_scene {
     // display output (rgk_display_measure_device / rgk_display_encode_device), allocated by the first call of either
     DevBuf<uint32_t> disp_hist;         // 256 bins, then the dark count; cleared on the stream by every measure before its launch
     DevBuf<float> disp_table;           // the 256 thresholds of the sRGB bytes (rgk_display_table), uploaded once
+    // device output path (rgk_output_write_exr_device / rgk_output_write_png_device), allocated by the first call of either, grown on demand
+    DevBuf<uint8_t> out_dev;            // what the pack kernels write: the file region, then the scale word and partial maxima / the checksum pieces
+    uint8_t* out_pin = nullptr;         // pinned: the whole file image, the device's part arriving in one copy
+    size_t out_pin_n = 0;
     std::vector<double> post_ms[POST_SLOTS]; // launch times of the last call of each kind (tuning "time_post")
     std::vector<hipEvent_t> events;
     uint32_t* h_counters = nullptr; // pinned
@@ -180,6 +184,7 @@ struct rgk_scene {
         for (auto e : events) (void)hipEventDestroy(e);
         if (h_counters) (void)hipHostFree(h_counters);
         if (h_stage) (void)hipHostFree(h_stage);
+        if (out_pin) (void)hipHostFree(out_pin);
         if (stream) (void)hipStreamDestroy(stream);
     }
 };

@@ -252,12 +252,25 @@ class Scene:
         params.check()
         capi.check(self.lib, self.lib.rgk_display_encode_device(self.h, xres, yres, d_rgb, d_count, C.byref(params), C.byref(stats), d_out_rgba))
 
+    def write_exr_device(self, path, xres, yres, d_rgb, d_count=None, output_scale=1.0):
+        """rgk_output_write_exr_device: the EXR the host writers produce, assembled on the GPU from DEVICE pointers (ints).  d_count:
+        accumulator mode (output_scale <= 0: auto); None: d_rgb is an image and output_scale (> 0, finite) multiplies it.  Returns the
+        scale applied."""
+        val = C.c_float(0.0)
+        capi.check(self.lib, self.lib.rgk_output_write_exr_device(self.h, str(path).encode(), xres, yres, d_rgb, d_count, float(output_scale), C.byref(val)))
+        return val.value
+
+    def write_png_device(self, path, xres, yres, d_rgba):
+        """rgk_output_write_png_device: the PNG rgk_output_write_png produces, from the words of display_encode_device on the device."""
+        capi.check(self.lib, self.lib.rgk_output_write_png_device(self.h, str(path).encode(), xres, yres, d_rgba))
+
     def post_timing(self, which):
         """HIP-event times (ms) of the launches of the last feature pass (0) / denoise call (1) / variance-guided denoise call (2) /
         noise estimate (3) / round fold (4: the copy of its tile list, the fold) / temporal pair (5: reproject, blend) /
         followed feature pass (6: list + ray generation, then walker and k_aov_hop per hop) / upsample call (7: prepare, gather) /
         remodulate call (8) / demodulated round (9: its divisor launches, its second resolves, summed over the passes) /
-        display measure (10: the clear of the histogram, k_display_hist) / display encode (11: k_display_encode);
+        display measure (10: the clear of the histogram, k_display_hist) / display encode (11: k_display_encode) /
+        device EXR (12: k_out_max or 0, k_out_pack_exr) / device PNG (13: k_out_pack_png, k_out_png_sums);
         set_tuning(time_post=1) first."""
         ms, n = (C.c_double * 32)(), C.c_uint32(32)
         capi.check(self.lib, self.lib.rgk_scene_get_post_timing(self.h, which, ms, C.byref(n)))
@@ -362,6 +375,36 @@ def write_png(path, rgba):
     capi.check(lib, lib.rgk_output_write_png(str(path).encode(), rgba.shape[1], rgba.shape[0], rgba.ctypes.data))
 
 
+def on_scene_gpu(scene, *tensors):
+    """Whether the device writers can take these tensors: a scene, and every tensor on its GPU."""
+    return scene is not None and all(t.is_cuda and t.device.index == scene.device for t in tensors)
+
+
+def write_exr_image(path, image, val=1.0, scene=None):
+    """The EXR of image * val, image a (y, x, 3) float32 torch tensor: through rgk_output_write_exr_device when `scene` is given, the
+    tensor lives on its GPU and val is finite and > 0; else write_exr of a host copy.  The same bytes either way."""
+    import math
+    import torch
+    if on_scene_gpu(scene, image) and math.isfinite(val) and val > 0.0:
+        image = image.contiguous()
+        torch.cuda.current_stream(image.device).synchronize()
+        scene.write_exr_device(path, int(image.shape[1]), int(image.shape[0]), image.data_ptr(), None, val)
+    else:
+        write_exr(path, (image * val).cpu().numpy())
+
+
+def write_png_image(path, rgba, scene=None):
+    """The PNG of a (y, x, 4) uint8 torch tensor: through rgk_output_write_png_device when `scene` is given and the tensor lives on its
+    GPU; else write_png of a host copy.  The same bytes either way."""
+    import torch
+    if on_scene_gpu(scene, rgba) and rgba.dim() == 3 and rgba.shape[2] == 4 and rgba.dtype == torch.uint8:
+        rgba = rgba.contiguous()
+        torch.cuda.current_stream(rgba.device).synchronize()
+        scene.write_png_device(path, int(rgba.shape[1]), int(rgba.shape[0]), rgba.data_ptr())
+    else:
+        write_png(path, rgba)
+
+
 def png_beside(path):
     """The PNG that goes with an EXR: the same stem."""
     import os
@@ -390,9 +433,14 @@ class EXRTexture:
             val = 1.0 / float(px.max())
         return px * val
 
-    def write(self, path, output_scale=-1.0):
+    def write(self, path, output_scale=-1.0, scene=None):
         """total_ob.Normalize(cfg->output_scale).Write(output_file) (render_driver.cpp:233,245) through the C ABI:
-        rgk_output_normalize + rgk_output_write_exr on host copies of the accumulator.  Returns the scale used."""
+        rgk_output_normalize + rgk_output_write_exr on host copies of the accumulator -- or, with `scene` and the accumulator on its
+        GPU, rgk_output_write_exr_device where it is: the same bytes.  Returns the scale used."""
+        if on_scene_gpu(scene, self.data, self.count):
+            import torch
+            torch.cuda.current_stream(self.data.device).synchronize()
+            return scene.write_exr_device(path, self.xsize, self.ysize, self.data.data_ptr(), self.count.data_ptr(), float(output_scale))
         lib = capi.load_product()
         acc = np.ascontiguousarray(self.data.cpu().numpy(), dtype=np.float32)
         cnt = np.ascontiguousarray(self.count.cpu().numpy()).view(np.uint32)
@@ -477,8 +525,12 @@ class RenderDriver:
 
     def __init__(self, scene, cfg, camera, rank=0, world_size=1, device=None, sampler=capi.SAMPLER_HALTON, flags=0,
                  host_reduce=False, track_noise=False, adaptive=None, history=None, aov_hops=0, track_demod=False,
-                 albedo_floor=capi.DEMOD_ALBEDO_FLOOR):
+                 albedo_floor=capi.DEMOD_ALBEDO_FLOOR, device_output=True):
         import torch
+        # device_output: render_frame's EXR and PNG files are assembled on the GPU (rgk_output_write_exr_device /
+        # rgk_output_write_png_device) when the tensors live on the scene's GPU; False: on the host from downloaded copies, which CPU
+        # tensors get anyway.  The files are byte-identical.
+        self.device_output = bool(device_output)
         # track_demod: rounds go through rgk_render_round_demod_device and keep, beside total_ob (which gets the bits it gets without),
         # demod_ob = D, the sum of each sample's radiance over the floored albedo at ITS OWN first hit, and div_ob = A, the sum of those
         # divisors; denoise() and upsample() then filter D / n with demodulate = 0 and multiply back (rgk_remodulate_device).
@@ -986,13 +1038,14 @@ class RenderDriver:
                 raise ValueError("display needs an output_file")
             display.check()
         self.display_stats = None
+        out_scene = self.scene if self.device_output else None  # the device writers' scene; None: the host writers
 
         def picture(path, image=None):
             """The PNG beside `path`: the accumulator's (which measures), or an image's with the accumulator's exposure."""
             if display is not None:
                 rgba, st = self.display(image, display, None if image is None else self.display_stats)
                 self.display_stats = st
-                write_png(png_beside(path), rgba)
+                write_png_image(png_beside(path), rgba, out_scene)
         if irradiance_file and (not self.track_demod or not output_file):
             raise ValueError("irradiance_file needs a driver made with track_demod=True and an output_file")
         if upsampled_file and (upsample_to is None or not output_file or self.track_noise or self.history is not None or self.aov_hops > 0):
@@ -1012,7 +1065,7 @@ class RenderDriver:
             for name, path in aov_files.items():
                 src = self.aov_hops_plane().float() if name == "hops" else a[name]
                 plane = src if src.dim() == 3 else src.unsqueeze(-1).expand(-1, -1, 3)
-                write_exr(path, plane.cpu().numpy())
+                write_exr_image(path, plane, 1.0, out_scene)
         if adapting and self.rounds_done >= 2:  # resumed
             live, _, done = self.adapt_select(until_noise)
             if done:
@@ -1023,24 +1076,24 @@ class RenderDriver:
                 break
             self.render_round(live=live)
             if output_file and self.rank == 0:
-                val = self.total_ob.write(output_file, getattr(self.cfg, "output_scale", -1.0))
+                val = self.total_ob.write(output_file, getattr(self.cfg, "output_scale", -1.0), out_scene)
                 picture(output_file)
                 if self.track_noise and self.rounds_done >= 2 and (denoised_file or noise_file):
                     den, var = self.denoise_variance()
                     if denoised_file:
-                        write_exr(denoised_file, (den * val).cpu().numpy())
+                        write_exr_image(denoised_file, den, val, out_scene)
                         picture(denoised_file, den)
                     if noise_file:
-                        write_exr(noise_file, (var.sqrt() * val).unsqueeze(-1).expand(-1, -1, 3).cpu().numpy())
+                        write_exr_image(noise_file, var.sqrt().unsqueeze(-1).expand(-1, -1, 3), val, out_scene)
                 elif denoised_file:
                     den = self.denoise()
-                    write_exr(denoised_file, (den * val).cpu().numpy())
+                    write_exr_image(denoised_file, den, val, out_scene)
                     picture(denoised_file, den)
                 if irradiance_file:
-                    write_exr(irradiance_file, (self.irradiance() * val).cpu().numpy())
+                    write_exr_image(irradiance_file, self.irradiance(), val, out_scene)
                 if upsampled_file:
                     up = self.upsample(*upsample_to, denoise=True if denoised_file else None)[0]
-                    write_exr(upsampled_file, (up * val).cpu().numpy())
+                    write_exr_image(upsampled_file, up, val, out_scene)
                     picture(upsampled_file, up)
             if checkpoint and self.rank == 0:
                 self.save_checkpoint(checkpoint)
@@ -1058,6 +1111,6 @@ class RenderDriver:
                 break
         if temporal and val is not None and self.rank == 0:
             den = self.denoise_temporal()
-            write_exr(denoised_file, (den * val).cpu().numpy())
+            write_exr_image(denoised_file, den, val, out_scene)
             picture(denoised_file, den)
         return self.total_ob

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Device code of two checkouts, compared kernel by kernel (no GPU needed): tools/device_code_diff.sh <parent-tree> <head-tree>
 #
-# Compiles rgk_kernels.hip, rgk_shade_kernels.hip, rgk_post.hip and rgk_build.hip of both trees to gfx950 assembly with the command
+# Compiles rgk_kernels.hip, rgk_shade_kernels.hip, rgk_post.hip, rgk_pack.hip and rgk_build.hip of both trees to gfx950 assembly with the command
 # recorded in profiles/host_split_device_code.txt (per source: the flags rgk_amd/build.py SOURCE_FLAGS gives it), normalises what
 # differs between two checkouts of the SAME source (the checkout path and the compilation-unit word __hip_cuid_<16 hex digits>)
 # and prints
@@ -15,7 +15,7 @@ HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 command -v "$HIPCC" >/dev/null || { echo "$0: no hipcc ($HIPCC)" >&2; exit 2; }
 CXXFILT=$(dirname "$(readlink -f "$(command -v "$HIPCC")")")/../llvm/bin/llvm-cxxfilt
 [ -x "$CXXFILT" ] || CXXFILT=$(command -v llvm-cxxfilt || command -v c++filt || echo cat)
-SOURCES="rgk_kernels rgk_shade_kernels rgk_post rgk_build"
+SOURCES="rgk_kernels rgk_shade_kernels rgk_post rgk_pack rgk_build"
 # rgk_amd/build.py SOURCE_FLAGS: the shading kernels are built without SLP vectorisation
 source_flags() { case $1 in rgk_shade_kernels) echo -fno-slp-vectorize ;; esac; }
 work=$(mktemp -d) || exit 2
